@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """videos/s of the DCVGAN G+D training iteration on MI355X (default: config/isogd-depth.yml, B = 70 per GPU, fp32).
 
-    python bench.py --gpus N --steps K --warmup W [--config isogd-depth|surreal-depth1|isogd-flow]
+    python bench.py --gpus N --steps K --warmup W [--config isogd-depth|surreal-depth1|isogd-flow] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline.  --full adds everything else this script measures (CPU
+baseline, minimal-schedule, as-trainer and 16-bit secondary legs, the dominant-kernel probe and its committed traffic; for N > 1 the
+per-phase collective times and the overlapped-reduction leg), each still skippable by its --no-* option.  --dump-outputs DIR writes
+what the last timed step computed (dump_outputs) before anything else runs.
 
 Both forms work for N > 1: under a launcher (WORLD_SIZE set) this process IS a rank; without one the parent — before any
 HIP call — starts N fresh child processes of this script (one per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set),
@@ -22,8 +27,8 @@ Rank 0 prints ONE JSON line.
                 (2 * M * OC * K FLOP per launch), timed alone with HIP events on the stream it is launched on.  `traffic`
                 (HBM bytes per iteration / per launch of the dominant kernel from rocprofv3 PMC passes) cannot be
                 collected from inside the process: it is read from the committed profile of the SAME kernel sources
-                (sha256), config and batch size, else null.
-  cpu_baseline  the CPU oracle's step (pure-torch restatement of the reference trainer, pinned to the reference by
+                (sha256), config and batch size, else null.  `dominant_kernel` is measured with --full only.
+  cpu_baseline  (--full only) the CPU oracle's step (pure-torch restatement of the reference trainer, pinned to the reference by
                 tests/golden) on this host's cores — rank 0, N = 1 only.
 """
 import argparse
@@ -64,12 +69,15 @@ def parse():
     ap.add_argument("--no-as-trainer", action="store_true", help="skip the secondary `as_trainer` key: the same iteration driven the way the reference's "
                                                                  "trainer.py drives it (4 host syncs on the losses, :326-328,363; a fresh pinned host batch "
                                                                  ".to(device) per iteration, :293-297), timed AFTER the headline region")
-    ap.add_argument("--minimal", action="store_true", help="(default; kept for older command lines)")
+    ap.add_argument("--minimal", action="store_true", help="(kept for older command lines; the `minimal_schedule` leg runs with --full)")
     ap.add_argument("--no-minimal", action="store_true", help="skip the secondary `minimal_schedule` key (the schedule with the dead D-phase generator backward elided, "
                                                               "timed AFTER the headline region) — profile runs use this so that the trace holds the as-written schedule only")
     ap.add_argument("--no-secondary", action="store_true", help="skip the `secondary_precisions` key: short runs of the 16-bit paths (bf16 channels-last data path on "
                                                                 "surreal-depth1 — the config BASELINE names for bf16 — and on the headline config; fp32-on-bf16 on the headline config), timed AFTER everything else")
     ap.add_argument("--cpus", type=int, default=0, help="pin this rank to K host CPUs (host-headroom probe: 8 ranks on a 16-CPU share have 2 each)")
+    ap.add_argument("--full", action="store_true", help="also run every secondary measurement (CPU baseline, minimal / as-trainer / 16-bit legs, dominant-kernel probe, "
+                                                        "N > 1 collective times and dp_overlap leg); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the losses and the models' state after the last timed step to DIR/<name>.npy (dump_outputs)")
     return ap.parse_args()
 
 
@@ -333,6 +341,30 @@ def cpu_baseline(cfg, batch, steps):
                       f"batch {batch}, {cfg.name} widths, fp32, {dt:.2f} s/step"}
 
 
+DUMP_STATE_ELEMENTS = 15_000_000    # 60 MB of float32: the model state a dump may hold, under the 64 MB cap with room for the loss files
+
+
+def dump_outputs(d, losses, models):
+    """What a caller of the timed step holds after its last step: the returned losses (DIR/<loss name>.npy, float64, shape (1,)) and
+    each model's updated floating-point state — parameters, then BatchNorm buffers, in state_dict order, flattened to float32
+    (DIR/state_<model>.npy).  The full-width models hold 71-86 MB: above DUMP_STATE_ELEMENTS in all, every element is kept with
+    probability DUMP_STATE_ELEMENTS / total, drawn by a numpy generator seeded with the model's place in name order, so the positions
+    depend on the configuration alone and two runs or builds are compared element for element.  (numpy, not torch's CPU ops: a rank's
+    torch thread count is its NUMA node's CPU count, which can be far above its CPU quota; a torch randperm + sort took 8 s there.)"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for k, v in losses.items():
+        np.save(os.path.join(d, f"{k}.npy"), np.array([float(v)], dtype=np.float64))
+    flat = {n: torch.cat([t.detach().reshape(-1).float() for t in m.state_dict().values() if t.is_floating_point()]).cpu().numpy()
+            for n, m in models.items()}
+    total = sum(f.size for f in flat.values())
+    for i, n in enumerate(sorted(flat)):
+        f = flat[n]
+        if total > DUMP_STATE_ELEMENTS:
+            f = f[np.random.default_rng(i).random(f.size, dtype=np.float32) < DUMP_STATE_ELEMENTS / total]
+        np.save(os.path.join(d, f"state_{n}.npy"), f)
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -375,7 +407,7 @@ def main():
     B = cfg.batchsize
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline(CONFIGS[a.config], a.cpu_batch, a.cpu_steps)
 
     if a.precision == "bf16cl":
@@ -423,12 +455,15 @@ def main():
     peak_mem_headline = torch.cuda.max_memory_allocated(dev)      # the headline iteration's own peak: read before any secondary leg allocates
     losses = {k: float(v) for k, v in out.items()}
     assert all(x == x and abs(x) < 1e4 for x in losses.values()), losses
+    if a.dump_outputs and rank == 0:        # before any secondary leg steps the same models on
+        dump_outputs(a.dump_outputs, out, models)
 
     # data parallel: what the communicator really is, the collectives' own time, and the overlapped reduction timed against the headline's — all AFTER the headline region
     dp_info = None
     if world > 1:
         dp_info = {"world": dist.get_world_size(), "backend": dist.get_backend(), "rccl_world": dist.get_world_size() if dist.get_backend() == "nccl" else None,
                    "rank0_device": str(dev), "devices_visible": torch.cuda.device_count()}
+    if world > 1 and a.full:
         try:
             bD, bG = opts["idis"].bucket, opts["ggen"].bucket
             bD.timed, bG.timed = [], []
@@ -450,7 +485,7 @@ def main():
 
     # secondary, clearly labelled, timed AFTER the headline region (--no-minimal skips it): identical parameter updates, the dead D-phase generator backward elided
     minimal = None
-    if not a.no_minimal:
+    if a.full and not a.no_minimal:
         runner2 = trainer.StepRunner(cfg, models, opts, trainer.build_loss(cfg), sync_losses=False, elide_dead_backward=True)
         runner2.iteration = runner.iteration
         runner2.step(xc, xg, 0)
@@ -465,7 +500,7 @@ def main():
     # .cpu().item() where trainer.py:326-328,363 read them, and every iteration starts from a fresh pinned host batch .to(device)
     # (trainer.py:293-297; the DataLoader there pins memory, train.py:101-109).  The headline above stays the HBM-resident, sync-free figure.
     as_trainer = None
-    if not a.no_as_trainer and world == 1:      # (N = 1 only: a secondary key must never be able to stall or fail a multi-rank headline run)
+    if a.full and not a.no_as_trainer and world == 1:      # (N = 1 only: a secondary key must never be able to stall or fail a multi-rank headline run)
         import itertools
         from dcvgan_amd.dataprep import DevicePrefetcher
         pin = [(xc.cpu().pin_memory(), xg.cpu().pin_memory()) for _ in range(2)]      # a loader's double buffer (DataLoader(pin_memory=True), train.py:101-109)
@@ -504,7 +539,7 @@ def main():
 
     # secondary, clearly labelled: the 16-bit paths, each on freshly built models of its config, timed after everything above
     secondary = None
-    if not a.no_secondary and world == 1 and a.precision == "fp32" and a.config == "isogd-depth" and not a.batch:
+    if a.full and not a.no_secondary and world == 1 and a.precision == "fp32" and a.config == "isogd-depth" and not a.batch:
         from dcvgan_amd import ops_cl
         secondary = {}
         legs = (("bf16cl", "surreal-depth1"), ("bf16cl", "isogd-depth"), ("f32x6", "isogd-depth"))
@@ -577,9 +612,9 @@ def main():
         vps = B * world / per_step
         f_step = flops_per_video_iteration(cfg)
         step_tflops = f_step * (B / per_step) / 1e12        # per GPU
-        probe = dominant_kernel_probe(models, cfg, dev)
+        probe = dominant_kernel_probe(models, cfg, dev) if a.full else None
         gb_step = ALGORITHMIC_HBM_GB_PER_VIDEO_ITERATION * B
-        traffic, traffic_detail = committed_traffic(B, probe["kernel"]) if a.precision == "fp32" else (None, None)
+        traffic, traffic_detail = committed_traffic(B, probe["kernel"]) if probe and a.precision == "fp32" else (None, None)
         step_traffic, step_traffic_detail = committed_step_traffic(a.config, B) if a.precision == "fp32" else (None, None)
         gating = "" if cfg.num_gen_update == 1 else f", D update every {cfg.num_gen_update} iterations (FLOPs averaged over the cycle)"
         line = {
@@ -603,7 +638,7 @@ def main():
                          "flops_per_video_step": f_step,
                          "mfma_floor_ms": f_step * B / (peak * 1e12) * 1e3,
                          "hbm_floor_ms": gb_step * (0.5 if a.precision == "bf16cl" else 1.0) / PEAK_HBM_GBPS * 1e3,
-                         "dominant_kernel": dict(probe, achieved=probe["tflops"], frac=probe["tflops"] / peak, traffic=traffic, traffic_detail=traffic_detail),
+                         "dominant_kernel": dict(probe, achieved=probe["tflops"], frac=probe["tflops"] / peak, traffic=traffic, traffic_detail=traffic_detail) if probe else None,
                          "step": {"achieved": step_tflops, "frac": step_tflops / peak, "flops_per_video_step": f_step},
                          "hbm": {"algorithmic_gb_per_step": gb_step, "achieved_gbps": gb_step / per_step, "peak_gbps": PEAK_HBM_GBPS,
                                  "frac": gb_step / per_step / PEAK_HBM_GBPS}},
@@ -618,7 +653,7 @@ def main():
         }
     else:
         line = None
-    if world > 1 and not a.no_dp_overlap:
+    if world > 1 and a.full and not a.no_dp_overlap:
         # Secondary `data_parallel.dp_overlap`: the same iteration with GradBucket(overlap=True) — per-model chunks reduced from the hook of their last gradient, on a
         # communication stream, under the rest of the backward — timed after everything else so that ONE multi-GPU run yields the A/B.  It has never met a world > 1 on
         # RCCL before the driver's run, so a watchdog guards it: if the leg is not done in time, rank 0 prints the headline line as it stands and every rank leaves.

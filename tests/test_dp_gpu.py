@@ -69,7 +69,7 @@ def test_bench_spawns_its_own_ranks(precision):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     p = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--all-ranks-on-device0", "--backend", "gloo",
-                        "--batch", "4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-minimal", "--precision", precision], env=env, capture_output=True, text=True, timeout=900)
+                        "--batch", "4", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-minimal", "--precision", precision], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -93,7 +93,7 @@ def test_bench_under_the_drivers_launcher():
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
                         os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--all-ranks-on-device0", "--backend", "gloo", "--batch", "4", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline", "--no-minimal", "--no-as-trainer", "--no-secondary"],
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--no-minimal", "--no-as-trainer", "--no-secondary"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -101,4 +101,4 @@ def test_bench_under_the_drivers_launcher():
     r = json.loads(lines[0])
     assert r["n_gpus"] == 2 and r["steps"] == 2 and r["warmup"] == 1 and r["scaling"] == "weak" and r["config"]["global_batch"] == 8 and r["config"]["parallelism"] == "dp2"
     assert r["value"] > 0 and r["data_parallel"]["world"] == 2 and r["data_parallel"]["backend"] == "gloo"
-    assert r["data_parallel"]["dp_overlap"].get("ms_per_step", 0) > 0, r["data_parallel"]["dp_overlap"]      # the leg the driver's own N > 1 run will execute too
+    assert r["data_parallel"]["dp_overlap"].get("ms_per_step", 0) > 0, r["data_parallel"]["dp_overlap"]      # the leg an N > 1 run with --full executes too

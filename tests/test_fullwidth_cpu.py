@@ -10,6 +10,8 @@ from oracle import dcvgan_oracle as O
 from tests import fullwidth as FW
 from tests import goldenio as G
 
+pytestmark = pytest.mark.usefixtures("golden_cpu_threads")
+
 FIX = ["fullwidth_isogd_depth.npz", "fullwidth_surreal_depth1.npz", "fullwidth_isogd_flow.npz"]
 
 

@@ -7,6 +7,8 @@ import torch
 from oracle import dcvgan_oracle as O
 from tests import goldenio as G
 
+pytestmark = pytest.mark.usefixtures("golden_cpu_threads")
+
 TOL = 2e-6  # same torch, same CPU kernels: expected bit-equal; allow thread-order noise
 
 

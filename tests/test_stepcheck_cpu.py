@@ -11,6 +11,8 @@ from oracle import dcvgan_oracle as O
 from oracle import stepcheck as SC
 from tests import goldenio as G
 
+pytestmark = pytest.mark.usefixtures("golden_cpu_threads")
+
 
 class _Fp32Runner:
     """trainer.StepRunner's duck type over the fp32 StepOracle; `layers`-like tap for its branch patterns."""

@@ -6,9 +6,9 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 export GIT_HEAD=${GIT_HEAD:-$(cat .git_head 2>/dev/null || echo unknown)}
 O=gpurun_out/round; rm -rf $O; mkdir -p $O; rm -rf /tmp/rp /tmp/pd_*
-timeout -k 10 600 python3 bench.py --steps 10 --warmup 3 > $O/bench.json 2> $O/bench.err || { tail -3 $O/bench.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full --steps 10 --warmup 3 > $O/bench.json 2> $O/bench.err || { tail -3 $O/bench.err; exit 1; }
 echo "bench done"; cut -c1-200 $O/bench.json
-timeout -k 10 500 rocprofv3 --kernel-trace --stats -d /tmp/rp -o r --output-format csv -- python3 bench.py --no-cpu-baseline --no-minimal --no-as-trainer --no-secondary --steps 5 --warmup 2 > $O/bench_under_rocprof.log 2>&1 || { tail -3 $O/bench_under_rocprof.log; exit 1; }
+timeout -k 10 500 rocprofv3 --kernel-trace --stats -d /tmp/rp -o r --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-minimal --no-as-trainer --no-secondary --steps 5 --warmup 2 > $O/bench_under_rocprof.log 2>&1 || { tail -3 $O/bench_under_rocprof.log; exit 1; }
 find /tmp/rp -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats_lanes.csv \;
 find /tmp/rp -name "*kernel_trace.csv" -exec cp {} /tmp/rp/trace.csv \;
 # the same command with the discriminators' side streams off: kernels run one at a time, so the per-kernel durations add up to the step
@@ -31,4 +31,4 @@ timeout -k 10 200 python3 tools/stress_d.py 4 > $O/stress_d_b4.txt 2>&1 || { tai
 rm -rf /tmp/rstress; timeout -k 10 300 rocprofv3 --kernel-trace --stats -d /tmp/rstress -o r --output-format csv -- python3 tools/stress_d.py 4 > $O/stress_d_under_rocprof.log 2>&1 || { tail -3 $O/stress_d_under_rocprof.log; exit 1; }
 find /tmp/rstress -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats_stress_d_b4.csv \;
 for c in isogd-depth surreal-depth1 isogd-flow; do timeout -k 10 250 python3 tools/layer_table.py $c --csv $O/layers_$c.csv > $O/layers_$c.txt 2>&1 || exit 1; tail -n 1 $O/layers_$c.txt; done
-for c in surreal-depth1 isogd-flow; do timeout -k 10 300 python3 bench.py --config $c --steps 6 --warmup 2 > $O/bench_$c.json 2> $O/bench_$c.err || { tail -3 $O/bench_$c.err; exit 1; }; cut -c1-200 $O/bench_$c.json; done
+for c in surreal-depth1 isogd-flow; do timeout -k 10 300 python3 bench.py --full --config $c --steps 6 --warmup 2 > $O/bench_$c.json 2> $O/bench_$c.err || { tail -3 $O/bench_$c.err; exit 1; }; cut -c1-200 $O/bench_$c.json; done
