@@ -45,35 +45,15 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 // mode the parity tests and the headline benchmark use), 1 = bf16 products with fp32 accumulation
 // (v_mfma_f32_32x32x16_bf16): tensors, weights, statistics and accumulators stay fp32 in HBM and LDS, the MFMA fragments
 // are rounded to bf16 (RNE, v_cvt_pk_bf16_f32) as they are read from LDS.  Throughput-only mode (BASELINE configs[2], [4]).
+// The process default; dcv_conv_geom.mfma overrides it per call (CallOpts::precision).
 std::atomic<int> g_precision{0};
-// per-call override from dcv_conv_geom.mfma (1 = fp32, 2 = bf16; 0 = the process default above), valid while a dcv_conv_* entry point runs on this thread
-static thread_local int t_precision = -1;
-// dcv_conv_backward_weight_acc: the slab reduce of the calling thread's weight-gradient call ADDS its sum to dw (set around the call, read at the three reduce launches)
-static thread_local int t_wgrad_acc = 0;
-// dcv_conv_backward_data_bn's request to the data-gradient path: when the op is the colour generator's RGB head (widen_mfma_kernel's geometry), run_gather launches
-// head_bn_kernel<mode> instead and sets `used`
-struct HeadBnRequest {
-    int mode, used, nwg;
-    const float* bx; dcv_dims5 bxd; float* bdx; dcv_dims5 bdxd;
-    const float* gamma; const float* beta; const float* mean; const float* invstd;
-    const float* cst; float* partial; size_t partial_bytes;
-    int cbn; float slope;
-};
-static thread_local HeadBnRequest* t_headbn = nullptr;
 // "The first cbn channels of the operand are act(BatchNorm(bx)) and were never written": dcv_conv_forward_bn / dcv_conv_backward_weight_bn ask the RGB head's forward
 // (thin_rows_kernel) and weight gradient (thinj_wgrad_kernel) to read the BatchNorm INPUT for those channels and normalise + activate on the fly.
 struct BnView {
     const float* bx; const float* gamma; const float* beta; const float* mean; const float* invstd;
     int64_t bx_sn;
     int32_t bx_sc, bx_sh, cbn, act;
-    float slope; int32_t used;
-};
-static thread_local BnView* t_bnview = nullptr;
-static inline int eff_precision() { return t_precision >= 0 ? t_precision : g_precision.load(std::memory_order_relaxed); }
-struct PrecisionScope {
-    int saved;
-    explicit PrecisionScope(const dcv_conv_geom* g) : saved(t_precision) { if (g && g->mfma > 0) t_precision = g->mfma - 1; }
-    ~PrecisionScope() { t_precision = saved; }
+    float slope;
 };
 
 // four v_cvt_pk_bf16_f32 (pairs converted as 2-vectors and laid side by side as dwords; element-wise conversion made the compiler
@@ -3201,7 +3181,10 @@ __global__ __launch_bounds__(256) void head_wgrad_kernel(const HeadArgs a) {
 #undef DCV_HEAD_LANES
 
 // --------------------------------------------------------------------------- //
-// host side: plans (index tables cached on the device per distinct geometry)
+// host side.  Every convolution call is planned before anything is launched: the planners (plan_conv / plan_gather,
+// plan_wgrad) choose the kernel and its template instance, the splits and the buffer layout, and return every refusal
+// the call can meet; the launchers (run_conv / run_gather, run_wgrad) only look up or build the cached index tables,
+// pack weights and launch.  The size queries of the C ABI are answered by the same planners.
 // --------------------------------------------------------------------------- //
 struct DevTable {
     KEntry* dev = nullptr;      // AoS (weight packing, wgrad J rows)
@@ -3213,11 +3196,15 @@ struct DevTable {
 static std::mutex g_plan_mu;
 static std::map<std::string, DevTable> g_tables;   // keys start with the device ordinal: tables live on one device
 
-// A/B switches for tools/ (variant off when the variable is set); read once, not per call
+// A/B switches for tools/ (variant off when the variable is set); read once, not per call, and by the planners only
 struct Toggles {
     bool no_lds_dma, no_dstep, no_patch, no_row64, no_widen, no_widen_mfma, no_thinj_wgrad, no_wgrad_dma, no_wgrad_dma64, no_quad, no_thin_wgrad;
     int half_m;
-    bool no_ragged, no_wgrad_d16;
+    bool no_ragged, no_wgrad_d16, no_head_kernels, no_stem3d_wgrad, wgrad_x6;
+    int stem3d_stages;
+#ifdef DCV_DEBUG_TIMING      // timing-experiment builds only (EXTRA_HIPCC_FLAGS=-DDCV_DEBUG_TIMING into an alt library): the shipped library cannot be told to drop its stores
+    bool debug_nostore;
+#endif
     Toggles() {
         auto on = [](const char* n) { return getenv(n) != nullptr; };
         no_lds_dma = on("DCV_NO_LDS_DMA"); no_dstep = on("DCV_NO_DSTEP"); no_patch = on("DCV_NO_PATCH"); no_row64 = on("DCV_NO_ROW64");
@@ -3225,11 +3212,40 @@ struct Toggles {
         half_m = getenv("DCV_HALF_M") ? atoi(getenv("DCV_HALF_M")) : -1;
         no_ragged = on("DCV_NO_RAGGED");
         no_wgrad_d16 = on("DCV_NO_WGRAD_D16");
+        no_head_kernels = on("DCV_NO_HEAD_KERNELS"); no_stem3d_wgrad = on("DCV_NO_STEM3D_WGRAD"); wgrad_x6 = on("DCV_WGRAD_X6");
+        stem3d_stages = getenv("DCV_STEM3D_STAGES") ? atoi(getenv("DCV_STEM3D_STAGES")) : 0;
+#ifdef DCV_DEBUG_TIMING
+        debug_nostore = on("DCV_DEBUG_NOSTORE");
+#endif
     }
 };
 static const Toggles& toggles() {
     static const Toggles t;
     return t;
+}
+
+// dcv_conv_backward_data_bn's request: the RGB head's data gradient (widen_mfma_kernel's geometry) fused with the BatchNorm backward of the operand's first
+// cbn channels, as head_bn_kernel<mode> (1: the data gradient and the BatchNorm's partial sums, 2: the BatchNorm input's gradient)
+struct HeadBnRequest {
+    int mode;
+    const float* bx; dcv_dims5 bxd; float* bdx; dcv_dims5 bdxd;
+    const float* gamma; const float* beta; const float* mean; const float* invstd;
+    const float* cst; float* partial; size_t partial_bytes;
+    int cbn; float slope;
+};
+
+// The options of one call: built by its extern "C" entry point, read by the planners and launchers
+struct CallOpts {
+    int precision = 0;                      // 0 fp32, 1 bf16 products, 2 fp32 on the bf16 pipe: dcv_conv_geom.mfma - 1, or the process default g_precision
+    int wgrad_acc = 0;                      // weight gradient: the slab reduce ADDS its sum to dw
+    const BnView* bnview = nullptr;         // dcv_conv_forward_bn / dcv_conv_backward_weight_bn
+    const HeadBnRequest* headbn = nullptr;  // dcv_conv_backward_data_bn
+};
+static int call_opts(const dcv_conv_geom* g, CallOpts* o, const char* tag) {
+    if (g && (g->mfma < 0 || g->mfma > 3))
+        return fail(DCV_EINVAL, "%s: dcv_conv_geom.mfma must be 0 (process default), 1 (fp32), 2 (bf16 products) or 3 (fp32 on the bf16 pipe)", tag);
+    o->precision = g && g->mfma > 0 ? g->mfma - 1 : g_precision.load(std::memory_order_relaxed);
+    return DCV_OK;
 }
 
 static std::string device_prefix() {
@@ -3240,13 +3256,16 @@ static std::string device_prefix() {
     return std::string(b, n);
 }
 
-static int get_table(const std::string& key, const std::vector<KEntry>& host, DevTable* out) {
+// the device copy of an index table: built by `build` and uploaded on the first use of its key
+template <class Build>
+static int get_table(const std::string& key, Build build, DevTable* out) {
     std::lock_guard<std::mutex> lk(g_plan_mu);
     auto it = g_tables.find(key);
     if (it != g_tables.end()) {
         *out = it->second;
         return DCV_OK;
     }
+    const std::vector<KEntry> host = build();
     DevTable t;
     t.rows = (int)host.size();
     DCV_HIP_CHECK(hipMalloc((void**)&t.dev, host.size() * sizeof(KEntry)));
@@ -3268,6 +3287,23 @@ static int get_table(const std::string& key, const std::vector<KEntry>& host, De
     return DCV_OK;
 }
 
+// smallest and largest of v * stride over the taps of one dim (range of the tap's share of a table offset)
+static void tap_offsets(const DimTaps& t, int64_t stride, int64_t* lo, int64_t* hi) {
+    *lo = *hi = (int64_t)t.delta[0] * stride;
+    for (int u = 1; u < t.n; ++u) {
+        *lo = std::min(*lo, (int64_t)t.delta[u] * stride);
+        *hi = std::max(*hi, (int64_t)t.delta[u] * stride);
+    }
+}
+
+// taps cover a contiguous range of offsets?  (*dmin: the smallest)
+static bool tap_span(const DimTaps& t, int* dmin) {
+    int lo = t.delta[0], hi = t.delta[0];
+    for (int u = 1; u < t.n; ++u) { lo = std::min(lo, t.delta[u]); hi = std::max(hi, t.delta[u]); }
+    *dmin = lo;
+    return hi - lo + 1 == t.n;
+}
+
 // One launch of the gather GEMM (one stride-parity class).
 struct GatherClass {
     // per dim (d,h,w): sub-grid extent, output multiplier/offset, taps
@@ -3276,6 +3312,10 @@ struct GatherClass {
     DimTaps taps[3];
     std::vector<int> tap_k[3];  // filter index along the dim for each tap u
 };
+// a class with taps and positions (a stride-parity class of stride > kernel has none: nothing to launch)
+static bool live(const GatherClass& c) {
+    return c.taps[0].n * c.taps[1].n * c.taps[2].n > 0 && c.o_ext[0] > 0 && c.o_ext[1] > 0 && c.o_ext[2] > 0;
+}
 
 struct TileCfg {
     int bn, bm;
@@ -3338,11 +3378,7 @@ static int flush_packs(const float* w, const PackArgs& packs, int n, int kmax, i
     return DCV_OK;
 }
 
-static int flush_pending(GatherArgsPack& pend, int n, dim3 grid, const TileCfg& tc, int KS, int OC, hipStream_t stream) {
-#ifdef DCV_DEBUG_TIMING      // timing-experiment builds only (EXTRA_HIPCC_FLAGS=-DDCV_DEBUG_TIMING into an alt library): the shipped library cannot be told to drop its stores
-    static const bool nostore = getenv("DCV_DEBUG_NOSTORE") != nullptr;
-    if (nostore) for (int i = 0; i < n; ++i) pend.c[i].p_pad2 = 0x5701;
-#endif
+static int flush_pending(GatherArgsPack& pend, int n, dim3 grid, const TileCfg& tc, int KS, int OC, int bfm, hipStream_t stream) {
     for (int i = n; i < 4; ++i) pend.c[i] = pend.c[0];
     {   // grid.x comes in as the largest class's (oc tiles x position tiles); see the kernel's id -> tile mapping
         const unsigned tiles_oc = (unsigned)(pend.c[0].OCp / tc.bn);
@@ -3352,7 +3388,6 @@ static int flush_pending(GatherArgsPack& pend, int n, dim3 grid, const TileCfg& 
         pend.c[0].pad0 = n;
     }
     const bool ds = pend.c[0].structured == 2, pt = pend.c[0].patch != 0;
-    const int bfm = eff_precision();
 #define DCV_LAUNCH_DMA1(A, B, C_, D, BF_)                                                                                     \
     {                                                                                                                         \
         if (ds && pt) hipLaunchKernelGGL((gather_gemm_dma_kernel<A, B, C_, D, true, true, BF_>), grid, dim3(256), 0, stream, pend); \
@@ -3388,7 +3423,6 @@ static int flush_pending(GatherArgsPack& pend, int n, dim3 grid, const TileCfg& 
 
 // Which structured K walk (index-table-free, LDS-DMA kernel) a class of a gather op takes: 0 none (table-driven register staging),
 // 2 depth-step order, 1 every step covers 16/T whole channels with all T taps, 3 4x4 inner taps with step = (channel, un-padded depth tap).
-// Decided HERE ONLY: the ragged split-K plan, the packed-weight format and the launch setup all read this one answer.
 static int structured_walk(const GatherClass& c, const dcv_dims5& xd, int RC, bool dstep, bool thin) {
     if (thin) return 0;
     if (dstep) return 2;
@@ -3401,96 +3435,115 @@ static int structured_walk(const GatherClass& c, const dcv_dims5& xd, int RC, bo
 }
 
 // bytes per packed weight element: fp32 / bf16 packs fit 4; the three bf16 planes of the fp32-on-bf16 mode need 6
-static inline size_t pack_elem_bytes() { return eff_precision() == 2 ? 6 : sizeof(float); }
+static inline size_t pack_elem_bytes(int precision) { return precision == 2 ? 6 : sizeof(float); }
 
-// The generic driver: reduce over `RC` channels of tensor `x` (dims xd) into `OC`
-// channels of tensor `y` (dims yd); classes describe position/tap relations;
-// weight element (oc, rc, kd, kh, kw) lives at oc*ws_o + rc*ws_r + ((kd*KH)+kh)*KW+kw.
-static int run_gather(const float* x, const dcv_dims5& xd, float* y, const dcv_dims5& yd, const float* w,
-                      int RC, int OC, int64_t ws_o, int64_t ws_r, int KH, int KW,
-                      const std::vector<GatherClass>& classes, int act, float slope, int accumulate,
-                      void* ws, size_t ws_bytes, hipStream_t stream, const char* tag,
-                      float* stat = nullptr, size_t stat_bytes = 0, int* stat_parts = nullptr, const dcv_wpack* pack = nullptr,
-                      const float* gate = nullptr, float gate_slope = 0.f) {
+// One gather-GEMM op: reduce over RC channels of x (dims xd) into OC channels of y (dims yd); classes describe position/tap relations;
+// weight element (oc, rc, kd, kh, kw) lives at w[oc*ws_o + rc*ws_r + ((kd*KH)+kh)*KW+kw].  The planner reads x only for its alignment;
+// the operand pointers are null in a size query.
+struct GatherOp {
+    const float* x = nullptr; float* y = nullptr; const float* w = nullptr;
+    dcv_dims5 xd{}, yd{};
+    int RC = 0, OC = 0, KH = 1, KW = 1;
+    int64_t ws_o = 0, ws_r = 0;
+    std::vector<GatherClass> classes;
+    int act = DCV_ACT_NONE, accumulate = 0;
+    float slope = 0.f;
+    bool stats = false;                      // fused BatchNorm partial sums asked for (forward only) ...
+    float* stat = nullptr; size_t stat_bytes = 0;   // ... into this buffer
+    const dcv_wpack* pack = nullptr;         // caller-owned packed weights: the planner reads only whether it has a buffer (else they go to the workspace)
+    const float* gate = nullptr; float gate_slope = 0.f;
+    const char* tag = "";
+};
+
+// the kernel a class of a gather op runs
+enum class GK { Dma, Rows, RowsBn, HeadBn, WidenMfma, WidenRows, ThinStruct, ThinGather, Gemm };
+struct ClassPlan {
+    GatherArgs a;               // everything but the buffer pointers, which the launcher sets
+    GK kind;
+    dim3 grid;
+    size_t ci;                  // index into GatherOp::classes
+    bool dstep;                 // depth-step K order (the index table's too)
+    bool stat;                  // the epilogue writes BatchNorm partial sums
+    int T, KS2, fmt;            // taps, K splits, packed-weight format
+    int rows_kind, rows_iw0;    // thin_rows_kernel's instance
+    int groups;                 // widen_mfma_kernel / head_bn_kernel: rows per wave
+    size_t wp_off, slab_off;    // packed weights: in the caller's pack when it has a buffer, else in ws; split-K slab: in ws
+};
+struct GatherPlan {
+    TileCfg tc{};
+    int OCp = 0;
+    std::vector<ClassPlan> cls;   // launch order
+    size_t ws_need = 0, pack_need = 0, stat_need = 0;   // workspace; packed weights (wherever they go); BatchNorm partial sums
+    bool stat_memset = false;     // classes of different tile counts leave partial-sum rows no workgroup writes: zeroed first
+    int stat_parts = 0;           // partial-sum rows the run leaves (0: none)
+};
+
+static int plan_gather(const GatherOp& op, const CallOpts& o, GatherPlan* P) {
+    const Toggles& tg = toggles();
+    const dcv_dims5 &xd = op.xd, &yd = op.yd;
+    const int RC = op.RC, OC = op.OC;
+    const char* tag = op.tag;
     TileCfg tc = pick_gather_tile(OC);
+    int nlive = 0, stat_ntm = 0, ntm_min = INT32_MAX;
+    auto workgroups = [&](int bm) {   // of all classes in one launch
+        int64_t W = 0;
+        for (const GatherClass& c : op.classes)
+            if (live(c)) W += ((OC + tc.bn - 1) / tc.bn) * (((int64_t)yd.n * c.o_ext[0] * c.o_ext[1] * c.o_ext[2] + bm - 1) / bm);
+        return W;
+    };
+    for (const GatherClass& c : op.classes) nlive += live(c);
     if (tc.bn >= 64) {
         // Tail regime: the op's workgroups (all classes, one launch) make a little more than a whole number of rounds of
         // the chip's 1024 resident workgroups, or do not fill one round.  Tiles of half as many positions then waste half as
         // much (a partial round of short workgroups) and fill an under-filled chip; measured on the 4x4 / 8x8-spatial
         // layers.  DCV_HALF_M = 0 / 1 forces the choice for A/B runs.
-        int64_t W = 0;
-        int ncls0 = 0;
-        for (const GatherClass& c : classes) {
-            if (c.taps[0].n * c.taps[1].n * c.taps[2].n == 0 || c.o_ext[0] <= 0 || c.o_ext[1] <= 0 || c.o_ext[2] <= 0) continue;
-            const int64_t Mc = (int64_t)yd.n * c.o_ext[0] * c.o_ext[1] * c.o_ext[2];
-            W += ((OC + tc.bn - 1) / tc.bn) * ((Mc + tc.bm - 1) / tc.bm);
-            ++ncls0;
-        }
+        const int64_t W = workgroups(tc.bm);
         const double rounds = (double)W / 1024.0, frac = rounds - (double)(int64_t)rounds;
         bool half = (rounds > 0.4 && rounds < 1.0) || (rounds >= 1.0 && rounds < 3.0 && frac > 0.15 && frac < 0.55);
-        if (toggles().half_m >= 0) half = toggles().half_m != 0;
+        if (tg.half_m >= 0) half = tg.half_m != 0;
         // a little more than a whole number of rounds: whole tiles with a K-split tail (below) rather than half tiles, where the tail qualifies
         // (and every class still has the >= 384 workgroups below which gather_splits splits the whole op)
-        if (half && rounds >= 1.0 && toggles().half_m < 0 && !toggles().no_lds_dma && ncls0 > 0 && W / ncls0 >= 384 &&
-            rag_plan(W, ((OC + tc.bn - 1) / tc.bn) * ncls0).k > 1) half = false;
+        if (half && rounds >= 1.0 && tg.half_m < 0 && !tg.no_lds_dma && nlive > 0 && W / nlive >= 384 &&
+            rag_plan(W, ((OC + tc.bn - 1) / tc.bn) * nlive).k > 1) half = false;
         if (half) tc.bm /= 2;
     }
     // ragged split-K plan of this op (LDS-DMA MFMA path only; decided per op because the classes share one launch)
     RagPlan rag{0, 1};
-    if (tc.bn >= 64 && !toggles().no_lds_dma) {
-        int64_t W = 0;
-        int ncls = 0;
-        for (const GatherClass& c : classes) {
-            if (c.taps[0].n * c.taps[1].n * c.taps[2].n == 0 || c.o_ext[0] <= 0 || c.o_ext[1] <= 0 || c.o_ext[2] <= 0) continue;
-            const int64_t Mc = (int64_t)yd.n * c.o_ext[0] * c.o_ext[1] * c.o_ext[2];
-            W += ((OC + tc.bn - 1) / tc.bn) * ((Mc + tc.bm - 1) / tc.bm);
-            ++ncls;
-        }
-        rag = rag_plan(W, ((OC + tc.bn - 1) / tc.bn) * ncls);
+    if (tc.bn >= 64 && !tg.no_lds_dma) {
+        rag = rag_plan(workgroups(tc.bm), ((OC + tc.bn - 1) / tc.bn) * nlive);
         // the fused BatchNorm partial sums come from the direct epilogue only: a split op makes the BN op read y once more,
         // which is not worth it for the large activations (their tail is a few per cent of many rounds anyway)
-        if (stat != nullptr && (int64_t)OC * yd.n * yd.d * yd.h * yd.w * 4 > (160ll << 20)) rag.k = 1;
+        if (op.stats && (int64_t)OC * yd.n * yd.d * yd.h * yd.w * 4 > (160ll << 20)) rag.k = 1;
     }
-    if (gate && tc.bn == 4) return fail(DCV_EUNSUPPORTED, "%s: the gated epilogue is not built into the thin (OC <= 4) kernels", tag);
-    if (gate)   // a stride-parity class without taps (stride > kernel) has positions no workgroup visits: they would stay un-gated
-        for (const GatherClass& c : classes)
+    if (op.gate && tc.bn == 4) return fail(DCV_EUNSUPPORTED, "%s: the gated epilogue is not built into the thin (OC <= 4) kernels", tag);
+    if (op.gate)   // a stride-parity class without taps (stride > kernel) has positions no workgroup visits: they would stay un-gated
+        for (const GatherClass& c : op.classes)
             if (c.taps[0].n * c.taps[1].n * c.taps[2].n == 0 && c.o_ext[0] > 0 && c.o_ext[1] > 0 && c.o_ext[2] > 0)
                 return fail(DCV_EUNSUPPORTED, "%s: gated epilogue with a tap-less position class", tag);
-    // packed weights: in the caller's buffer when one is given (and already valid when pack->ready), else in `ws`
-    char* const pk_base = pack && pack->buf ? reinterpret_cast<char*>(pack->buf) : nullptr;
-    const bool pk_ready = pk_base && pack->ready;
-    size_t pk_off = 0;
     const int OCp = (OC + tc.bn - 1) / tc.bn * tc.bn;
+    P->tc = tc; P->OCp = OCp; P->cls.clear(); P->pack_need = 0;
     // fused BatchNorm partial sums (forward only): one row of {sum, sum^2} per (class, position tile)
-    int stat_ntm = 0, stat_ncls = 0, stat_ci = 0;
-    bool stat_ok = stat != nullptr && act == DCV_ACT_NONE && !accumulate && tc.bn != 4;
-    if (stat_ok) {
-        int ntm_min = INT32_MAX;
-        for (const GatherClass& c : classes) {
-            if (c.taps[0].n * c.taps[1].n * c.taps[2].n == 0 || c.o_ext[0] <= 0 || c.o_ext[1] <= 0 || c.o_ext[2] <= 0) continue;
-            const int64_t Mc = (int64_t)yd.n * c.o_ext[0] * c.o_ext[1] * c.o_ext[2];
-            const int ntm = (int)((Mc + tc.bm - 1) / tc.bm);
-            stat_ntm = std::max<int>(stat_ntm, ntm);
-            ntm_min = std::min<int>(ntm_min, ntm);
-            ++stat_ncls;
-        }
-        const size_t need = (size_t)stat_ncls * stat_ntm * OCp * 2 * sizeof(float);
-        if (need == 0 || need > stat_bytes) stat_ok = false;
-        // every (class, position tile) row is written by exactly one workgroup when the classes have the same tile
-        // count (the usual case); only ragged classes leave rows that must read as zero
-        else if (ntm_min != stat_ntm) DCV_HIP_CHECK(hipMemsetAsync(stat, 0, need, stream));
+    for (const GatherClass& c : op.classes) {
+        if (!live(c)) continue;
+        const int ntm = (int)(((int64_t)yd.n * c.o_ext[0] * c.o_ext[1] * c.o_ext[2] + tc.bm - 1) / tc.bm);
+        stat_ntm = std::max(stat_ntm, ntm);
+        ntm_min = std::min(ntm_min, ntm);
     }
-    if (stat_parts) *stat_parts = 0;
-    size_t ws_off = 0;
-    GatherArgsPack pend;
-    PackArgs packs;
-    memset(&packs, 0, sizeof(packs));
-    int npack = 0, packmax = 0;
-    int npend = 0, KSpend = 1, OCpend = 0;
-    dim3 pend_grid(0, 1, 1);
-    for (const GatherClass& c : classes) {
+    P->stat_need = (size_t)nlive * stat_ntm * OCp * 2 * sizeof(float);
+    bool stat_ok = op.stats && op.act == DCV_ACT_NONE && !op.accumulate && tc.bn != 4 && P->stat_need > 0 && P->stat_need <= op.stat_bytes;
+    // every (class, position tile) row is written by exactly one workgroup when the classes have the same tile
+    // count (the usual case); only ragged classes leave rows that must read as zero
+    P->stat_memset = stat_ok && ntm_min != stat_ntm;
+    const bool own_pack = op.pack && op.pack->buf;
+    size_t pk_off = 0, ws_off = 0;
+    int stat_ci = 0;
+    for (size_t ci = 0; ci < op.classes.size(); ++ci) {
+        const GatherClass& c = op.classes[ci];
+        if (!live(c)) continue;
+        ClassPlan cp{};
+        memset(&cp.a, 0, sizeof(cp.a));
+        cp.ci = ci;
         const int T = c.taps[0].n * c.taps[1].n * c.taps[2].n;
-        if (T == 0 || c.o_ext[0] <= 0 || c.o_ext[1] <= 0 || c.o_ext[2] <= 0) continue;
         const int64_t K = (int64_t)RC * T;
         const int KIT = (int)((K + 15) / 16);
         const int64_t M64 = (int64_t)yd.n * c.o_ext[0] * c.o_ext[1] * c.o_ext[2];
@@ -3501,144 +3554,64 @@ static int run_gather(const float* x, const dcv_dims5& xd, float* y, const dcv_d
             const DimTaps& t0 = c.taps[0];
             const int nd = t0.n;
             if (tc.bn != 4 && (nd == 2 || nd == 4 || nd == 8) && c.taps[1].n * c.taps[2].n == 4 && RC % 4 == 0 && t0.mul == 1 &&
-                xd.sc * 16 < (1ll << 30) && xd.sd * 4 * nd < (1ll << 30) && !toggles().no_lds_dma && !toggles().no_dstep) {
+                xd.sc * 16 < (1ll << 30) && xd.sd * 4 * nd < (1ll << 30) && !tg.no_lds_dma && !tg.no_dstep) {
                 bool consecutive = true;
                 for (int u = 0; u < nd; ++u) consecutive = consecutive && t0.delta[u] == -u;
                 const bool padded = t0.base - (nd - 1) < 0 || c.o_ext[0] - 1 + t0.base >= t0.size;
                 dstep = consecutive && padded;
             }
         }
-        // ---- K table (cached) ----
-        std::string key = device_prefix() + tag;
-        {
-            char buf[512];
-            int nn = snprintf(buf, sizeof(buf), "|g%d|%d|%d|%lld|%lld|%d|%d|%lld|%lld|%lld|%lld|", (int)dstep, RC, OC, (long long)ws_o, (long long)ws_r, KH, KW,
-                              (long long)xd.sc, (long long)xd.sd, (long long)xd.sh, (long long)xd.sw);
-            key.append(buf, nn);
+        {   // the K table's element offsets (every channel with every tap) fit 32-bit byte offsets
+            int64_t lo = std::min<int64_t>(0, (int64_t)(RC - 1) * xd.sc), hi = std::max<int64_t>(0, (int64_t)(RC - 1) * xd.sc);
+            const int64_t strides[3] = {xd.sd, xd.sh, xd.sw};
             for (int d = 0; d < 3; ++d) {
-                nn = snprintf(buf, sizeof(buf), "%d:", c.taps[d].n);
-                key.append(buf, nn);
-                for (int u = 0; u < c.taps[d].n; ++u) {
-                    nn = snprintf(buf, sizeof(buf), "%d,%d;", c.taps[d].delta[u], c.tap_k[d][u]);
-                    key.append(buf, nn);
-                }
+                int64_t l, h;
+                tap_offsets(c.taps[d], strides[d], &l, &h);
+                lo += l;
+                hi += h;
             }
-        }
-        DevTable tab;
-        {
-            std::lock_guard<std::mutex> lk(g_plan_mu);
-            auto it = g_tables.find(key);
-            if (it != g_tables.end()) tab = it->second;
-        }
-        if (!tab.dev) {
-            std::vector<KEntry> host((size_t)KIT * 16);
-            size_t k = 0;
-            // K order (rc, ud, uh, uw); depth-step order: (rc / 4, ud descending, rc % 4, uh, uw)
-            const int ND = c.taps[0].n, NI = c.taps[1].n * c.taps[2].n;
-            for (int64_t kk = 0; kk < K; ++kk) {
-                int rc, ud, ui;
-                if (dstep) {
-                    ui = (int)(kk % NI);
-                    const int rcl = (int)(kk / NI % 4);
-                    ud = ND - 1 - (int)(kk / (NI * 4) % ND);
-                    rc = (int)(kk / ((int64_t)NI * 4 * ND)) * 4 + rcl;
-                } else {
-                    ui = (int)(kk % NI);
-                    ud = (int)(kk / NI % ND);
-                    rc = (int)(kk / ((int64_t)NI * ND));
-                }
-                const int uh = ui / c.taps[2].n, uw = ui % c.taps[2].n;
-                        {
-                            KEntry e;
-                            const int64_t xo = (int64_t)rc * xd.sc + (int64_t)c.taps[0].delta[ud] * xd.sd +
-                                               (int64_t)c.taps[1].delta[uh] * xd.sh + (int64_t)c.taps[2].delta[uw] * xd.sw;
-                            if (xo > INT32_MAX / 4 || xo < INT32_MIN / 4) return fail(DCV_EUNSUPPORTED, "%s: tensor too large for 32-bit offsets", tag);
-                            e.x_off = (int32_t)xo;
-                            e.tapsel = (1u << ud) | (1u << (8 + uh)) | (1u << (16 + uw));
-                            e.w_off = (int32_t)(rc * ws_r + ((int64_t)c.tap_k[0][ud] * KH + c.tap_k[1][uh]) * KW + c.tap_k[2][uw]);
-                            e.pad = 0;
-                            host[k++] = e;
-                        }
-            }
-            for (; k < host.size(); ++k) host[k] = KEntry{0, 1u << 31, 0, 0};
-            int rc_ = get_table(key, host, &tab);
-            if (rc_ != DCV_OK) return rc_;
+            if (hi > INT32_MAX / 4 || lo < INT32_MIN / 4) return fail(DCV_EUNSUPPORTED, "%s: tensor too large for 32-bit offsets", tag);
         }
         // ---- split-K decision: under-filled grids with a long K loop ----
         const int Mp = (int)((M64 + tc.bm - 1) / tc.bm * tc.bm);
         const int blocks = (OCp / tc.bn) * (Mp / tc.bm);
         // the classes of an op share one launch, so the grid to fill is all of them together (depth-step classes
         // skip a varying share of their steps and measured better with the per-class count)
-        int KS = gather_splits(tc.bn != 4 && !dstep ? blocks * (int)classes.size() : blocks, KIT, tc.bn == 4);
-        if (t_bnview) KS = 1;      // the normalise-on-load operand exists for the row kernel only (small batches would otherwise take the split-K gather)
-        // ragged split-K (rag_plan): this class will take the LDS-DMA kernel (same conditions as the structured-walk choice below),
-        // the op is not split as a whole, and a part keeps at least 8 K steps
-        int rag_m0 = 0;
+        int KS = gather_splits(tc.bn != 4 && !dstep ? blocks * (int)op.classes.size() : blocks, KIT, tc.bn == 4);
+        if (o.bnview) KS = 1;      // the normalise-on-load operand exists for the row kernel only (small batches would otherwise take the split-K gather)
+        // the LDS-DMA kernel: a structured walk (the toggle keeps the structured walk for the register-staged kernel)
         const int walk = structured_walk(c, xd, RC, dstep, tc.bn == 4);
-        const bool will_dma = walk != 0 && !toggles().no_lds_dma;   // (the toggle keeps the structured walk for the register-staged kernel)
-        if (KS == 1 && rag.k > 1 && will_dma && KIT / rag.k >= 8) {
+        const bool dma = walk != 0 && !tg.no_lds_dma;
+        // ragged split-K (rag_plan): this class takes the LDS-DMA kernel, the op is not split as a whole, and a part keeps at least 8 K steps
+        int rag_m0 = 0;
+        if (KS == 1 && rag.k > 1 && dma && KIT / rag.k >= 8) {
             KS = rag.k;
             rag_m0 = (int)std::min<int64_t>((int64_t)rag.t1 * tc.bm, Mp);
         } else if (rag.k > 1 && KS == 1) {
             // this class cannot take the ragged split: the classes after it do not either.  Classes already planned keep theirs — the
-            // pending-launch logic below flushes whenever grid.y differs, so the two groups go out as separate launches.
+            // launcher flushes its pending launch whenever grid.y differs, so the two groups go out as separate launches.
             rag.k = 1;
         }
         const int kper = (KIT + KS - 1) / KS;
         const int KS2 = (KIT + kper - 1) / kper;
         const int slab_mp = Mp - rag_m0;
-        // ---- pack weights ----
-        const size_t wp_bytes = align_up((size_t)KIT * 16 * OCp * pack_elem_bytes(), 256);
+        // ---- buffers: packed weights, split-K slab ----
+        const size_t wp_bytes = align_up((size_t)KIT * 16 * OCp * pack_elem_bytes(o.precision), 256);
         const size_t slab_bytes = KS2 > 1 ? align_up(std::max<size_t>((size_t)KS2 * OCp * slab_mp * sizeof(float), 256), 256) : 0;
-        float* wp;
-        if (pk_base) {
-            if (pk_off + wp_bytes > pack->bytes) return fail(DCV_EWORKSPACE, "%s: packed-weight buffer too small (%zu needed, %zu given)", tag, pk_off + wp_bytes, pack->bytes);
-            wp = reinterpret_cast<float*>(pk_base + pk_off);
-            pk_off += wp_bytes;
-        } else {
-            if (ws_off + wp_bytes > ws_bytes) return fail(DCV_EWORKSPACE, "%s: workspace too small (%zu needed, %zu given)", tag, ws_off + wp_bytes, ws_bytes);
-            wp = reinterpret_cast<float*>(static_cast<char*>(ws) + ws_off);
-            ws_off += wp_bytes;
-        }
-        if (ws_off + slab_bytes > ws_bytes) return fail(DCV_EWORKSPACE, "%s: workspace too small (%zu needed, %zu given)", tag, ws_off + slab_bytes, ws_bytes);
-        float* slab = KS2 > 1 ? reinterpret_cast<float*>(static_cast<char*>(ws) + ws_off) : nullptr;
-        ws_off += slab_bytes;
-        if (!pk_ready) {
-            packs.ktab[npack] = tab.dev;
-            packs.wp[npack] = wp;
-            packs.K16[npack] = KIT * 16;
-            packs.fmt[npack] = will_dma ? eff_precision() : 0;   // 0 fp32 [k][OCp], 1 bf16, 2 three bf16 planes: the LDS-DMA kernel instance of that precision reads it
-            if (KIT * 16 > packmax) packmax = KIT * 16;
-            ++npack;
-        }
-        if (npack == 4) {
-            int rcp = flush_packs(w, packs, npack, packmax, OC, OCp, ws_o, stream);
-            if (rcp != DCV_OK) return rcp;
-            npack = 0;
-            packmax = 0;
-        }
-        // ---- GEMM ----
-        GatherArgs a;
-        memset(&a, 0, sizeof(a));
-        a.x = x;
-        a.y = y;
-        a.wp = wp;
-        a.koff = tab.koff;
-        a.ksel = tab.ksel;
-        a.M = (int)M64;
-        a.OC = OC;
-        a.OCp = OCp;
-        a.KIT = KIT;
-        a.OD = c.o_ext[0];
-        a.OH = c.o_ext[1];
-        a.OW = c.o_ext[2];
+        P->pack_need += wp_bytes;
+        size_t& wp_at = own_pack ? pk_off : ws_off;
+        cp.wp_off = wp_at; wp_at += wp_bytes;
+        cp.slab_off = ws_off; ws_off += slab_bytes;
+        cp.fmt = dma ? o.precision : 0;   // 0 fp32 [k][OCp], 1 bf16, 2 three bf16 planes: the LDS-DMA kernel instance of that precision reads it
+        cp.dstep = dstep; cp.T = T; cp.KS2 = KS2;
+        // ---- GEMM arguments ----
+        GatherArgs& a = cp.a;
+        a.M = (int)M64; a.OC = OC; a.OCp = OCp; a.KIT = KIT;
+        a.OD = c.o_ext[0]; a.OH = c.o_ext[1]; a.OW = c.o_ext[2];
         a.div_sp = make_fastdiv((uint32_t)(c.o_ext[0] * c.o_ext[1] * c.o_ext[2]));
         a.div_hw = make_fastdiv((uint32_t)(c.o_ext[1] * c.o_ext[2]));
         a.div_w = make_fastdiv((uint32_t)c.o_ext[2]);
-        a.td = c.taps[0];
-        a.th = c.taps[1];
-        a.tw = c.taps[2];
-        a.x_sn = xd.sn;
+        a.td = c.taps[0]; a.th = c.taps[1]; a.tw = c.taps[2];
         // per-block 32-bit offset budget: samples touched by one M tile
         {
             const int64_t per = (int64_t)c.o_ext[0] * c.o_ext[1] * c.o_ext[2];
@@ -3650,28 +3623,13 @@ static int run_gather(const float* x, const dcv_dims5& xd, float* y, const dcv_d
             if (yd.sn < 0 || yd.sc < 0 || yd.sd < 0 || yd.sh < 0 || yd.sw < 0 || yspan >= (1ll << 29) || (int64_t)OCp * yd.sc >= (1ll << 30))
                 return fail(DCV_EUNSUPPORTED, "%s: output too large for 32-bit block offsets", tag);
         }
-        a.x_sd = (int32_t)xd.sd;
-        a.x_sh = (int32_t)xd.sh;
-        a.x_sw = (int32_t)xd.sw;
-        a.y_sn = yd.sn;
-        a.y_sc = yd.sc;
-        a.y_sd = yd.sd * c.out_mul[0];
-        a.y_sh = yd.sh * c.out_mul[1];
-        a.y_sw = yd.sw * c.out_mul[2];
+        a.x_sn = xd.sn; a.x_sd = (int32_t)xd.sd; a.x_sh = (int32_t)xd.sh; a.x_sw = (int32_t)xd.sw;
+        a.y_sn = yd.sn; a.y_sc = yd.sc; a.y_sd = yd.sd * c.out_mul[0]; a.y_sh = yd.sh * c.out_mul[1]; a.y_sw = yd.sw * c.out_mul[2];
         a.y_off = yd.sd * c.out_off[0] + yd.sh * c.out_off[1] + yd.sw * c.out_off[2];
-        a.act = act;
-        a.slope = slope;
-        a.accumulate = accumulate;
-        a.slab = slab;
-        a.kper = kper;
-        a.Mp = Mp;
-        a.slab_mp = slab_mp;
-        a.rag_m0 = rag_m0;
-        a.gate = gate;
-        a.gate_slope = gate_slope;
-        a.stat = stat_ok && KS2 == 1 ? stat : nullptr;
-        a.stat_ntm = stat_ntm;
-        a.stat_cls = stat_ci++;
+        a.act = op.act; a.slope = op.slope; a.accumulate = op.accumulate; a.gate_slope = op.gate_slope;
+        a.kper = kper; a.Mp = Mp; a.slab_mp = slab_mp; a.rag_m0 = rag_m0;
+        cp.stat = stat_ok && KS2 == 1;
+        a.stat_ntm = stat_ntm; a.stat_cls = stat_ci++;
         bool thin_struct = false;
         if (tc.bn == 4 && (T == 4 || T == 9 || T == 16) && xd.sc * 4 < (1ll << 30) && (KS2 == 1 || (kper * 16) % T == 0)) {
             // K order is (rc, ud, uh, uw): tap t of every channel has the same relative offset
@@ -3726,7 +3684,7 @@ static int run_gather(const float* x, const dcv_dims5& xd, float* y, const dcv_d
             }
         }
         // ---- patch staging? (w-contiguous operand, whole output rows per tile, aligned 16-byte granules) ----
-        if (a.structured && tc.bn != 4 && !toggles().no_patch) {
+        if (a.structured && tc.bn != 4 && !tg.no_patch) {
             const int nd = c.taps[0].n, nh = c.taps[1].n, nw = c.taps[2].n;
             int CH = 0;   // channels per K step; a step holds ONE depth tap
             if (a.structured == 2) CH = 4;
@@ -3734,36 +3692,22 @@ static int run_gather(const float* x, const dcv_dims5& xd, float* y, const dcv_d
             else if (nd == 1 && 16 % (nh * nw) == 0) CH = 16 / (nh * nw);
             const int OW = c.o_ext[2], IW = c.taps[2].size;
             auto ilog2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return (1 << l) == v ? l : -1; };
-            auto span = [](const DimTaps& t, int* dmin) {   // taps cover a contiguous range of n offsets?
-                int lo = t.delta[0], hi = t.delta[0];
-                for (int u = 1; u < t.n; ++u) { lo = std::min(lo, t.delta[u]); hi = std::max(hi, t.delta[u]); }
-                *dmin = lo;
-                return hi - lo + 1 == t.n;
-            };
             int dminh = 0, dminw = 0;
-            const bool contig = span(c.taps[1], &dminh) && span(c.taps[2], &dminw);
+            const bool contig = tap_span(c.taps[1], &dminh) && tap_span(c.taps[2], &dminw);
             const int dw1 = nw >= 2 ? c.taps[2].delta[1] - c.taps[2].delta[0] : 0;
             const bool pairs = (nw == 2 || nw == 4) && (dw1 == 1 || dw1 == -1) && (nw == 2 || c.taps[2].delta[3] - c.taps[2].delta[2] == dw1);
             const int iwmin = c.taps[2].base + dminw;
             const int IWp = IW + 8, GPR = IW / 4 + 2;
             const int l2nh = ilog2(nh), l2ow = ilog2(OW);
             const bool aligned = xd.sw == 1 && IW % 4 == 0 && xd.sh % 4 == 0 && xd.sc % 4 == 0 && xd.sd % 4 == 0 && xd.sn % 4 == 0 &&
-                                 (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (a.structured != 2 || a.x_back % 4 == 0);
+                                 (reinterpret_cast<uintptr_t>(op.x) & 15) == 0 && (a.structured != 2 || a.x_back % 4 == 0);
             if (CH > 0 && CH * nh * nw == 16 && contig && pairs && l2nh >= 0 && l2ow >= 0 && OW <= tc.bm && aligned && iwmin >= -4 &&
                 (OW - 1) * c.taps[2].mul + iwmin + nw - 1 <= IW + 3 && xd.sc * 4 * CH < (1ll << 30)) {
                 const int TR = tc.bm / OW;
                 const int G = CH * TR * nh * GPR;
                 if (G <= 4 * tc.bm) {
-                    a.patch = 1;
-                    a.p_G = G;
-                    a.p_log2nh = l2nh;
-                    a.p_log2tr = ilog2(TR);
-                    a.p_log2ow = l2ow;
-                    a.p_iwp = IWp;
-                    a.p_ihmin = c.taps[1].base + dminh;
-                    a.p_iwmin4 = iwmin + 4;
-                    a.p_dw1 = dw1;
-                    a.p_sc4 = (int32_t)(xd.sc * 4);
+                    a.patch = 1; a.p_G = G; a.p_log2nh = l2nh; a.p_log2tr = ilog2(TR); a.p_log2ow = l2ow; a.p_iwp = IWp;
+                    a.p_ihmin = c.taps[1].base + dminh; a.p_iwmin4 = iwmin + 4; a.p_dw1 = dw1; a.p_sc4 = (int32_t)(xd.sc * 4);
                     a.p_gpr = make_fastdiv((uint32_t)GPR);
                     for (int r = 0; r < 16; ++r) {
                         const int t = r % (nh * nw), chr = r / (nh * nw), uh = t / nw, uw = t % nw;
@@ -3772,56 +3716,29 @@ static int run_gather(const float* x, const dcv_dims5& xd, float* y, const dcv_d
                 }
             }
         }
-        const dim3 grid((unsigned)blocks, (unsigned)KS2);
-        const bool dma = a.structured && tc.bn != 4 && !toggles().no_lds_dma;
         if (!dma || KS2 > 1) stat_ok = false;   // only the LDS-DMA kernel's direct epilogue produces the sums
-        if (will_dma != dma) return fail(DCV_EINVAL, "%s: internal: structured_walk and the launch setup disagree", tag);
-        if (!dma && npack > 0) {   // an immediate launch needs its packed weights now
-            int rcp = flush_packs(w, packs, npack, packmax, OC, OCp, ws_o, stream);
-            if (rcp != DCV_OK) return rcp;
-            npack = 0;
-            packmax = 0;
-        }
-        if (dma) {   // deferred: merged with the other classes of this op below
-            if (npend > 0 && (pend_grid.y != grid.y || pend.c[0].KIT != a.KIT || pend.c[0].patch != a.patch)) {
-                if (npack > 0) { int rcp = flush_packs(w, packs, npack, packmax, OC, OCp, ws_o, stream); if (rcp != DCV_OK) return rcp; npack = 0; packmax = 0; }
-                int rc2 = flush_pending(pend, npend, pend_grid, tc, KSpend, OCpend, stream);
-                if (rc2 != DCV_OK) return rc2;
-                npend = 0;
-            }
-            pend.c[npend++] = a;
-            if (npend == 1 || grid.x > pend_grid.x) pend_grid.x = grid.x;
-            pend_grid.y = grid.y;
-            KSpend = KS2;
-            OCpend = OC;
-            if (npend == 4) {
-                if (npack > 0) { int rcp = flush_packs(w, packs, npack, packmax, OC, OCp, ws_o, stream); if (rcp != DCV_OK) return rcp; npack = 0; packmax = 0; }
-                int rc2 = flush_pending(pend, npend, pend_grid, tc, KSpend, OCpend, stream);
-                if (rc2 != DCV_OK) return rc2;
-                npend = 0;
-            }
+        if (dma) {   // merged with the other classes of this op into one launch
+            cp.kind = GK::Dma;
+            cp.grid = dim3((unsigned)blocks, (unsigned)KS2);
+#ifdef DCV_DEBUG_TIMING
+            if (tg.debug_nostore) a.p_pad2 = 0x5701;
+#endif
+            P->cls.push_back(cp);
             continue;
         }
         // OC <= 4, unit stride, 32- or 64-wide rows, (3x3 | 2x2 | 2x2x4) taps: the row-reuse kernel
         int rows_kind = 0;   // 1: 3x3 @64   2: 2x2 @32   3: 2x2x4 @32
-        int rows_iw0 = 0;
         if (tc.bn == 4 && KS2 == 1 && xd.sw == 1 && c.taps[0].mul == 1 && c.taps[1].mul == 1 && c.taps[2].mul == 1 &&
-            c.o_ext[2] == c.taps[2].size && !toggles().no_row64 && xd.sc * 4 < (1ll << 30) && xd.sd * 4 * 8 < (1ll << 30)) {
+            c.o_ext[2] == c.taps[2].size && !tg.no_row64 && xd.sc * 4 < (1ll << 30) && xd.sd * 4 * 8 < (1ll << 30)) {
             const int nd = c.taps[0].n, nh = c.taps[1].n, nw = c.taps[2].n, OWc = c.o_ext[2], OHc = c.o_ext[1];
             if (nd == 1 && nh == 3 && nw == 3 && OWc == 64 && OHc % 4 == 0) rows_kind = 1;
             else if (nd == 1 && nh == 2 && nw == 2 && OWc == 32 && OHc % 8 == 0) rows_kind = 2;
             else if (nd == 4 && nh == 2 && nw == 2 && OWc == 32 && OHc % 8 == 0) rows_kind = 3;
             if (rows_kind) {
-                auto span = [](const DimTaps& t, int* dmin) {
-                    int lo = t.delta[0], hi = t.delta[0];
-                    for (int u = 1; u < t.n; ++u) { lo = std::min(lo, t.delta[u]); hi = std::max(hi, t.delta[u]); }
-                    *dmin = lo;
-                    return hi - lo + 1 == t.n;
-                };
                 int dminh = 0, dminw = 0;
-                const bool ok = span(c.taps[1], &dminh) && span(c.taps[2], &dminw);
-                rows_iw0 = c.taps[2].base + dminw;
-                if (!ok || rows_iw0 < -1 || rows_iw0 + nw - 1 > 1 || (rows_kind == 1 && rows_iw0 != -1)) rows_kind = 0;
+                const bool ok = tap_span(c.taps[1], &dminh) && tap_span(c.taps[2], &dminw);
+                cp.rows_iw0 = c.taps[2].base + dminw;
+                if (!ok || cp.rows_iw0 < -1 || cp.rows_iw0 + nw - 1 > 1 || (rows_kind == 1 && cp.rows_iw0 != -1)) rows_kind = 0;
                 else {
                     a.p_ihmin = c.taps[1].base + dminh;
                     a.s_stepA = (int32_t)(xd.sc * 4);
@@ -3837,40 +3754,21 @@ static int run_gather(const float* x, const dcv_dims5& xd, float* y, const dcv_d
             }
         }
         if (rows_kind) {
-            DCV_NOTE_KERNEL("thin_rows_kernel (OC %d, kind %d)", OC, rows_kind);
-            if (npack > 0) {
-                int rcp = flush_packs(w, packs, npack, packmax, OC, OCp, ws_o, stream);
-                if (rcp != DCV_OK) return rcp;
-                npack = 0;
-                packmax = 0;
-            }
-            const dim3 gr((unsigned)(M64 / 256));
-            if (BnView* bv = t_bnview) {
+            cp.kind = GK::Rows; cp.rows_kind = rows_kind; cp.grid = dim3((unsigned)(M64 / 256));
+            if (const BnView* bv = o.bnview) {
                 // (rows_kind 1 only: the RGB head; the operand's row pitch must be the BatchNorm input's)
                 if (rows_kind != 1 || OC != 3 || bv->bx_sh != a.x_sh || bv->cbn > RC) return fail(DCV_EUNSUPPORTED, "%s: BatchNorm-on-load is built for the 3-channel 3x3 head on 64-wide rows", tag);
-                DCV_NOTE_KERNEL("thin_rows_kernel (OC %d, kind %d, BatchNorm + activation of the first %d channels on load)", OC, rows_kind, bv->cbn);
-                hipLaunchKernelGGL((thin_rows_kernel<3, 3, 3, 1, false, -1, true>), gr, dim3(256), 0, stream, a, RC, *bv);
-                bv->used = 1;
-            } else
-            if (rows_kind == 1) launch_thin_rows<3, 3, 1, false, -1>(a, OC, RC, gr, stream);
-            else if (rows_kind == 2 && rows_iw0 == -1) launch_thin_rows<2, 2, 1, true, -1>(a, OC, RC, gr, stream);
-            else if (rows_kind == 2) launch_thin_rows<2, 2, 1, true, 0>(a, OC, RC, gr, stream);
-            else if (rows_iw0 == -1) launch_thin_rows<2, 2, 4, true, -1>(a, OC, RC, gr, stream);
-            else launch_thin_rows<2, 2, 4, true, 0>(a, OC, RC, gr, stream);
-            DCV_LAUNCH_CHECK();
+                cp.kind = GK::RowsBn;
+            }
+            P->cls.push_back(cp);
             continue;
         }
         // <= 4 gathered channels, many output channels, 3x3 / unit stride / 64-wide rows: the register-resident form
-        if (tc.bn != 4 && !gate && RC <= 4 && KS2 == 1 && xd.sw == 1 && c.taps[0].n == 1 && c.taps[1].n == 3 && c.taps[2].n == 3 &&
+        if (tc.bn != 4 && !op.gate && RC <= 4 && KS2 == 1 && xd.sw == 1 && c.taps[0].n == 1 && c.taps[1].n == 3 && c.taps[2].n == 3 &&
             c.taps[1].mul == 1 && c.taps[2].mul == 1 && c.o_ext[2] == 64 && c.taps[2].size == 64 && c.o_ext[1] % 4 == 0 &&
-            c.out_mul[1] == 1 && c.out_mul[2] == 1 && (size_t)RC * 9 * OCp * sizeof(float) <= 48 * 1024 && !toggles().no_widen) {
-            auto span3 = [](const DimTaps& t, int* dmin) {
-                int lo = std::min(t.delta[0], std::min(t.delta[1], t.delta[2])), hi = std::max(t.delta[0], std::max(t.delta[1], t.delta[2]));
-                *dmin = lo;
-                return hi - lo == 2;
-            };
+            c.out_mul[1] == 1 && c.out_mul[2] == 1 && (size_t)RC * 9 * OCp * sizeof(float) <= 48 * 1024 && !tg.no_widen) {
             int dminh = 0, dminw = 0;
-            if (span3(c.taps[1], &dminh) && span3(c.taps[2], &dminw) && c.taps[2].base + dminw == -1) {
+            if (tap_span(c.taps[1], &dminh) && tap_span(c.taps[2], &dminw) && c.taps[2].base + dminw == -1) {
                 a.p_ihmin = c.taps[1].base + dminh;
                 a.s_stepA = (int32_t)(xd.sc * 4);
                 for (int ra = 0; ra < 3; ++ra)
@@ -3882,149 +3780,211 @@ static int run_gather(const float* x, const dcv_dims5& xd, float* y, const dcv_d
                         }
                         a.s_local[ra * 3 + b] = uh * 3 + uw;
                     }
-                if (npack > 0) {
-                    int rcp = flush_packs(w, packs, npack, packmax, OC, OCp, ws_o, stream);
-                    if (rcp != DCV_OK) return rcp;
-                    npack = 0;
-                    packmax = 0;
-                }
+                cp.kind = GK::WidenRows;
+                cp.grid = dim3((unsigned)(M64 / 256));
                 // 3 gathered channels (the RGB head's data gradient): K = 27 on the matrix pipe, bound by its stores (widen_mfma_kernel)
-                if (RC == 3 && (OCp == 128 || OCp == 64) && !toggles().no_widen_mfma && xd.sc * 4 * RC < (1ll << 30)) {
+                if (RC == 3 && (OCp == 128 || OCp == 64) && !tg.no_widen_mfma && xd.sc * 4 * RC < (1ll << 30)) {
                     const int OHc = c.o_ext[1];
-                    const int groups = OHc % 16 == 0 ? 4 : OHc % 8 == 0 ? 2 : 1;   // rows per wave (measured 1 / 2 / 4 / 8 / 16 at B = 70: 0.57 / 0.53 / 0.53 / 0.70 / 0.80 ms)
-                    const dim3 gm((unsigned)(M64 / 256 / groups));
-                    if (HeadBnRequest* hb = t_headbn) {      // fused with the BatchNorm backward of the first hb->cbn channels (dcv_conv_backward_data_bn)
-                        const bool ok = OCp == 128 && OC == 128 && (hb->cbn == 32 || hb->cbn == 64 || hb->cbn == 96) && !accumulate && act == DCV_ACT_NONE && c.o_ext[0] == 1 &&
-                                        hb->bxd.n == yd.n && hb->bxd.c == hb->cbn && hb->bxd.d == 1 && hb->bxd.h == OHc && hb->bxd.w == 64 &&
-                                        hb->bxd.sn >= 0 && hb->bxd.sc >= 0 && hb->bxd.sh >= 0 && hb->bxd.sw >= 0 &&
-                                        (int64_t)hb->cbn * hb->bxd.sc + (int64_t)OHc * hb->bxd.sh + 64 * hb->bxd.sw < (1ll << 29) &&
-                                        (hb->mode == 1 ? (size_t)gm.x * hb->cbn * 2 * sizeof(float) <= hb->partial_bytes
-                                                       : (hb->bdxd.sn >= 0 && hb->bdxd.sc >= 0 && hb->bdxd.sh >= 0 && hb->bdxd.sw >= 0 &&
-                                                          (int64_t)hb->cbn * hb->bdxd.sc + (int64_t)OHc * hb->bdxd.sh + 64 * hb->bdxd.sw < (1ll << 29)));
-                        if (ok) {
-                            HeadBnArgs ha;
-                            memset(&ha, 0, sizeof(ha));
-                            ha.g = a;
-                            ha.bx = hb->bx; ha.bdx = hb->bdx; ha.gamma = hb->gamma; ha.beta = hb->beta; ha.mean = hb->mean; ha.invstd = hb->invstd;
-                            ha.cst = hb->cst; ha.partial = hb->partial;
-                            ha.bx_sn = hb->bxd.sn; ha.bx_sc = (int32_t)hb->bxd.sc; ha.bx_sh = (int32_t)hb->bxd.sh; ha.bx_sw = (int32_t)hb->bxd.sw;
-                            ha.bdx_sn = hb->bdxd.sn; ha.bdx_sc = (int32_t)hb->bdxd.sc; ha.bdx_sh = (int32_t)hb->bdxd.sh; ha.bdx_sw = (int32_t)hb->bdxd.sw;
-                            ha.cbn = hb->cbn; ha.groups = groups; ha.slope = hb->slope;
-                            DCV_NOTE_KERNEL("head_bn_kernel<%d> (RGB head data gradient + BatchNorm backward of %d channels)", hb->mode, hb->cbn);
-                            if (hb->mode == 1) hipLaunchKernelGGL((head_bn_kernel<1>), gm, dim3(256), 0, stream, ha);
-                            else hipLaunchKernelGGL((head_bn_kernel<2>), gm, dim3(256), 0, stream, ha);
-                            DCV_LAUNCH_CHECK();
-                            hb->used = 1;
-                            hb->nwg = (int)gm.x;
-                            continue;
-                        }
+                    cp.groups = OHc % 16 == 0 ? 4 : OHc % 8 == 0 ? 2 : 1;   // rows per wave (measured 1 / 2 / 4 / 8 / 16 at B = 70: 0.57 / 0.53 / 0.53 / 0.70 / 0.80 ms)
+                    cp.grid = dim3((unsigned)(M64 / 256 / cp.groups));
+                    cp.kind = GK::WidenMfma;
+                    // fused with the BatchNorm backward of the first hb->cbn channels (dcv_conv_backward_data_bn): both of its passes must fit
+                    if (const HeadBnRequest* hb = o.headbn) {
+                        if (OCp == 128 && OC == 128 && (hb->cbn == 32 || hb->cbn == 64 || hb->cbn == 96) && !op.accumulate && op.act == DCV_ACT_NONE && c.o_ext[0] == 1 &&
+                            hb->bxd.n == yd.n && hb->bxd.c == hb->cbn && hb->bxd.d == 1 && hb->bxd.h == OHc && hb->bxd.w == 64 &&
+                            hb->bxd.sn >= 0 && hb->bxd.sc >= 0 && hb->bxd.sh >= 0 && hb->bxd.sw >= 0 &&
+                            (int64_t)hb->cbn * hb->bxd.sc + (int64_t)OHc * hb->bxd.sh + 64 * hb->bxd.sw < (1ll << 29) &&
+                            (size_t)cp.grid.x * hb->cbn * 2 * sizeof(float) <= hb->partial_bytes &&
+                            hb->bdxd.sn >= 0 && hb->bdxd.sc >= 0 && hb->bdxd.sh >= 0 && hb->bdxd.sw >= 0 &&
+                            (int64_t)hb->cbn * hb->bdxd.sc + (int64_t)OHc * hb->bdxd.sh + 64 * hb->bdxd.sw < (1ll << 29))
+                            cp.kind = GK::HeadBn;
                     }
-                    DCV_NOTE_KERNEL("widen_mfma_kernel<%d, %d>", RC, OCp / 32);
-                    if (OCp == 128) hipLaunchKernelGGL((widen_mfma_kernel<3, 4>), gm, dim3(256), 0, stream, a, groups);
-                    else hipLaunchKernelGGL((widen_mfma_kernel<3, 2>), gm, dim3(256), 0, stream, a, groups);
-                    DCV_LAUNCH_CHECK();
-                    continue;
                 }
-                const dim3 gw((unsigned)(M64 / 256));
-                const size_t shm = (size_t)RC * 9 * OCp * sizeof(float);
-                DCV_NOTE_KERNEL("widen_rows_kernel<%d>", RC);
-                switch (RC) {
-                    case 1: hipLaunchKernelGGL(widen_rows_kernel<1>, gw, dim3(256), shm, stream, a); break;
-                    case 2: hipLaunchKernelGGL(widen_rows_kernel<2>, gw, dim3(256), shm, stream, a); break;
-                    case 3: hipLaunchKernelGGL(widen_rows_kernel<3>, gw, dim3(256), shm, stream, a); break;
-                    default: hipLaunchKernelGGL(widen_rows_kernel<4>, gw, dim3(256), shm, stream, a); break;
-                }
-                DCV_LAUNCH_CHECK();
+                P->cls.push_back(cp);
                 continue;
             }
         }
-        DCV_NOTE_KERNEL("%s (%d x %d tile%s)", tc.bn == 4 ? (thin_struct ? "thin_struct_kernel" : "thin_gather_kernel") : "gather_gemm_kernel", tc.bn, tc.bm, KS2 > 1 ? ", split-K" : "");
-        if (tc.bn == 4 && thin_struct) {
-            const int rcps = KS2 > 1 ? kper * 16 / T : RC;   // whole channels per K split
-            if (T == 4) launch_thin_struct<4>(a, OC, RC, rcps, grid, stream);
-            else if (T == 9) launch_thin_struct<9>(a, OC, RC, rcps, grid, stream);
-            else launch_thin_struct<16>(a, OC, RC, rcps, grid, stream);
-        } else if (tc.bn == 4) hipLaunchKernelGGL(thin_gather_kernel, grid, dim3(256), 0, stream, a);
-        else if (tc.bn == 128 && tc.bm == 64) launch_gather<2, 1, 2, 2>(a, grid, stream);
-        else if (tc.bn == 64 && tc.bm == 128) launch_gather<2, 1, 1, 4>(a, grid, stream);
-        else if (tc.bn == 128) launch_gather<2, 2, 2, 2>(a, grid, stream);
-        else if (tc.bn == 64) launch_gather<2, 2, 1, 4>(a, grid, stream);
-        else launch_gather<1, 2, 1, 4>(a, grid, stream);
-        DCV_LAUNCH_CHECK();
-        if (KS2 > 1) {
-            const int64_t tot = (int64_t)OC * (Mp / 4);
-            GatherArgsPack one;
-            for (int i = 0; i < 4; ++i) one.c[i] = a;
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((tot + 255) / 256), 1), dim3(256), 0, stream, one, KS2);
-            DCV_LAUNCH_CHECK();
-        }
+        cp.kind = tc.bn != 4 ? GK::Gemm : thin_struct ? GK::ThinStruct : GK::ThinGather;
+        cp.grid = dim3((unsigned)blocks, (unsigned)KS2);
+        P->cls.push_back(cp);
     }
-    if (npack > 0) {
-        int rcp = flush_packs(w, packs, npack, packmax, OC, OCp, ws_o, stream);
-        if (rcp != DCV_OK) return rcp;
-    }
-    if (npend > 0) {
-        int rc2 = flush_pending(pend, npend, pend_grid, tc, KSpend, OCpend, stream);
-        if (rc2 != DCV_OK) return rc2;
-    }
-    if (stat_parts && stat_ok) *stat_parts = stat_ncls * stat_ntm;
+    P->ws_need = ws_off;
+    P->stat_parts = stat_ok ? nlive * stat_ntm : 0;
     return DCV_OK;
 }
 
-static size_t gather_ws_bytes(int RC, int OC, int N, const std::vector<GatherClass>& classes) {
-    const TileCfg tc = pick_gather_tile(OC);
-    const int OCp = (OC + tc.bn - 1) / tc.bn * tc.bn;
-    size_t tot = 0;
-    for (const GatherClass& c : classes) {
-        const int T = c.taps[0].n * c.taps[1].n * c.taps[2].n;
-        if (T == 0 || c.o_ext[0] <= 0 || c.o_ext[1] <= 0 || c.o_ext[2] <= 0) continue;
-        const int64_t K = (int64_t)RC * T;
-        const int KIT = (int)((K + 15) / 16);
-        tot += align_up((size_t)KIT * 16 * OCp * pack_elem_bytes(), 256);
-        const int64_t M64 = (int64_t)N * c.o_ext[0] * c.o_ext[1] * c.o_ext[2];
-        const int64_t Mp = (M64 + tc.bm - 1) / tc.bm * tc.bm;
-        const int blocks = (int)((OCp / tc.bn) * (Mp / tc.bm));
-        const int KS = gather_splits(blocks, KIT, tc.bn == 4);   // per-class count: an upper bound of run_gather's choice
-        if (KS > 1) tot += align_up((size_t)KS * OCp * Mp * sizeof(float), 256);
-    }
-    // ragged split-K slabs (rag_plan), for either position-tile size run_gather may pick: an upper bound of its choice
-    size_t rag_tot = 0;
-    if (tc.bn >= 64)
-        for (int bm : {tc.bm, tc.bm / 2}) {
-            int64_t W = 0;
-            int ncls = 0;
-            for (const GatherClass& c : classes) {
-                if (c.taps[0].n * c.taps[1].n * c.taps[2].n == 0 || c.o_ext[0] <= 0 || c.o_ext[1] <= 0 || c.o_ext[2] <= 0) continue;
-                const int64_t Mc = (int64_t)N * c.o_ext[0] * c.o_ext[1] * c.o_ext[2];
-                W += (OCp / tc.bn) * ((Mc + bm - 1) / bm);
-                ++ncls;
+// the K table of a class (cached per geometry): row k = (x offset, tap bits, weight offset) of K index k
+static int gather_table(const GatherOp& op, const ClassPlan& cp, DevTable* tab) {
+    const GatherClass& c = op.classes[cp.ci];
+    const dcv_dims5& xd = op.xd;
+    std::string key = device_prefix() + op.tag;
+    {
+        char buf[512];
+        int nn = snprintf(buf, sizeof(buf), "|g%d|%d|%d|%lld|%lld|%d|%d|%lld|%lld|%lld|%lld|", (int)cp.dstep, op.RC, op.OC, (long long)op.ws_o, (long long)op.ws_r, op.KH, op.KW,
+                          (long long)xd.sc, (long long)xd.sd, (long long)xd.sh, (long long)xd.sw);
+        key.append(buf, nn);
+        for (int d = 0; d < 3; ++d) {
+            nn = snprintf(buf, sizeof(buf), "%d:", c.taps[d].n);
+            key.append(buf, nn);
+            for (int u = 0; u < c.taps[d].n; ++u) {
+                nn = snprintf(buf, sizeof(buf), "%d,%d;", c.taps[d].delta[u], c.tap_k[d][u]);
+                key.append(buf, nn);
             }
-            const RagPlan rp = rag_plan(W, (OCp / tc.bn) * ncls);
-            if (rp.k <= 1) continue;
-            size_t t = 0;
-            for (const GatherClass& c : classes) {
-                if (c.taps[0].n * c.taps[1].n * c.taps[2].n == 0 || c.o_ext[0] <= 0 || c.o_ext[1] <= 0 || c.o_ext[2] <= 0) continue;
-                const int64_t Mc = (int64_t)N * c.o_ext[0] * c.o_ext[1] * c.o_ext[2];
-                const int64_t Mp = (Mc + bm - 1) / bm * bm;
-                const int64_t m0 = std::min<int64_t>((int64_t)rp.t1 * bm, Mp);
-                t += align_up((size_t)rp.k * OCp * (size_t)(Mp - m0) * sizeof(float) + 256, 256);
-            }
-            rag_tot = std::max(rag_tot, t);
         }
-    return tot + rag_tot + 256;
+    }
+    return get_table(key, [&] {
+        const int64_t K = (int64_t)op.RC * cp.T;
+        std::vector<KEntry> host((size_t)cp.a.KIT * 16);
+        size_t k = 0;
+        // K order (rc, ud, uh, uw); depth-step order: (rc / 4, ud descending, rc % 4, uh, uw)
+        const int ND = c.taps[0].n, NI = c.taps[1].n * c.taps[2].n;
+        for (int64_t kk = 0; kk < K; ++kk) {
+            int rc, ud, ui;
+            if (cp.dstep) {
+                ui = (int)(kk % NI);
+                const int rcl = (int)(kk / NI % 4);
+                ud = ND - 1 - (int)(kk / (NI * 4) % ND);
+                rc = (int)(kk / ((int64_t)NI * 4 * ND)) * 4 + rcl;
+            } else {
+                ui = (int)(kk % NI);
+                ud = (int)(kk / NI % ND);
+                rc = (int)(kk / ((int64_t)NI * ND));
+            }
+            const int uh = ui / c.taps[2].n, uw = ui % c.taps[2].n;
+            host[k++] = KEntry{(int32_t)((int64_t)rc * xd.sc + (int64_t)c.taps[0].delta[ud] * xd.sd + (int64_t)c.taps[1].delta[uh] * xd.sh + (int64_t)c.taps[2].delta[uw] * xd.sw),
+                               (1u << ud) | (1u << (8 + uh)) | (1u << (16 + uw)),
+                               (int32_t)(rc * op.ws_r + ((int64_t)c.tap_k[0][ud] * op.KH + c.tap_k[1][uh]) * op.KW + c.tap_k[2][uw]), 0};
+        }
+        for (; k < host.size(); ++k) host[k] = KEntry{0, 1u << 31, 0, 0};
+        return host;
+    }, tab);
 }
 
-static size_t gather_pack_bytes(int RC, int OC, const std::vector<GatherClass>& classes) {
-    const TileCfg tc = pick_gather_tile(OC);
-    const int OCp = (OC + tc.bn - 1) / tc.bn * tc.bn;
-    size_t tot = 0;
-    for (const GatherClass& c : classes) {
-        const int T = c.taps[0].n * c.taps[1].n * c.taps[2].n;
-        if (T == 0 || c.o_ext[0] <= 0 || c.o_ext[1] <= 0 || c.o_ext[2] <= 0) continue;
-        const int KIT = (int)(((int64_t)RC * T + 15) / 16);
-        tot += align_up((size_t)KIT * 16 * OCp * pack_elem_bytes(), 256);
+// one class that runs as a launch of its own (every kind but GK::Dma)
+static int launch_class(const GatherOp& op, const ClassPlan& cp, const GatherArgs& a, const TileCfg& tc, const CallOpts& o, hipStream_t stream) {
+    const int OC = op.OC, RC = op.RC, OCp = a.OCp;
+    switch (cp.kind) {
+    case GK::RowsBn:
+        DCV_NOTE_KERNEL("thin_rows_kernel (OC %d, kind %d, BatchNorm + activation of the first %d channels on load)", OC, cp.rows_kind, o.bnview->cbn);
+        hipLaunchKernelGGL((thin_rows_kernel<3, 3, 3, 1, false, -1, true>), cp.grid, dim3(256), 0, stream, a, RC, *o.bnview);
+        break;
+    case GK::Rows:
+        DCV_NOTE_KERNEL("thin_rows_kernel (OC %d, kind %d)", OC, cp.rows_kind);
+        if (cp.rows_kind == 1) launch_thin_rows<3, 3, 1, false, -1>(a, OC, RC, cp.grid, stream);
+        else if (cp.rows_kind == 2 && cp.rows_iw0 == -1) launch_thin_rows<2, 2, 1, true, -1>(a, OC, RC, cp.grid, stream);
+        else if (cp.rows_kind == 2) launch_thin_rows<2, 2, 1, true, 0>(a, OC, RC, cp.grid, stream);
+        else if (cp.rows_iw0 == -1) launch_thin_rows<2, 2, 4, true, -1>(a, OC, RC, cp.grid, stream);
+        else launch_thin_rows<2, 2, 4, true, 0>(a, OC, RC, cp.grid, stream);
+        break;
+    case GK::HeadBn: {
+        const HeadBnRequest* hb = o.headbn;
+        HeadBnArgs ha;
+        memset(&ha, 0, sizeof(ha));
+        ha.g = a;
+        ha.bx = hb->bx; ha.bdx = hb->bdx; ha.gamma = hb->gamma; ha.beta = hb->beta; ha.mean = hb->mean; ha.invstd = hb->invstd;
+        ha.cst = hb->cst; ha.partial = hb->partial;
+        ha.bx_sn = hb->bxd.sn; ha.bx_sc = (int32_t)hb->bxd.sc; ha.bx_sh = (int32_t)hb->bxd.sh; ha.bx_sw = (int32_t)hb->bxd.sw;
+        ha.bdx_sn = hb->bdxd.sn; ha.bdx_sc = (int32_t)hb->bdxd.sc; ha.bdx_sh = (int32_t)hb->bdxd.sh; ha.bdx_sw = (int32_t)hb->bdxd.sw;
+        ha.cbn = hb->cbn; ha.groups = cp.groups; ha.slope = hb->slope;
+        DCV_NOTE_KERNEL("head_bn_kernel<%d> (RGB head data gradient + BatchNorm backward of %d channels)", hb->mode, hb->cbn);
+        if (hb->mode == 1) hipLaunchKernelGGL((head_bn_kernel<1>), cp.grid, dim3(256), 0, stream, ha);
+        else hipLaunchKernelGGL((head_bn_kernel<2>), cp.grid, dim3(256), 0, stream, ha);
+        break;
     }
-    return tot;
+    case GK::WidenMfma:
+        DCV_NOTE_KERNEL("widen_mfma_kernel<%d, %d>", RC, OCp / 32);
+        if (OCp == 128) hipLaunchKernelGGL((widen_mfma_kernel<3, 4>), cp.grid, dim3(256), 0, stream, a, cp.groups);
+        else hipLaunchKernelGGL((widen_mfma_kernel<3, 2>), cp.grid, dim3(256), 0, stream, a, cp.groups);
+        break;
+    case GK::WidenRows: {
+        const size_t shm = (size_t)RC * 9 * OCp * sizeof(float);
+        DCV_NOTE_KERNEL("widen_rows_kernel<%d>", RC);
+        switch (RC) {
+            case 1: hipLaunchKernelGGL(widen_rows_kernel<1>, cp.grid, dim3(256), shm, stream, a); break;
+            case 2: hipLaunchKernelGGL(widen_rows_kernel<2>, cp.grid, dim3(256), shm, stream, a); break;
+            case 3: hipLaunchKernelGGL(widen_rows_kernel<3>, cp.grid, dim3(256), shm, stream, a); break;
+            default: hipLaunchKernelGGL(widen_rows_kernel<4>, cp.grid, dim3(256), shm, stream, a); break;
+        }
+        break;
+    }
+    default: {
+        const int KS2 = cp.KS2, T = cp.T;
+        DCV_NOTE_KERNEL("%s (%d x %d tile%s)", cp.kind == GK::ThinStruct ? "thin_struct_kernel" : cp.kind == GK::ThinGather ? "thin_gather_kernel" : "gather_gemm_kernel",
+                        tc.bn, tc.bm, KS2 > 1 ? ", split-K" : "");
+        if (cp.kind == GK::ThinStruct) {
+            const int rcps = KS2 > 1 ? a.kper * 16 / T : RC;   // whole channels per K split
+            if (T == 4) launch_thin_struct<4>(a, OC, RC, rcps, cp.grid, stream);
+            else if (T == 9) launch_thin_struct<9>(a, OC, RC, rcps, cp.grid, stream);
+            else launch_thin_struct<16>(a, OC, RC, rcps, cp.grid, stream);
+        } else if (cp.kind == GK::ThinGather) hipLaunchKernelGGL(thin_gather_kernel, cp.grid, dim3(256), 0, stream, a);
+        else if (tc.bn == 128 && tc.bm == 64) launch_gather<2, 1, 2, 2>(a, cp.grid, stream);
+        else if (tc.bn == 64 && tc.bm == 128) launch_gather<2, 1, 1, 4>(a, cp.grid, stream);
+        else if (tc.bn == 128) launch_gather<2, 2, 2, 2>(a, cp.grid, stream);
+        else if (tc.bn == 64) launch_gather<2, 2, 1, 4>(a, cp.grid, stream);
+        else launch_gather<1, 2, 1, 4>(a, cp.grid, stream);
+        DCV_LAUNCH_CHECK();
+        if (KS2 == 1) return DCV_OK;
+        const int64_t tot = (int64_t)OC * (a.Mp / 4);
+        GatherArgsPack one;
+        for (int i = 0; i < 4; ++i) one.c[i] = a;
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((tot + 255) / 256), 1), dim3(256), 0, stream, one, KS2);
+        break;
+    }
+    }
+    DCV_LAUNCH_CHECK();
+    return DCV_OK;
+}
+
+// Launch a planned gather op with the call's packed-weight buffer (already valid when pack->ready).  Its buffers were checked before this runs.
+static int run_gather(const GatherOp& op, const GatherPlan& P, const CallOpts& o, const dcv_wpack* pack, void* ws, hipStream_t stream) {
+    const TileCfg& tc = P.tc;
+    const bool own_pack = pack && pack->buf;
+    char* const wp_base = static_cast<char*>(own_pack ? pack->buf : ws);
+    const bool pk_ready = own_pack && pack->ready;
+    if (P.stat_memset) DCV_HIP_CHECK(hipMemsetAsync(op.stat, 0, P.stat_need, stream));
+    GatherArgsPack pend;
+    PackArgs packs;
+    memset(&packs, 0, sizeof(packs));
+    int npack = 0, packmax = 0, npend = 0, KSpend = 1;
+    dim3 pend_grid(0, 1, 1);
+    auto flush_pk = [&]() {
+        if (npack == 0) return (int)DCV_OK;
+        const int rc = flush_packs(op.w, packs, npack, packmax, op.OC, P.OCp, op.ws_o, stream);
+        npack = packmax = 0;
+        return rc;
+    };
+    auto flush_pend = [&]() {   // (its packed weights first)
+        int rc = flush_pk();
+        if (rc == DCV_OK && npend > 0) rc = flush_pending(pend, npend, pend_grid, tc, KSpend, op.OC, o.precision, stream);
+        npend = 0;
+        return rc;
+    };
+    for (const ClassPlan& cp : P.cls) {
+        DevTable tab;
+        int rc = gather_table(op, cp, &tab);
+        if (rc != DCV_OK) return rc;
+        GatherArgs a = cp.a;
+        float* const wp = reinterpret_cast<float*>(wp_base + cp.wp_off);
+        a.x = op.x; a.y = op.y; a.wp = wp; a.koff = tab.koff; a.ksel = tab.ksel; a.gate = op.gate;
+        a.slab = cp.KS2 > 1 ? reinterpret_cast<float*>(static_cast<char*>(ws) + cp.slab_off) : nullptr;
+        a.stat = cp.stat ? op.stat : nullptr;
+        if (!pk_ready) {
+            packs.ktab[npack] = tab.dev; packs.wp[npack] = wp; packs.K16[npack] = a.KIT * 16; packs.fmt[npack] = cp.fmt;
+            packmax = std::max(packmax, a.KIT * 16);
+            if (++npack == 4 && (rc = flush_pk()) != DCV_OK) return rc;
+        }
+        if (cp.kind != GK::Dma) {   // an immediate launch needs its packed weights now
+            if ((rc = flush_pk()) != DCV_OK || (rc = launch_class(op, cp, a, tc, o, stream)) != DCV_OK) return rc;
+            continue;
+        }
+        if (npend > 0 && (pend_grid.y != cp.grid.y || pend.c[0].KIT != a.KIT || pend.c[0].patch != a.patch) && (rc = flush_pend()) != DCV_OK) return rc;
+        pend.c[npend++] = a;
+        if (npend == 1 || cp.grid.x > pend_grid.x) pend_grid.x = cp.grid.x;
+        pend_grid.y = cp.grid.y;
+        KSpend = cp.KS2;
+        if (npend == 4 && (rc = flush_pend()) != DCV_OK) return rc;
+    }
+    return flush_pend();
 }
 
 // "direct" relation: gathered position = o*stride - pad + k  (conv fprop, convT dgrad)
@@ -4125,106 +4085,9 @@ static void launch_wgrad(const WgradArgs& a, int gx, int gy, hipStream_t s) {
     else hipLaunchKernelGGL((wgrad_gemm_kernel<TD, TJ, WD, WJ, false>), dim3(gx, gy), dim3(256), 0, s, a);
 }
 
-// dense tensor D (dims dd, channels DC), gathered tensor G (dims gd, channels GC):
-// R[dc][gc][kd][kh][kw] = sum_{n,pos} D[n,dc,pos] * G[n,gc,pos*s - p + k]
-// Thin weight gradient (thin_wgrad3_kernel).  Returns -1 when the geometry is not its own.
-static int try_thin_wgrad(const float* D, const dcv_dims5& dd, const float* G, const dcv_dims5& gd, float* R, const int k[3], const int s[3], const int p[3],
-                          void* ws, size_t ws_bytes, hipStream_t stream, const char* tag, size_t* need_only) {
-    if (toggles().no_thin_wgrad) return -1;
-    const int DC = dd.c, GC = gd.c;
-    if (GC > 2 || dd.sw != 1 || gd.sw != 1 || dd.n != gd.n) return -1;
-    if (!(k[0] == 1 && k[1] == 3 && k[2] == 3 && s[0] == 1 && s[1] == 1 && s[2] == 1 && p[0] == 0 && p[1] == 1 && p[2] == 1 && dd.d == 1 && gd.d == 1 &&
-          dd.w == 64 && gd.w == 64 && dd.h == gd.h && dd.h % 4 == 0))
-        return -1;
-    const int dcw = GC == 1 ? 8 : 4;
-    if (DC % (4 * dcw) != 0) return -1;
-    const int groups = DC / (4 * dcw);
-    const int P = dd.n;
-    const int J = GC * 9;
-    int nslab = std::max(1, std::min(P, 2048 / groups));
-    const int pps = (P + nslab - 1) / nslab;
-    nslab = (P + pps - 1) / pps;
-    const size_t need = align_up((size_t)nslab * DC * J * sizeof(float), 256);
-    if (need_only) {
-        *need_only = need + 256;
-        return DCV_OK;
-    }
-    if (!D || !G || !R || !ws) return fail(DCV_EINVAL, "%s: null pointer", tag);
-    if (need > ws_bytes) return fail(DCV_EWORKSPACE, "%s: workspace too small (%zu needed, %zu given)", tag, need, ws_bytes);
-    ThinWgradArgs a;
-    memset(&a, 0, sizeof(a));
-    a.d = D; a.g = G; a.slab = static_cast<float*>(ws);
-    a.P = P; a.DC = DC; a.OH = dd.h; a.J = J; a.pps = pps;
-    a.d_sn = dd.sn; a.d_sc = dd.sc; a.d_sh = dd.sh;
-    a.g_sn = gd.sn; a.g_sc = gd.sc; a.g_sh = gd.sh;
-    const dim3 grid((unsigned)groups, (unsigned)nslab);
-    if (GC == 1) hipLaunchKernelGGL((thin_wgrad3_kernel<1, 8>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((thin_wgrad3_kernel<2, 4>), grid, dim3(256), 0, stream, a);
-    DCV_NOTE_KERNEL("thin_wgrad3_kernel<%d, %d> (%d slabs)", GC, dcw, nslab);
-    DCV_LAUNCH_CHECK();
-    const int64_t tot = (int64_t)DC * J;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((tot + 63) / 64)), dim3(256), 0, stream, a.slab, R, nslab, DC, J, DC, J, t_wgrad_acc);
-    DCV_LAUNCH_CHECK();
-    return DCV_OK;
-}
-
-// Thin-J weight gradient on the matrix pipe (thinj_wgrad_kernel).  Returns -1 when the geometry is not its own.
-static int try_thinj_wgrad(const float* D, const dcv_dims5& dd, const float* G, const dcv_dims5& gd, float* R, const int k[3], const int s[3], const int p[3],
-                           void* ws, size_t ws_bytes, hipStream_t stream, const char* tag, size_t* need_only) {
-    if (toggles().no_thinj_wgrad || eff_precision() == 1) return -1;
-    const int DC = dd.c, GC = gd.c;
-    if (GC != 3 || DC % 128 != 0 || dd.sw != 1 || gd.sw != 1 || dd.n != gd.n) return -1;
-    if (!(k[0] == 1 && k[1] == 3 && k[2] == 3 && s[0] == 1 && s[1] == 1 && s[2] == 1 && p[0] == 0 && p[1] == 1 && p[2] == 1 && dd.d == 1 && gd.d == 1 &&
-          dd.w == 64 && gd.w == 64 && dd.h == gd.h && dd.h % 2 == 0))
-        return -1;
-    // 16-byte loads of the dense operand; 32-bit byte offsets inside one image
-    if (dd.sc % 4 != 0 || dd.sh % 4 != 0 || dd.sn % 4 != 0 || (D && (reinterpret_cast<uintptr_t>(D) & 15) != 0) || dd.sc < 0 || dd.sh < 0 ||
-        (int64_t)DC * dd.sc * 4 + (int64_t)dd.h * dd.sh * 4 >= (1ll << 31) || gd.sc > INT32_MAX / 8 || gd.sh > INT32_MAX / 8 || gd.sc < 0 || gd.sh < 0)
-        return -1;
-    const int OH = dd.h, rpc = OH % 8 == 0 ? 8 : OH % 4 == 0 ? 4 : 2;
-    const int cpi = OH / rpc;
-    const int64_t nchunk64 = (int64_t)dd.n * cpi;
-    if (nchunk64 >= (1 << 30)) return -1;
-    const int nchunk = (int)nchunk64, dtiles = DC / 128;
-    const int target = std::max(1, 768 / dtiles);                  // three workgroups per CU (the kernel's register budget) in one round
-    const int cpw = (nchunk + target - 1) / target;
-    const int S = (nchunk + cpw - 1) / cpw;
-    const size_t need = align_up((size_t)S * DC * 32 * sizeof(float), 256);
-    if (need_only) {
-        *need_only = need + 256;
-        return DCV_OK;
-    }
-    if (!D || !G || !R || !ws) return fail(DCV_EINVAL, "%s: null pointer", tag);
-    if (need > ws_bytes) return fail(DCV_EWORKSPACE, "%s: workspace too small (%zu needed, %zu given)", tag, need, ws_bytes);
-    ThinJArgs a;
-    memset(&a, 0, sizeof(a));
-    a.d = D; a.g = G; a.slab = static_cast<float*>(ws);
-    a.OH = OH; a.DC = DC; a.GC = GC; a.J = GC * 9; a.rpc = rpc; a.nchunk = nchunk; a.cpw = cpw; a.cpi = cpi;
-    a.d_sn = dd.sn; a.g_sn = gd.sn;
-    a.d_sc = (int32_t)dd.sc; a.d_sh = (int32_t)dd.sh; a.g_sc = (int32_t)gd.sc; a.g_sh = (int32_t)gd.sh;
-    if (BnView* bv = t_bnview) {
-        if (bv->bx_sc % 4 != 0 || bv->bx_sh % 4 != 0 || bv->bx_sn % 4 != 0 || (reinterpret_cast<uintptr_t>(bv->bx) & 15) != 0 || bv->cbn % 32 != 0 || bv->cbn > DC ||
-            (int64_t)bv->cbn * bv->bx_sc * 4 + (int64_t)OH * bv->bx_sh * 4 >= (1ll << 31))
-            return fail(DCV_EUNSUPPORTED, "%s: BatchNorm-on-load needs a 16-byte aligned BatchNorm input and whole 32-channel groups", tag);
-        hipLaunchKernelGGL((thinj_wgrad_kernel<3, true>), dim3((unsigned)S, (unsigned)dtiles), dim3(256), 0, stream, a, *bv);
-        bv->used = 1;
-        DCV_NOTE_KERNEL("thinj_wgrad_kernel<%d> (%d slabs, BatchNorm + activation of the first %d dense channels on load)", GC, S, bv->cbn);
-    } else {
-    hipLaunchKernelGGL((thinj_wgrad_kernel<3>), dim3((unsigned)S, (unsigned)dtiles), dim3(256), 0, stream, a);
-    DCV_NOTE_KERNEL("thinj_wgrad_kernel<%d> (%d slabs)", GC, S);
-    }
-    DCV_LAUNCH_CHECK();
-    const int J = GC * 9;
-    const int64_t tot = (int64_t)DC * J;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((tot + 63) / 64)), dim3(256), 0, stream, a.slab, R, S, DC, J, DC, 32, t_wgrad_acc);
-    DCV_LAUNCH_CHECK();
-    return DCV_OK;
-}
-
 // the discriminators' heads (head_fwd / head_dgrad / head_wgrad kernels): x = the module's input (N, C, D, 8, 8), y = its output (N, 1, OD, 4, 4)
-static bool head_shape_ok(const int k[3], const int s[3], const int p[3], bool transposed, const dcv_dims5& x, const dcv_dims5& y) {
-    static const bool off = getenv("DCV_NO_HEAD_KERNELS") != nullptr;
-    if (off || transposed || eff_precision() == 1) return false;
+static bool head_shape_ok(const int k[3], const int s[3], const int p[3], bool transposed, const dcv_dims5& x, const dcv_dims5& y, int precision) {
+    if (toggles().no_head_kernels || transposed || precision == 1) return false;
     if (!((k[0] == 1 || k[0] == 4) && k[1] == 4 && k[2] == 4 && s[0] == 1 && s[1] == 2 && s[2] == 2 && p[0] == 0 && p[1] == 1 && p[2] == 1)) return false;
     if (y.c != 1 || x.h != 8 || x.w != 8 || x.sh != 8 || x.sw != 1 || y.h != 4 || y.w != 4 || y.sh != 4 || y.sw != 1 || x.d != y.d + k[0] - 1 || y.d < 1 || x.n != y.n) return false;
     if (x.c < 1 || x.sc < 0 || x.sd < 0 || x.sn < 0 || y.sd < 0 || y.sn < 0 || x.sc >= (1ll << 30) || x.sd >= (1ll << 30) || y.sd >= (1ll << 30)) return false;
@@ -4236,18 +4099,15 @@ static int head_splits(const dcv_dims5& x) {      // forward: channel splits so 
     return std::min(cs, 16);
 }
 static size_t head_fwd_bytes(const dcv_dims5& x, int nd) { return align_up((size_t)head_splits(x) * x.n * x.d * nd * 16 * sizeof(float), 256) + 256; }
-static HeadArgs head_args(const dcv_dims5& x, const dcv_dims5& y, int nd) {
+static HeadArgs head_args(const dcv_dims5& x, const dcv_dims5& y) {
     HeadArgs a;
     memset(&a, 0, sizeof(a));
     a.x_sn = x.sn; a.y_sn = y.sn; a.x_sc = (int32_t)x.sc; a.x_sd = (int32_t)x.sd; a.y_sd = (int32_t)y.sd;
     a.N = x.n; a.C = x.c; a.D = x.d; a.OD = y.d;
-    (void)nd;
     return a;
 }
-static int run_head_fwd(const float* x, const dcv_dims5& xd, const float* w, float* y, const dcv_dims5& yd, int nd, int act, float slope, void* ws, size_t ws_bytes, hipStream_t st) {
-    const size_t need = head_fwd_bytes(xd, nd);
-    if (!ws || need > ws_bytes) return fail(DCV_EWORKSPACE, "conv_fwd (head): workspace too small (%zu needed, %zu given)", need, ws_bytes);
-    HeadArgs a = head_args(xd, yd, nd);
+static int run_head_fwd(const float* x, const dcv_dims5& xd, const float* w, float* y, const dcv_dims5& yd, int nd, int act, float slope, void* ws, hipStream_t st) {
+    HeadArgs a = head_args(xd, yd);
     a.x = x; a.w = w; a.out = y; a.part = static_cast<float*>(ws);
     a.CS = head_splits(xd); a.cper = (xd.c + a.CS - 1) / a.CS; a.act = act; a.slope = slope;
     const dim3 grid((unsigned)(((int64_t)xd.n * xd.d + 3) / 4), (unsigned)a.CS);
@@ -4259,7 +4119,7 @@ static int run_head_fwd(const float* x, const dcv_dims5& xd, const float* w, flo
     return DCV_OK;
 }
 static int run_head_dgrad(const float* dy, const dcv_dims5& yd, const float* w, float* dx, const dcv_dims5& xd, int nd, int accumulate, hipStream_t st) {
-    HeadArgs a = head_args(xd, yd, nd);
+    HeadArgs a = head_args(xd, yd);
     a.dy = dy; a.w = w; a.out = dx; a.accumulate = accumulate;
     a.CS = std::max(1, std::min(xd.c / 16, 8)); a.cper = (xd.c + a.CS - 1) / a.CS;
     const dim3 grid((unsigned)(((int64_t)xd.n * xd.d + 3) / 4), (unsigned)a.CS);
@@ -4274,10 +4134,8 @@ static int head_wgrad_shares(const dcv_dims5& x) {      // plane shares so that 
     return std::max(1, std::min(std::min(groups, 32), (512 + cgs - 1) / cgs));
 }
 static size_t head_wgrad_bytes(const dcv_dims5& x, int nd) { return align_up((size_t)head_wgrad_shares(x) * x.c * nd * 16 * sizeof(float), 256) + 256; }
-static int run_head_wgrad(const float* x, const dcv_dims5& xd, const float* dy, const dcv_dims5& yd, float* dw, int nd, int accumulate, void* ws, size_t ws_bytes, hipStream_t st) {
-    const size_t need = head_wgrad_bytes(xd, nd);
-    if (!ws || need > ws_bytes) return fail(DCV_EWORKSPACE, "conv_bwd_weight (head): workspace too small (%zu needed, %zu given)", need, ws_bytes);
-    HeadArgs a = head_args(xd, yd, nd);
+static int run_head_wgrad(const float* x, const dcv_dims5& xd, const float* dy, const dcv_dims5& yd, float* dw, int nd, int accumulate, void* ws, hipStream_t st) {
+    HeadArgs a = head_args(xd, yd);
     a.x = x; a.dy = dy; a.part = static_cast<float*>(ws);
     const int shares = head_wgrad_shares(xd);
     const dim3 grid((unsigned)((xd.c + 7) / 8), (unsigned)shares);
@@ -4292,100 +4150,149 @@ static int run_head_wgrad(const float* x, const dcv_dims5& xd, const float* dy, 
     return DCV_OK;
 }
 
-// the 3-D discriminators' stems (stem3d_wgrad_kernel): -1 = not this shape
-static int try_stem3d_wgrad(const float* D, const dcv_dims5& dd, const float* G, const dcv_dims5& gd, float* R, const int k[3], const int s[3], const int p[3],
-                            void* ws, size_t ws_bytes, hipStream_t stream, const char* tag, size_t* need_only) {
-    static const bool off = getenv("DCV_NO_STEM3D_WGRAD") != nullptr;
-    if (off || eff_precision() == 1) return -1;
+// One weight gradient: dense tensor D (dims dd, channels DC), gathered tensor G (dims gd, channels GC):
+// R[dc][gc][kd][kh][kw] = sum_{n,pos} D[n,dc,pos] * G[n,gc,pos*s - p + k].  The planner reads the pointers only for their alignment;
+// they are null in a size query.
+struct WgradOp {
+    const float* D = nullptr; const float* G = nullptr; float* R = nullptr;
+    dcv_dims5 dd{}, gd{};
+    int k[3], s[3], p[3];
+    const char* tag = "";
+};
+// the kernel family of a weight gradient: the discriminators' heads, the colour generator's stem (thin) and RGB head (thinj, with or without
+// BatchNorm on load), the 3-D discriminators' stems, the tiled GEMM (LDS-DMA or register-staged)
+enum class WK { Head, Thin, ThinJ, Stem3d, Tiled };
+struct WgradPlan {
+    WK kind = WK::Tiled;
+    size_t need = 0;            // workspace bytes: the slabs the reduce sums
+    bool bn = false;            // ThinJ: BatchNorm + activation of the operand's first channels on load (CallOpts::bnview)
+    int nslab = 0;              // slabs
+    dim3 grid;
+    ThinWgradArgs thin;         // Thin: thin_wgrad3_kernel<gc, 8 / gc>
+    ThinJArgs tj;               // ThinJ
+    Stem3Args st;               // Stem3d: stem3d_wgrad_kernel<gc, stages>
+    int gc = 0, stages = 0;
+    WgradArgs g;                // Tiled
+    WgradTile tc{};
+    int dma = -1;               // Tiled: wgrad_dma_kernel<.., dma, d16> (its template precision), or -1 for wgrad_gemm_kernel
+    bool d16 = false;
+};
+
+// Thin weight gradient (thin_wgrad3_kernel): the colour generator's stem
+static bool plan_thin_wgrad(const WgradOp& op, WgradPlan* P) {
+    const dcv_dims5 &dd = op.dd, &gd = op.gd;
+    const int *k = op.k, *s = op.s, *p = op.p;
     const int DC = dd.c, GC = gd.c;
-    if (DC != 32 || GC < 1 || GC > 3 || dd.sw != 1 || gd.sw != 1 || dd.n != gd.n) return -1;
-    if (!(k[0] == 4 && k[1] == 4 && k[2] == 4 && s[0] == 1 && s[1] == 2 && s[2] == 2 && p[0] == 0 && p[1] == 1 && p[2] == 1)) return -1;
-    if (gd.w != 64 || dd.w != 32 || gd.h != 2 * dd.h || dd.h < 1 || gd.d != dd.d + 3 || dd.d < 1) return -1;
+    if (toggles().no_thin_wgrad || GC > 2 || dd.sw != 1 || gd.sw != 1 || dd.n != gd.n) return false;
+    if (!(k[0] == 1 && k[1] == 3 && k[2] == 3 && s[0] == 1 && s[1] == 1 && s[2] == 1 && p[0] == 0 && p[1] == 1 && p[2] == 1 && dd.d == 1 && gd.d == 1 &&
+          dd.w == 64 && gd.w == 64 && dd.h == gd.h && dd.h % 4 == 0))
+        return false;
+    const int dcw = GC == 1 ? 8 : 4;
+    if (DC % (4 * dcw) != 0) return false;
+    const int groups = DC / (4 * dcw);
+    const int N = dd.n;
+    int nslab = std::max(1, std::min(N, 2048 / groups));
+    const int pps = (N + nslab - 1) / nslab;
+    nslab = (N + pps - 1) / pps;
+    ThinWgradArgs& a = P->thin;
+    memset(&a, 0, sizeof(a));
+    a.P = N; a.DC = DC; a.OH = dd.h; a.J = GC * 9; a.pps = pps;
+    a.d_sn = dd.sn; a.d_sc = dd.sc; a.d_sh = dd.sh;
+    a.g_sn = gd.sn; a.g_sc = gd.sc; a.g_sh = gd.sh;
+    P->kind = WK::Thin; P->gc = GC; P->nslab = nslab; P->grid = dim3((unsigned)groups, (unsigned)nslab);
+    P->need = align_up((size_t)nslab * DC * a.J * sizeof(float), 256);
+    return true;
+}
+
+// Thin-J weight gradient on the matrix pipe (thinj_wgrad_kernel): the colour generator's RGB head, one MFMA column of taps, the dense operand streamed once
+static bool plan_thinj_wgrad(const WgradOp& op, const CallOpts& o, WgradPlan* P) {
+    const dcv_dims5 &dd = op.dd, &gd = op.gd;
+    const int *k = op.k, *s = op.s, *p = op.p;
+    const int DC = dd.c, GC = gd.c;
+    if (toggles().no_thinj_wgrad || o.precision == 1) return false;
+    if (GC != 3 || DC % 128 != 0 || dd.sw != 1 || gd.sw != 1 || dd.n != gd.n) return false;
+    if (!(k[0] == 1 && k[1] == 3 && k[2] == 3 && s[0] == 1 && s[1] == 1 && s[2] == 1 && p[0] == 0 && p[1] == 1 && p[2] == 1 && dd.d == 1 && gd.d == 1 &&
+          dd.w == 64 && gd.w == 64 && dd.h == gd.h && dd.h % 2 == 0))
+        return false;
+    // 16-byte loads of the dense operand; 32-bit byte offsets inside one image
+    if (dd.sc % 4 != 0 || dd.sh % 4 != 0 || dd.sn % 4 != 0 || (reinterpret_cast<uintptr_t>(op.D) & 15) != 0 || dd.sc < 0 || dd.sh < 0 ||
+        (int64_t)DC * dd.sc * 4 + (int64_t)dd.h * dd.sh * 4 >= (1ll << 31) || gd.sc > INT32_MAX / 8 || gd.sh > INT32_MAX / 8 || gd.sc < 0 || gd.sh < 0)
+        return false;
+    const int OH = dd.h, rpc = OH % 8 == 0 ? 8 : OH % 4 == 0 ? 4 : 2;
+    const int cpi = OH / rpc;
+    const int64_t nchunk64 = (int64_t)dd.n * cpi;
+    if (nchunk64 >= (1 << 30)) return false;
+    // BatchNorm on load: a 16-byte aligned BatchNorm input and whole 32-channel groups
+    if (const BnView* bv = o.bnview)
+        if (bv->bx_sc % 4 != 0 || bv->bx_sh % 4 != 0 || bv->bx_sn % 4 != 0 || (reinterpret_cast<uintptr_t>(bv->bx) & 15) != 0 || bv->cbn % 32 != 0 || bv->cbn > DC ||
+            (int64_t)bv->cbn * bv->bx_sc * 4 + (int64_t)OH * bv->bx_sh * 4 >= (1ll << 31))
+            return false;
+    const int nchunk = (int)nchunk64, dtiles = DC / 128;
+    const int target = std::max(1, 768 / dtiles);                  // three workgroups per CU (the kernel's register budget) in one round
+    const int cpw = (nchunk + target - 1) / target;
+    const int S = (nchunk + cpw - 1) / cpw;
+    ThinJArgs& a = P->tj;
+    memset(&a, 0, sizeof(a));
+    a.OH = OH; a.DC = DC; a.GC = GC; a.J = GC * 9; a.rpc = rpc; a.nchunk = nchunk; a.cpw = cpw; a.cpi = cpi;
+    a.d_sn = dd.sn; a.g_sn = gd.sn;
+    a.d_sc = (int32_t)dd.sc; a.d_sh = (int32_t)dd.sh; a.g_sc = (int32_t)gd.sc; a.g_sh = (int32_t)gd.sh;
+    P->kind = WK::ThinJ; P->bn = o.bnview != nullptr; P->nslab = S; P->grid = dim3((unsigned)S, (unsigned)dtiles);
+    P->need = align_up((size_t)S * DC * 32 * sizeof(float), 256);
+    return true;
+}
+
+// the 3-D discriminators' stems (stem3d_wgrad_kernel): one wave per run of output rows, everything staged once
+static bool plan_stem3d_wgrad(const WgradOp& op, const CallOpts& o, WgradPlan* P) {
+    const dcv_dims5 &dd = op.dd, &gd = op.gd;
+    const int *k = op.k, *s = op.s, *p = op.p;
+    if (toggles().no_stem3d_wgrad || o.precision == 1) return false;
+    const int DC = dd.c, GC = gd.c;
+    if (DC != 32 || GC < 1 || GC > 3 || dd.sw != 1 || gd.sw != 1 || dd.n != gd.n) return false;
+    if (!(k[0] == 4 && k[1] == 4 && k[2] == 4 && s[0] == 1 && s[1] == 2 && s[2] == 2 && p[0] == 0 && p[1] == 1 && p[2] == 1)) return false;
+    if (gd.w != 64 || dd.w != 32 || gd.h != 2 * dd.h || dd.h < 1 || gd.d != dd.d + 3 || dd.d < 1) return false;
     // 16-byte LDS-DMA granules: rows of both operands on 16-byte addresses
     if (gd.sn % 4 || gd.sc % 4 || gd.sd % 4 || gd.sh % 4 || dd.sn % 4 || dd.sc % 4 || dd.sd % 4 || dd.sh % 4 ||
-        (G && (reinterpret_cast<uintptr_t>(G) & 15) != 0) || (D && (reinterpret_cast<uintptr_t>(D) & 15) != 0))
-        return -1;
+        (reinterpret_cast<uintptr_t>(op.G) & 15) != 0 || (reinterpret_cast<uintptr_t>(op.D) & 15) != 0)
+        return false;
     // 32-bit byte offsets inside one sample (the kernel's buffer resources start at the sample)
-    if (gd.sc < 0 || gd.sd < 0 || gd.sh < 0 || dd.sc < 0 || dd.sd < 0 || dd.sh < 0) return -1;
+    if (gd.sc < 0 || gd.sd < 0 || gd.sh < 0 || dd.sc < 0 || dd.sd < 0 || dd.sh < 0) return false;
     if ((int64_t)(GC - 1) * gd.sc + (int64_t)(gd.d - 1) * gd.sd + (int64_t)(gd.h - 1) * gd.sh + 64 >= (1ll << 28) ||
         (int64_t)31 * dd.sc + (int64_t)(dd.d - 1) * dd.sd + (int64_t)(dd.h - 1) * dd.sh + 32 >= (1ll << 28))
-        return -1;
+        return false;
     const int64_t rows64 = (int64_t)dd.n * dd.d * dd.h;
-    if (rows64 < 1 || rows64 >= (1 << 30)) return -1;
+    if (rows64 < 1 || rows64 >= (1 << 30)) return false;
     const int rows = (int)rows64, J = 64 * GC;
-    static const int ns_env = getenv("DCV_STEM3D_STAGES") ? atoi(getenv("DCV_STEM3D_STAGES")) : 0;      // A/B only
+    const int ns_env = toggles().stem3d_stages;      // A/B only
     const int NS = ns_env >= 2 && ns_env <= 4 ? ns_env : 2;      // measured at B = 70 with the wide slab reduce: 1 channel 0.059 / 0.069 / 0.067 ms with 2 / 3 / 4 stages, 3 channels 0.130 / 0.156 / 0.221
     const int stage_bytes = (GC * 1024 + 1024) * 4;
     const int cap = 256 * std::max(1, std::min(8, (159 * 1024) / (NS * stage_bytes)));      // waves the chip holds at this LDS footprint
     const int rpw = std::max(8, (rows + cap - 1) / cap);
     const int nwg = (rows + rpw - 1) / rpw;
-    const size_t need = align_up((size_t)nwg * 32 * J * sizeof(float), 256);
-    if (need_only) {
-        *need_only = need + 256;
-        return DCV_OK;
-    }
-    if (!D || !G || !R || !ws) return fail(DCV_EINVAL, "%s: null pointer", tag);
-    if (need > ws_bytes) return fail(DCV_EWORKSPACE, "%s: workspace too small (%zu needed, %zu given)", tag, need, ws_bytes);
-    Stem3Args a;
+    Stem3Args& a = P->st;
     memset(&a, 0, sizeof(a));
-    a.d = D; a.g = G; a.slab = static_cast<float*>(ws);
     a.d_sn = dd.sn; a.g_sn = gd.sn;
     a.d_sc = (int32_t)dd.sc; a.d_sd = (int32_t)dd.sd; a.d_sh = (int32_t)dd.sh;
     a.g_sc = (int32_t)gd.sc; a.g_sd = (int32_t)gd.sd; a.g_sh = (int32_t)gd.sh;
     a.OD = dd.d; a.OH = dd.h; a.H = gd.h; a.rows = rows; a.rpw = rpw; a.J = J;
-#define DCV_STEM3(C_, N_) hipLaunchKernelGGL((stem3d_wgrad_kernel<C_, N_>), dim3((unsigned)nwg), dim3(64), 0, stream, a)
-    if (GC == 1) { if (NS == 2) DCV_STEM3(1, 2); else if (NS == 3) DCV_STEM3(1, 3); else DCV_STEM3(1, 4); }
-    else if (GC == 2) { if (NS == 2) DCV_STEM3(2, 2); else if (NS == 3) DCV_STEM3(2, 3); else DCV_STEM3(2, 4); }
-    else { if (NS == 2) DCV_STEM3(3, 2); else if (NS == 3) DCV_STEM3(3, 3); else DCV_STEM3(3, 4); }
-#undef DCV_STEM3
-    DCV_NOTE_KERNEL("stem3d_wgrad_kernel<%d, %d stages> (%d waves x %d output rows)", GC, NS, nwg, rpw);
-    DCV_LAUNCH_CHECK();
-    if ((reinterpret_cast<uintptr_t>(R) & 15) == 0)
-        hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3((unsigned)((8 * J + 3) / 4)), dim3(256), 0, stream, a.slab, R, nwg, 8 * J, t_wgrad_acc);
-    else
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((32 * J + 63) / 64)), dim3(256), 0, stream, a.slab, R, nwg, 32, J, 32, J, t_wgrad_acc);
-    DCV_LAUNCH_CHECK();
-    return DCV_OK;
+    P->kind = WK::Stem3d; P->gc = GC; P->stages = NS; P->nslab = nwg; P->grid = dim3((unsigned)nwg);
+    P->need = align_up((size_t)nwg * 32 * J * sizeof(float), 256);
+    return true;
 }
 
-static int run_wgrad(const float* D, const dcv_dims5& dd, const float* G, const dcv_dims5& gd, float* R,
-                     const int k[3], const int s[3], const int p[3], void* ws, size_t ws_bytes, hipStream_t stream, const char* tag,
-                     size_t* need_only) {
-    const int DC = dd.c, GC = gd.c;
-    const int T = k[0] * k[1] * k[2];
-    const int64_t J64 = (int64_t)GC * T;
-    if (J64 >= (1 << 30)) return fail(DCV_EUNSUPPORTED, "%s: J too large", tag);
-    size_t thin_need = 0;
-    if (head_shape_ok(k, s, p, false, gd, dd) && dd.c == 1) {      // a discriminator's head (conv: dense = dy with one channel, gathered = x)
-        if (need_only) { *need_only = head_wgrad_bytes(gd, k[0]); return DCV_OK; }
-        if (!D || !G || !R) return fail(DCV_EINVAL, "%s: null pointer", tag);
-        return run_head_wgrad(G, gd, D, dd, R, k[0], t_wgrad_acc, ws, ws_bytes, stream);
-    }
-    {   // the colour generator's stem: VALU kernel
-        const int rc_ = try_thin_wgrad(D, dd, G, gd, R, k, s, p, ws, ws_bytes, stream, tag, need_only ? &thin_need : nullptr);
-        if (rc_ != -1 && !need_only) return rc_;
-    }
-    {   // the colour generator's RGB head: one MFMA column of taps, the dense operand streamed once
-        size_t tj_need = 0;
-        const int rc_ = try_thinj_wgrad(D, dd, G, gd, R, k, s, p, ws, ws_bytes, stream, tag, need_only ? &tj_need : nullptr);
-        if (rc_ != -1 && !need_only) return rc_;
-        thin_need = std::max(thin_need, tj_need);
-    }
-    {   // the 3-D discriminators' stems: one wave per run of output rows, everything staged once
-        size_t st_need = 0;
-        const int rc_ = try_stem3d_wgrad(D, dd, G, gd, R, k, s, p, ws, ws_bytes, stream, tag, need_only ? &st_need : nullptr);
-        if (rc_ != -1 && !need_only) return rc_;
-        thin_need = std::max(thin_need, st_need);
-    }
-    const int J = (int)J64;
+// the tiled weight gradient: wgrad_dma_kernel (LDS-DMA, 4x4 inner taps) or wgrad_gemm_kernel (index table, register staging)
+static int plan_tiled_wgrad(const WgradOp& op, const CallOpts& o, WgradPlan* P) {
+    const Toggles& tg = toggles();
+    const dcv_dims5 &dd = op.dd, &gd = op.gd;
+    const int *k = op.k, *s = op.s, *p = op.p;
+    const int DC = dd.c, GC = gd.c, J = GC * k[0] * k[1] * k[2];
     const WgradTile tc = pick_wgrad_tile(DC, J);
     const int DCp = (DC + tc.bd - 1) / tc.bd * tc.bd;
     const int Jp = (J + tc.bj - 1) / tc.bj * tc.bj;
     const int64_t M64 = (int64_t)dd.n * dd.d * dd.h * dd.w;
-    if (M64 >= (1ll << 31)) return fail(DCV_EUNSUPPORTED, "%s: too many positions", tag);
+    if (M64 >= (1ll << 31)) return fail(DCV_EUNSUPPORTED, "%s: too many positions", op.tag);
     const int tiles = (DCp / tc.bd) * (Jp / tc.bj);
     // double-buffered LDS-DMA form: 128 x 128 tile, 4x4 inner taps, un-padded depth taps, full channel tiles
-    bool dma = !toggles().no_wgrad_dma && ((tc.bd == 128 && tc.bj == 128) || (tc.bd == 64 && tc.bj == 128 && !toggles().no_wgrad_dma64)) && k[1] == 4 && k[2] == 4 &&
+    bool dma = !tg.no_wgrad_dma && ((tc.bd == 128 && tc.bj == 128) || (tc.bd == 64 && tc.bj == 128 && !tg.no_wgrad_dma64)) && k[1] == 4 && k[2] == 4 &&
                (k[0] == 1 || k[0] == 2 || k[0] == 4 || k[0] == 8) && (k[0] == 1 || (p[0] == 0 && s[0] == 1)) &&
                DC % tc.bd == 0 && J % 128 == 0 && gd.sc * 4 < (1ll << 30) && dd.sc * 4 < (1ll << 30);
     int S = 1;
@@ -4413,63 +4320,21 @@ static int run_wgrad(const float* D, const dcv_dims5& dd, const float* G, const 
         chunk = ((M64 + S - 1) / S + 63) / 64 * 64;
     }
     const int S2 = (int)((M64 + chunk - 1) / chunk);
-    const size_t need = align_up((size_t)S2 * DCp * Jp * sizeof(float), 256);
-    if (need_only) {
-        *need_only = std::max(need + 256, thin_need);
-        return DCV_OK;
+    {   // the J table's element offsets fit 32-bit byte offsets
+        const int64_t xo = std::max<int64_t>(0, (int64_t)(GC - 1) * gd.sc) + std::max<int64_t>(0, (int64_t)(k[0] - 1) * gd.sd) +
+                           std::max<int64_t>(0, (int64_t)(k[1] - 1) * gd.sh) + std::max<int64_t>(0, (int64_t)(k[2] - 1) * gd.sw);
+        if (xo > INT32_MAX / 4) return fail(DCV_EUNSUPPORTED, "%s: tensor too large for 32-bit offsets", op.tag);
     }
-    if (need > ws_bytes) return fail(DCV_EWORKSPACE, "%s: workspace too small (%zu needed, %zu given)", tag, need, ws_bytes);
-
-    char kb[512];
-    int nn = snprintf(kb, sizeof(kb), "%s|w|%d|%d,%d,%d|%lld|%lld|%lld|%lld", tag, GC, k[0], k[1], k[2], (long long)gd.sc, (long long)gd.sd, (long long)gd.sh, (long long)gd.sw);
-    std::string key = device_prefix() + std::string(kb, nn);
-    DevTable tab;
-    {
-        std::lock_guard<std::mutex> lk(g_plan_mu);
-        auto it = g_tables.find(key);
-        if (it != g_tables.end()) tab = it->second;
-    }
-    if (!tab.dev) {
-        std::vector<KEntry> host((size_t)J);
-        size_t q = 0;
-        for (int gc = 0; gc < GC; ++gc)
-            for (int ud = 0; ud < k[0]; ++ud)
-                for (int uh = 0; uh < k[1]; ++uh)
-                    for (int uw = 0; uw < k[2]; ++uw) {
-                        KEntry e;
-                        const int64_t xo = (int64_t)gc * gd.sc + (int64_t)ud * gd.sd + (int64_t)uh * gd.sh + (int64_t)uw * gd.sw;
-                        if (xo > INT32_MAX / 4) return fail(DCV_EUNSUPPORTED, "%s: tensor too large for 32-bit offsets", tag);
-                        e.x_off = (int32_t)xo;
-                        e.tapsel = (1u << ud) | (1u << (8 + uh)) | (1u << (16 + uw));
-                        e.w_off = 0;
-                        e.pad = 0;
-                        host[q++] = e;
-                    }
-        int rc_ = get_table(key, host, &tab);
-        if (rc_ != DCV_OK) return rc_;
-    }
-    WgradArgs a;
+    WgradArgs& a = P->g;
     memset(&a, 0, sizeof(a));
-    a.dptr = D;
-    a.gptr = G;
-    a.slab = static_cast<float*>(ws);
-    a.jtab = tab.dev;
-    a.M = (int)M64;
-    a.DC = DC;
-    a.J = J;
-    a.DCp = DCp;
-    a.Jp = Jp;
-    a.chunk = (int)chunk;
+    a.M = (int)M64; a.DC = DC; a.J = J; a.DCp = DCp; a.Jp = Jp; a.chunk = (int)chunk;
     a.div_sp = make_fastdiv((uint32_t)(dd.d * dd.h * dd.w));
     a.div_hw = make_fastdiv((uint32_t)(dd.h * dd.w));
     a.div_w = make_fastdiv((uint32_t)dd.w);
     const int gext[3] = {gd.d, gd.h, gd.w};
     DimTaps* ts[3] = {&a.td, &a.th, &a.tw};
     for (int d = 0; d < 3; ++d) {
-        ts[d]->n = k[d];
-        ts[d]->mul = s[d];
-        ts[d]->base = -p[d];
-        ts[d]->size = gext[d];
+        ts[d]->n = k[d]; ts[d]->mul = s[d]; ts[d]->base = -p[d]; ts[d]->size = gext[d];
         for (int u = 0; u < k[d]; ++u) ts[d]->delta[u] = u;
     }
     {
@@ -4477,7 +4342,7 @@ static int run_wgrad(const float* D, const dcv_dims5& dd, const float* G, const 
         const int64_t per = (int64_t)dd.d * dd.h * dd.w;
         const int64_t samples = chunk / per + 2;
         const int64_t dspan = samples * dd.sn + (int64_t)DCp * dd.sc, gspan = samples * gd.sn + (int64_t)GC * gd.sc;
-        if (dspan >= (1ll << 29) || gspan >= (1ll << 29)) return fail(DCV_EUNSUPPORTED, "%s: tensors too large for 32-bit block offsets", tag);
+        if (dspan >= (1ll << 29) || gspan >= (1ll << 29)) return fail(DCV_EUNSUPPORTED, "%s: tensors too large for 32-bit block offsets", op.tag);
     }
     a.d_sn = dd.sn; a.g_sn = gd.sn;
     a.d_sc4 = (int32_t)(dd.sc * 4); a.d_sd = (int32_t)dd.sd; a.d_sh = (int32_t)dd.sh; a.d_sw = (int32_t)dd.sw;
@@ -4495,51 +4360,139 @@ static int run_wgrad(const float* D, const dcv_dims5& dd, const float* G, const 
             a.hw_sel[t] = (1u << (8 + uh)) | (1u << (16 + uw));
         }
     }
+    // fp32 on the bf16 pipe (precision 2): the weight gradient keeps the native fp32 MFMA kernel unless DCV_WGRAD_X6 is set — both of its operands are
+    // activations, so both are split in registers (176 vector operations per 24 MFMAs): measured 112-128 TFLOP/s against the native kernel's 120-135
+    // (profiles/r04_f32x6_layers.csv); the gather kernels, whose weights arrive pre-split, gain 1.4-1.5x
+    P->dma = dma && a.log2nd >= 0 ? (o.precision == 2 && !tg.wgrad_x6 ? 0 : o.precision) : -1;
     // 16-byte staging of the dense operand (wgrad_dma_kernel<.., D16>): its rows are contiguous, 16-byte aligned runs of positions, and tiles, chunks
     // and M are whole granules of 4 positions
     // ... and only the 64-row tile takes it: its 48 row DMAs per 64 MFMAs are what bounds it (cgen.down0 1.351 -> 1.286 ms, gdis.5 0.355 -> 0.353), while
     // the MFMA-bound 128 x 128 tile measured 4-6 % SLOWER with it (the 2-way conflicts of the swizzled fragment reads; profiles/r03_ab_wgrad_d16.txt)
-    const bool d16 = !toggles().no_wgrad_d16 && tc.bd == 64 && dd.sw == 1 && dd.w % 4 == 0 && dd.sh % 4 == 0 && dd.sd % 4 == 0 && dd.sn % 4 == 0 && dd.sc % 4 == 0 &&
-                     (reinterpret_cast<uintptr_t>(D) % 16) == 0 && M64 % 4 == 0 && chunk % 4 == 0 && eff_precision() != 1 && !(eff_precision() == 2 && getenv("DCV_WGRAD_X6"));
-    {
-        const int wbf = eff_precision() == 2 && getenv("DCV_WGRAD_X6") == nullptr ? 0 : eff_precision();
-        if (dma && a.log2nd >= 0) DCV_NOTE_KERNEL("wgrad_dma_kernel<%d, %d, %s> (%d x %d tile, %d slabs%s)", tc.bd == 128 ? 2 : 1, wbf, d16 ? "true" : "false", tc.bd, tc.bj, S2,
-                                                  wbf == 2 ? ", f32x6: fp32 on the bf16 pipe" : wbf ? ", bf16 products" : "");
-        else DCV_NOTE_KERNEL("wgrad_gemm_kernel (%d x %d tile, %d slabs)", tc.bd, tc.bj, S2);
-    }
-    // fp32 on the bf16 pipe (precision 2): the weight gradient keeps the native fp32 MFMA kernel unless DCV_WGRAD_X6 is set — both of its operands are
-    // activations, so both are split in registers (176 vector operations per 24 MFMAs): measured 112-128 TFLOP/s against the native kernel's 120-135
-    // (profiles/r04_f32x6_layers.csv); the gather kernels, whose weights arrive pre-split, gain 1.4-1.5x
-    static const bool wgrad_x6 = getenv("DCV_WGRAD_X6") != nullptr;
-    if (dma && a.log2nd >= 0 && eff_precision() == 2 && wgrad_x6) {
-        if (tc.bd == 128) hipLaunchKernelGGL((wgrad_dma_kernel<2, 2>), dim3(tiles, S2), dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((wgrad_dma_kernel<1, 2>), dim3(tiles, S2), dim3(256), 0, stream, a);
-    } else if (dma && a.log2nd >= 0 && eff_precision() == 1) {
-        if (tc.bd == 128) hipLaunchKernelGGL((wgrad_dma_kernel<2, 1>), dim3(tiles, S2), dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((wgrad_dma_kernel<1, 1>), dim3(tiles, S2), dim3(256), 0, stream, a);
-    } else if (dma && a.log2nd >= 0 && d16) {
-        hipLaunchKernelGGL((wgrad_dma_kernel<1, 0, true>), dim3(tiles, S2), dim3(256), 0, stream, a);
-    } else if (dma && a.log2nd >= 0) {
-        if (tc.bd == 128) hipLaunchKernelGGL((wgrad_dma_kernel<2, 0>), dim3(tiles, S2), dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((wgrad_dma_kernel<1, 0>), dim3(tiles, S2), dim3(256), 0, stream, a);
-    }
-    else if (tc.bd == 128 && tc.bj == 32) launch_wgrad<1, 1, 4, 1>(a, tiles, S2, stream);
-    else if (tc.bd == 128 && tc.bj == 128) launch_wgrad<2, 2, 2, 2>(a, tiles, S2, stream);
-    else if (tc.bd == 128 && tc.bj == 64) launch_wgrad<2, 1, 2, 2>(a, tiles, S2, stream);
-    else if (tc.bd == 64 && tc.bj == 256) launch_wgrad<2, 2, 1, 4>(a, tiles, S2, stream);
-    else if (tc.bd == 64 && tc.bj == 128) launch_wgrad<2, 1, 1, 4>(a, tiles, S2, stream);
-    else if (tc.bd == 32 && tc.bj == 256) launch_wgrad<1, 2, 1, 4>(a, tiles, S2, stream);
-    else launch_wgrad<1, 1, 1, 4>(a, tiles, S2, stream);
-    DCV_LAUNCH_CHECK();
-    const int64_t tot = (int64_t)DC * J;
-    if (J % 4 == 0 && Jp % 4 == 0 && (reinterpret_cast<uintptr_t>(R) & 15) == 0)
-        hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3((unsigned)((tot / 4 + 63) / 64)), dim3(256), 0, stream, a.slab, R, S2, DC, J, DCp, Jp, t_wgrad_acc);
-    else
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((tot + 63) / 64)), dim3(256), 0, stream, a.slab, R, S2, DC, J, DCp, Jp, t_wgrad_acc);
-    DCV_LAUNCH_CHECK();
+    P->d16 = P->dma == 0 && !tg.no_wgrad_d16 && tc.bd == 64 && dd.sw == 1 && dd.w % 4 == 0 && dd.sh % 4 == 0 && dd.sd % 4 == 0 && dd.sn % 4 == 0 && dd.sc % 4 == 0 &&
+             (reinterpret_cast<uintptr_t>(op.D) % 16) == 0 && M64 % 4 == 0 && chunk % 4 == 0 && o.precision != 1 && !(o.precision == 2 && tg.wgrad_x6);
+    P->kind = WK::Tiled; P->tc = tc; P->nslab = S2; P->grid = dim3((unsigned)tiles, (unsigned)S2);
+    P->need = align_up((size_t)S2 * DCp * Jp * sizeof(float), 256);
     return DCV_OK;
 }
 
+static int plan_wgrad(const WgradOp& op, const CallOpts& o, WgradPlan* P) {
+    if ((int64_t)op.gd.c * op.k[0] * op.k[1] * op.k[2] >= (1 << 30)) return fail(DCV_EUNSUPPORTED, "%s: J too large", op.tag);
+    if (head_shape_ok(op.k, op.s, op.p, false, op.gd, op.dd, o.precision) && op.dd.c == 1) {      // a discriminator's head (conv: dense = dy with one channel, gathered = x)
+        P->kind = WK::Head; P->need = head_wgrad_bytes(op.gd, op.k[0]);
+        return DCV_OK;
+    }
+    if (plan_thin_wgrad(op, P) || plan_thinj_wgrad(op, o, P) || plan_stem3d_wgrad(op, o, P)) return DCV_OK;
+    return plan_tiled_wgrad(op, o, P);
+}
+
+// Launch a planned weight gradient.  Its workspace was checked before this runs.
+static int run_wgrad(const WgradOp& op, const WgradPlan& P, const CallOpts& o, void* ws, hipStream_t stream) {
+    const float *D = op.D, *G = op.G;
+    float* const R = op.R;
+    float* const slab = static_cast<float*>(ws);
+    const int DC = op.dd.c, acc = o.wgrad_acc;
+    switch (P.kind) {
+    case WK::Head:
+        return run_head_wgrad(G, op.gd, D, op.dd, R, op.k[0], acc, ws, stream);
+    case WK::Thin: {
+        ThinWgradArgs a = P.thin;
+        a.d = D; a.g = G; a.slab = slab;
+        if (P.gc == 1) hipLaunchKernelGGL((thin_wgrad3_kernel<1, 8>), P.grid, dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL((thin_wgrad3_kernel<2, 4>), P.grid, dim3(256), 0, stream, a);
+        DCV_NOTE_KERNEL("thin_wgrad3_kernel<%d, %d> (%d slabs)", P.gc, P.gc == 1 ? 8 : 4, P.nslab);
+        DCV_LAUNCH_CHECK();
+        const int64_t tot = (int64_t)DC * a.J;
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((tot + 63) / 64)), dim3(256), 0, stream, slab, R, P.nslab, DC, a.J, DC, a.J, acc);
+        break;
+    }
+    case WK::ThinJ: {
+        ThinJArgs a = P.tj;
+        a.d = D; a.g = G; a.slab = slab;
+        if (P.bn) {
+            hipLaunchKernelGGL((thinj_wgrad_kernel<3, true>), P.grid, dim3(256), 0, stream, a, *o.bnview);
+            DCV_NOTE_KERNEL("thinj_wgrad_kernel<%d> (%d slabs, BatchNorm + activation of the first %d dense channels on load)", a.GC, P.nslab, o.bnview->cbn);
+        } else {
+            hipLaunchKernelGGL((thinj_wgrad_kernel<3>), P.grid, dim3(256), 0, stream, a);
+            DCV_NOTE_KERNEL("thinj_wgrad_kernel<%d> (%d slabs)", a.GC, P.nslab);
+        }
+        DCV_LAUNCH_CHECK();
+        const int64_t tot = (int64_t)DC * a.J;
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((tot + 63) / 64)), dim3(256), 0, stream, slab, R, P.nslab, DC, a.J, DC, 32, acc);
+        break;
+    }
+    case WK::Stem3d: {
+        Stem3Args a = P.st;
+        a.d = D; a.g = G; a.slab = slab;
+        const int J = a.J, NS = P.stages;
+#define DCV_STEM3(C_, N_) hipLaunchKernelGGL((stem3d_wgrad_kernel<C_, N_>), P.grid, dim3(64), 0, stream, a)
+        if (P.gc == 1) { if (NS == 2) DCV_STEM3(1, 2); else if (NS == 3) DCV_STEM3(1, 3); else DCV_STEM3(1, 4); }
+        else if (P.gc == 2) { if (NS == 2) DCV_STEM3(2, 2); else if (NS == 3) DCV_STEM3(2, 3); else DCV_STEM3(2, 4); }
+        else { if (NS == 2) DCV_STEM3(3, 2); else if (NS == 3) DCV_STEM3(3, 3); else DCV_STEM3(3, 4); }
+#undef DCV_STEM3
+        DCV_NOTE_KERNEL("stem3d_wgrad_kernel<%d, %d stages> (%d waves x %d output rows)", P.gc, NS, P.nslab, a.rpw);
+        DCV_LAUNCH_CHECK();
+        if ((reinterpret_cast<uintptr_t>(R) & 15) == 0)
+            hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3((unsigned)((8 * J + 3) / 4)), dim3(256), 0, stream, slab, R, P.nslab, 8 * J, acc);
+        else
+            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((32 * J + 63) / 64)), dim3(256), 0, stream, slab, R, P.nslab, 32, J, 32, J, acc);
+        break;
+    }
+    case WK::Tiled: {
+        const int GC = op.gd.c, *k = op.k;
+        const dcv_dims5& gd = op.gd;
+        char kb[512];
+        const int nn = snprintf(kb, sizeof(kb), "%s|w|%d|%d,%d,%d|%lld|%lld|%lld|%lld", op.tag, GC, k[0], k[1], k[2], (long long)gd.sc, (long long)gd.sd, (long long)gd.sh, (long long)gd.sw);
+        DevTable tab;
+        const int rc = get_table(device_prefix() + std::string(kb, nn), [&] {
+            std::vector<KEntry> host;
+            for (int gc = 0; gc < GC; ++gc)
+                for (int ud = 0; ud < k[0]; ++ud)
+                    for (int uh = 0; uh < k[1]; ++uh)
+                        for (int uw = 0; uw < k[2]; ++uw)
+                            host.push_back(KEntry{(int32_t)((int64_t)gc * gd.sc + (int64_t)ud * gd.sd + (int64_t)uh * gd.sh + (int64_t)uw * gd.sw),
+                                                  (1u << ud) | (1u << (8 + uh)) | (1u << (16 + uw)), 0, 0});
+            return host;
+        }, &tab);
+        if (rc != DCV_OK) return rc;
+        WgradArgs a = P.g;
+        a.dptr = D; a.gptr = G; a.slab = slab; a.jtab = tab.dev;
+        const WgradTile tc = P.tc;
+        const int gx = (int)P.grid.x, S2 = P.nslab;
+        if (P.dma >= 0) DCV_NOTE_KERNEL("wgrad_dma_kernel<%d, %d, %s> (%d x %d tile, %d slabs%s)", tc.bd == 128 ? 2 : 1, P.dma, P.d16 ? "true" : "false", tc.bd, tc.bj, S2,
+                                        P.dma == 2 ? ", f32x6: fp32 on the bf16 pipe" : P.dma ? ", bf16 products" : "");
+        else DCV_NOTE_KERNEL("wgrad_gemm_kernel (%d x %d tile, %d slabs)", tc.bd, tc.bj, S2);
+        if (P.dma == 2) {
+            if (tc.bd == 128) hipLaunchKernelGGL((wgrad_dma_kernel<2, 2>), P.grid, dim3(256), 0, stream, a);
+            else hipLaunchKernelGGL((wgrad_dma_kernel<1, 2>), P.grid, dim3(256), 0, stream, a);
+        } else if (P.dma == 1) {
+            if (tc.bd == 128) hipLaunchKernelGGL((wgrad_dma_kernel<2, 1>), P.grid, dim3(256), 0, stream, a);
+            else hipLaunchKernelGGL((wgrad_dma_kernel<1, 1>), P.grid, dim3(256), 0, stream, a);
+        } else if (P.dma == 0 && P.d16) {
+            hipLaunchKernelGGL((wgrad_dma_kernel<1, 0, true>), P.grid, dim3(256), 0, stream, a);
+        } else if (P.dma == 0) {
+            if (tc.bd == 128) hipLaunchKernelGGL((wgrad_dma_kernel<2, 0>), P.grid, dim3(256), 0, stream, a);
+            else hipLaunchKernelGGL((wgrad_dma_kernel<1, 0>), P.grid, dim3(256), 0, stream, a);
+        }
+        else if (tc.bd == 128 && tc.bj == 32) launch_wgrad<1, 1, 4, 1>(a, gx, S2, stream);
+        else if (tc.bd == 128 && tc.bj == 128) launch_wgrad<2, 2, 2, 2>(a, gx, S2, stream);
+        else if (tc.bd == 128 && tc.bj == 64) launch_wgrad<2, 1, 2, 2>(a, gx, S2, stream);
+        else if (tc.bd == 64 && tc.bj == 256) launch_wgrad<2, 2, 1, 4>(a, gx, S2, stream);
+        else if (tc.bd == 64 && tc.bj == 128) launch_wgrad<2, 1, 1, 4>(a, gx, S2, stream);
+        else if (tc.bd == 32 && tc.bj == 256) launch_wgrad<1, 2, 1, 4>(a, gx, S2, stream);
+        else launch_wgrad<1, 1, 1, 4>(a, gx, S2, stream);
+        DCV_LAUNCH_CHECK();
+        const int J = a.J, Jp = a.Jp, DCp = a.DCp;
+        const int64_t tot = (int64_t)DC * J;
+        if (J % 4 == 0 && Jp % 4 == 0 && (reinterpret_cast<uintptr_t>(R) & 15) == 0)
+            hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3((unsigned)((tot / 4 + 63) / 64)), dim3(256), 0, stream, slab, R, S2, DC, J, DCp, Jp, acc);
+        else
+            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((tot + 63) / 64)), dim3(256), 0, stream, slab, R, S2, DC, J, DCp, Jp, acc);
+        break;
+    }
+    }
+    DCV_LAUNCH_CHECK();
+    return DCV_OK;
+}
 }  // namespace dcv
 
 using namespace dcv;
@@ -4602,6 +4555,7 @@ int dcv_conv_effective_precision(const dcv_conv_geom* g) {
 }
 uint64_t dcv_launch_count(void) { return g_launches.load(); }
 
+
 // A transposed convolution of a 1x1(x1) input with stride 1 and no padding (the latent layer, generator.py:61:
 // ConvTranspose2d(dim_z, 8 ngf, 4, 1, 0)) is a plain matrix product y[n, (co, kd, kh, kw)] = sum_ci x[n, ci] w[ci, (co, kd, kh, kw)]:
 // as a k x k scatter it would walk k^3 taps of which all but one are padding for every output position.  When y is
@@ -4624,157 +4578,198 @@ static bool latent_form(const dcv_conv_geom* g, const dcv_dims5* x, const dcv_di
     return true;
 }
 
-// OC <= 4 scatter-form ops of the 4x4 / stride-2 / pad-1 family on 32 -> 64 wide rows: thin_quad_kernel (returns false when the
-// geometry is another one and the generic class-by-class path has to run)
-static bool try_thin_quad(const float* src, const dcv_dims5& sd_, float* dst, const dcv_dims5& dd, const float* w, const int k[3], const int s[3], const int p[3],
-                          int act, float slope, int accumulate, hipStream_t stream) {
+
+
+// OC <= 4 scatter-form ops of the 4x4 / stride-2 / pad-1 family on 32 -> 64 wide rows: thin_quad_kernel (false when the geometry is another one)
+static bool plan_thin_quad(const dcv_dims5& sd_, const dcv_dims5& dd, const int k[3], const int s[3], const int p[3], int act, float slope, int accumulate, QuadArgs* a) {
     if (toggles().no_quad) return false;
     const int OC = dd.c, RC = sd_.c;
     if (OC > 4 || k[1] != 4 || k[2] != 4 || s[1] != 2 || s[2] != 2 || p[1] != 1 || p[2] != 1 || s[0] != 1 || p[0] != 0 || (k[0] != 1 && k[0] != 4)) return false;
     if (sd_.w != 32 || dd.w != 64 || dd.h != 2 * sd_.h || sd_.h % 4 != 0 || sd_.sw != 1 || dd.sw != 1) return false;
     if (dd.d != sd_.d + k[0] - 1) return false;
     if ((int64_t)dd.n * dd.d * (sd_.h / 4) >= (1ll << 31) || sd_.sh * (int64_t)sd_.h >= (1ll << 30)) return false;
-    QuadArgs a;
-    memset(&a, 0, sizeof(a));
-    a.s = src; a.y = dst; a.w = w;
-    a.N = dd.n; a.RC = RC; a.OC = OC; a.SD = sd_.d; a.SH = sd_.h; a.OD = dd.d;
-    a.s_sn = sd_.sn; a.s_sc = sd_.sc; a.s_sd = sd_.sd; a.s_sh = sd_.sh;
-    a.y_sn = dd.sn; a.y_sc = dd.sc; a.y_sd = dd.sd; a.y_sh = dd.sh;
+    memset(a, 0, sizeof(*a));
+    a->N = dd.n; a->RC = RC; a->OC = OC; a->SD = sd_.d; a->SH = sd_.h; a->OD = dd.d;
+    a->s_sn = sd_.sn; a->s_sc = sd_.sc; a->s_sd = sd_.sd; a->s_sh = sd_.sh;
+    a->y_sn = dd.sn; a->y_sc = dd.sc; a->y_sd = dd.sd; a->y_sh = dd.sh;
     const int T = k[0] * 16;
-    a.w_o = T; a.w_r = (int64_t)OC * T;
-    a.act = act; a.slope = slope; a.accumulate = accumulate;
-    const dim3 grid((unsigned)((int64_t)dd.n * dd.d * (sd_.h / 4)));
+    a->w_o = T; a->w_r = (int64_t)OC * T;
+    a->act = act; a->slope = slope; a->accumulate = accumulate;
+    return true;
+}
+static int run_thin_quad(QuadArgs a, const float* src, float* dst, const float* w, int kd, hipStream_t stream) {
+    a.s = src; a.y = dst; a.w = w;
+    const dim3 grid((unsigned)((int64_t)a.N * a.OD * (a.SH / 4)));
 #define DCV_QUAD(NOC_)                                                                                          \
     {                                                                                                           \
-        if (k[0] == 1) hipLaunchKernelGGL((thin_quad_kernel<NOC_, 1>), grid, dim3(256), 0, stream, a);          \
+        if (kd == 1) hipLaunchKernelGGL((thin_quad_kernel<NOC_, 1>), grid, dim3(256), 0, stream, a);            \
         else hipLaunchKernelGGL((thin_quad_kernel<NOC_, 4>), grid, dim3(256), 0, stream, a);                    \
     }
-    switch (OC) {
+    switch (a.OC) {
         case 1: DCV_QUAD(1) break;
         case 2: DCV_QUAD(2) break;
         case 3: DCV_QUAD(3) break;
         default: DCV_QUAD(4) break;
     }
 #undef DCV_QUAD
-    DCV_NOTE_KERNEL("thin_quad_kernel<%d, %d>", OC, k[0]);
-    return true;
+    DCV_NOTE_KERNEL("thin_quad_kernel<%d, %d>", a.OC, kd);
+    DCV_LAUNCH_CHECK();
+    return DCV_OK;
 }
 
-// which: 0 forward, 1 backward-data, 2 backward-weight
-static int conv_dispatch(int which, const dcv_conv_geom* g, const float* a_, const dcv_dims5* xd, const float* w,
-                         float* out, const dcv_dims5* yd, int act, float slope, int accumulate,
-                         void* ws, size_t ws_bytes, void* stream, size_t* need_only,
-                         float* stat = nullptr, size_t stat_bytes = 0, int* stat_parts = nullptr, size_t* stat_need = nullptr,
-                         const dcv_wpack* pack = nullptr, size_t* pack_need = nullptr, const float* gate = nullptr, float gate_slope = 0.f) {
-    // xd = module input dims, yd = module output dims, always.
-    if (g && (g->mfma < 0 || g->mfma > 3)) return fail(DCV_EINVAL, "conv: dcv_conv_geom.mfma must be 0 (process default), 1 (fp32), 2 (bf16 products) or 3 (fp32 on the bf16 pipe)");
-    PrecisionScope prec_scope(g);
-    // a caller-owned packed copy is valid for ONE effective precision (its format depends on it): never read or fill one stamped for another
-    if (pack && pack->buf && !need_only && !pack_need && !stat_need && pack->precision != eff_precision() + 1)
-        return fail(DCV_EINVAL, "conv: dcv_wpack.precision is %d but this call runs at precision %d (1 fp32, 2 bf16 products, 3 fp32-on-bf16): %s",
-                    pack->precision, eff_precision() + 1, pack->ready ? "a ready pack of another format would be read" : "stamp the buffer with dcv_conv_effective_precision(g)");
-    {
-        dcv_conv_geom g2;
-        dcv_dims5 y2;
-        if (!gate && latent_form(g, xd, yd, &g2, &y2)) {
-            if (stat_parts) *stat_parts = 0;       // per-(channel, tap) columns are not BatchNorm channels: the BN op runs its own statistics pass
-            if (stat_need) { *stat_need = 0; return DCV_OK; }
-            return conv_dispatch(which, &g2, a_, xd, w, out, &y2, act, slope, accumulate, ws, ws_bytes, stream, need_only, nullptr, 0, nullptr, nullptr, pack, pack_need);
-        }
-    }
-    int rc = check_geom(g, xd, yd, "conv");
-    if (rc != DCV_OK) return rc;
-    const int k[3] = {g->kd, g->kh, g->kw}, s[3] = {g->sd, g->sh, g->sw}, p[3] = {g->pd, g->ph, g->pw};
-    const int xi[3] = {xd->d, xd->h, xd->w}, yo[3] = {yd->d, yd->h, yd->w};
+// One forward (which 0) or data-gradient (which 1) call as its entry point received it; the operand pointers are null in a size query.
+struct ConvCall {
+    int which = 0;
+    const dcv_conv_geom* g = nullptr;
+    const dcv_dims5 *xd = nullptr, *yd = nullptr;   // module input / output dims, always
+    const float* src = nullptr; const float* w = nullptr; float* dst = nullptr;   // x / dy, weights, y / dx
+    int act = DCV_ACT_NONE, accumulate = 0; float slope = 0.f;
+    bool stats = false; float* stat = nullptr; size_t stat_bytes = 0;   // fused BatchNorm partial sums (dcv_conv_forward_stats)
+    const dcv_wpack* pack = nullptr;
+    const float* gate = nullptr; float gate_slope = 0.f;                // dcv_conv_backward_data_gated
+};
+enum class ConvPath { Gather, HeadFwd, HeadDgrad, Quad };
+struct ConvPlan {
+    ConvPath path = ConvPath::Gather;
+    dcv_conv_geom g{}; dcv_dims5 xd{}, yd{};   // after the latent layer's re-description
+    GatherOp op;        // the op as a gather GEMM, whatever the path
+    GatherPlan gp;      // its plan: path Gather, and every size query
+    QuadArgs quad;      // path Quad (all but the pointers)
+    size_t ws_need = 0;
+};
+
+// `sizes`: plan the gather GEMM whatever the path (the size queries: a stats buffer or a gated epilogue takes it for every geometry)
+static int plan_conv(const ConvCall& c, const CallOpts& o, ConvPlan* P, bool sizes = false) {
+    if (c.which != 0 && c.which != 1) return fail(DCV_EINVAL, "conv: bad dispatch");
+    if (!c.g || !c.xd || !c.yd) return fail(DCV_EINVAL, "conv: null descriptor");
+    const bool latent = !c.gate && latent_form(c.g, c.xd, c.yd, &P->g, &P->yd);
+    if (!latent) { P->g = *c.g; P->yd = *c.yd; }
+    P->xd = *c.xd;
+    const dcv_conv_geom& g = P->g;
+    const dcv_dims5 &xd = P->xd, &yd = P->yd;
+    const int rc0 = check_geom(&g, &xd, &yd, "conv");
+    if (rc0 != DCV_OK) return rc0;
+    const int which = c.which;
+    const int k[3] = {g.kd, g.kh, g.kw}, s[3] = {g.sd, g.sh, g.sw}, p[3] = {g.pd, g.ph, g.pw};
+    const int xi[3] = {xd.d, xd.h, xd.w}, yo[3] = {yd.d, yd.h, yd.w};
     const int T = k[0] * k[1] * k[2];
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    // src / dst: the gathered and the produced tensor
+    const dcv_dims5& src = which == 0 ? xd : yd;
+    const dcv_dims5& dst = which == 0 ? yd : xd;
+    GatherOp& op = P->op;
+    op = GatherOp();
+    op.x = c.src; op.xd = src; op.y = c.dst; op.yd = dst; op.w = c.w;
+    op.RC = src.c; op.OC = dst.c; op.KH = k[1]; op.KW = k[2];
     // forward of conv / backward-data of convT : direct gather from the module INPUT side tensor
-    const bool direct = (which == 0 && !g->transposed) || (which == 1 && g->transposed);
-    if (which == 0 || which == 1) {
-        // src tensor dims / dst tensor dims
-        const dcv_dims5& src = (which == 0) ? *xd : *yd;
-        const dcv_dims5& dst = (which == 0) ? *yd : *xd;
-        const int RC = src.c, OC = dst.c;
-        std::vector<GatherClass> cls;
-        int64_t ws_o, ws_r;
-        if (direct) {
-            // conv fprop: src = x (gathered at o*s-p+k), dst = y.  weight (cout, cin, T): oc = cout
-            // convT dgrad: src = dy (module output), dst = dx; dx[i] = sum dy[i*s-p+k] w[ci,co,k]: weight (cin, cout, T): oc = cin
-            const int* o_ext = (which == 0) ? yo : xi;
-            const int* in_ext = (which == 0) ? xi : yo;
-            cls = direct_classes(k, s, p, o_ext, in_ext);
-            ws_o = (int64_t)RC * T;
-            ws_r = T;
-        } else {
-            // conv dgrad: src = dy, dst = dx, weight (cout, cin, T): oc = cin -> ws_o = T, ws_r = cin*T
-            // convT fprop: src = x, dst = y, weight (cin, cout, T): oc = cout -> ws_o = T, ws_r = cout*T
-            const int* out_ext = (which == 0) ? yo : xi;
-            const int* in_ext = (which == 0) ? xi : yo;
-            cls = scatter_classes(k, s, p, out_ext, in_ext);
-            ws_o = T;
-            ws_r = (int64_t)OC * T;
-        }
-        if (stat_need) {   // upper bound of the fused-BN partial-sum buffer (run_gather may halve the position tile)
-            TileCfg tc = pick_gather_tile(OC);
-            if (tc.bn >= 64) tc.bm /= 2;
-            const int OCp = (OC + tc.bn - 1) / tc.bn * tc.bn;
-            int64_t ntm = 0, ncls = 0;
-            for (const GatherClass& c : cls) {
-                const int64_t Mc = (int64_t)dst.n * std::max(c.o_ext[0], 0) * std::max(c.o_ext[1], 0) * std::max(c.o_ext[2], 0);
-                ntm = std::max<int64_t>(ntm, (Mc + tc.bm - 1) / tc.bm);
-                ++ncls;
-            }
-            *stat_need = (size_t)(ncls * ntm * OCp * 2) * sizeof(float);
-            return DCV_OK;
-        }
-        if (pack_need) {
-            *pack_need = gather_pack_bytes(RC, OC, cls);
-            return DCV_OK;
-        }
-        const bool head = !stat && !gate && head_shape_ok(k, s, p, g->transposed != 0, *xd, *yd);
-        if (need_only) {
-            *need_only = gather_ws_bytes(RC, OC, dst.n, cls);
-            if (head && which == 0) *need_only = std::max(*need_only, head_fwd_bytes(*xd, k[0]));
-            return DCV_OK;
-        }
-        if (!a_ || !w || !out) return fail(DCV_EINVAL, "conv: null pointer");
-        // a discriminator's head, C -> 1 on 8 x 8 planes.  Measured at B = 70 (profiles/r06_ab_heads.txt): the forward kernel wins for the 3-D heads (0.081 -> 0.028 ms,
-        // 0.035 -> 0.019) and ties for the 2-D one; the data-gradient kernel wins for the 2-D head (0.046 -> 0.014) and loses to the tile kernel for the 3-D ones
-        if (head && which == 0 && k[0] == 4) {
-            if (stat_parts) *stat_parts = 0;
-            return run_head_fwd(a_, *xd, w, out, *yd, k[0], act, slope, ws, ws_bytes, st);
-        }
-        if (head && which == 1 && k[0] == 1) {
-            if (stat_parts) *stat_parts = 0;
-            return run_head_dgrad(a_, *yd, w, out, *xd, k[0], accumulate, st);
-        }
-        if (!direct && !stat && !gate && try_thin_quad(a_, src, out, dst, w, k, s, p, act, slope, accumulate, st)) {
-            if (stat_parts) *stat_parts = 0;
-            DCV_LAUNCH_CHECK();
-            return DCV_OK;
-        }
-        return run_gather(a_, src, out, dst, w, RC, OC, ws_o, ws_r, k[1], k[2], cls, act, slope, accumulate, ws, ws_bytes, st,
-                          which == 0 ? (g->transposed ? "convT_fwd" : "conv_fwd") : (g->transposed ? "convT_bwd_data" : "conv_bwd_data"),
-                          stat, stat_bytes, stat_parts, pack, gate, gate_slope);
+    const bool direct = (which == 0 && !g.transposed) || (which == 1 && g.transposed);
+    if (direct) {
+        // conv fprop: src = x (gathered at o*s-p+k), dst = y.  weight (cout, cin, T): oc = cout
+        // convT dgrad: src = dy (module output), dst = dx; dx[i] = sum dy[i*s-p+k] w[ci,co,k]: weight (cin, cout, T): oc = cin
+        op.classes = direct_classes(k, s, p, which == 0 ? yo : xi, which == 0 ? xi : yo);
+        op.ws_o = (int64_t)op.RC * T; op.ws_r = T;
+    } else {
+        // conv dgrad: src = dy, dst = dx, weight (cout, cin, T): oc = cin -> ws_o = T, ws_r = cin*T
+        // convT fprop: src = x, dst = y, weight (cin, cout, T): oc = cout -> ws_o = T, ws_r = cout*T
+        op.classes = scatter_classes(k, s, p, which == 0 ? yo : xi, which == 0 ? xi : yo);
+        op.ws_o = T; op.ws_r = (int64_t)op.OC * T;
     }
-    return fail(DCV_EINVAL, "conv: bad dispatch");
+    op.act = c.act; op.slope = c.slope; op.accumulate = c.accumulate;
+    op.stats = c.stats && !latent;      // per-(channel, tap) columns are not BatchNorm channels: the BN op runs its own statistics pass
+    op.stat = c.stat; op.stat_bytes = c.stat_bytes; op.pack = c.pack; op.gate = c.gate; op.gate_slope = c.gate_slope;
+    op.tag = which == 0 ? (g.transposed ? "convT_fwd" : "conv_fwd") : (g.transposed ? "convT_bwd_data" : "conv_bwd_data");
+    // a discriminator's head, C -> 1 on 8 x 8 planes.  Measured at B = 70 (profiles/r06_ab_heads.txt): the forward kernel wins for the 3-D heads (0.081 -> 0.028 ms,
+    // 0.035 -> 0.019) and ties for the 2-D one; the data-gradient kernel wins for the 2-D head (0.046 -> 0.014) and loses to the tile kernel for the 3-D ones
+    const bool head = !op.stats && !c.gate && head_shape_ok(k, s, p, g.transposed != 0, xd, yd, o.precision);
+    P->path = ConvPath::Gather;
+    P->ws_need = 0;
+    if (head && which == 0 && k[0] == 4) {
+        P->path = ConvPath::HeadFwd;
+        P->ws_need = head_fwd_bytes(xd, k[0]);
+    } else if (head && which == 1 && k[0] == 1) P->path = ConvPath::HeadDgrad;
+    else if (!direct && !op.stats && !c.gate && plan_thin_quad(src, dst, k, s, p, c.act, c.slope, c.accumulate, &P->quad)) P->path = ConvPath::Quad;
+    if (P->path != ConvPath::Gather && !sizes) return DCV_OK;
+    const int rc = plan_gather(op, o, &P->gp);
+    if (rc != DCV_OK) return rc;
+    P->ws_need = std::max(P->ws_need, P->gp.ws_need);
+    return DCV_OK;
+}
+
+// Launch a planned forward / data-gradient call, after checking every buffer it needs
+static int run_conv(const ConvCall& c, const ConvPlan& P, const CallOpts& o, void* ws, size_t ws_bytes, void* stream, int* stat_parts = nullptr) {
+    if (stat_parts) *stat_parts = 0;
+    // a caller-owned packed copy is valid for ONE effective precision (its format depends on it): never read or fill one stamped for another
+    if (c.pack && c.pack->buf && c.pack->precision != o.precision + 1)
+        return fail(DCV_EINVAL, "conv: dcv_wpack.precision is %d but this call runs at precision %d (1 fp32, 2 bf16 products, 3 fp32-on-bf16): %s",
+                    c.pack->precision, o.precision + 1, c.pack->ready ? "a ready pack of another format would be read" : "stamp the buffer with dcv_conv_effective_precision(g)");
+    if (!c.src || !c.w || !c.dst) return fail(DCV_EINVAL, "conv: null pointer");
+    if (P.ws_need > ws_bytes) return fail(DCV_EWORKSPACE, "%s: workspace too small (%zu needed, %zu given)", P.op.tag, P.ws_need, ws_bytes);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (P.path) {
+    case ConvPath::HeadFwd: return run_head_fwd(c.src, P.xd, c.w, c.dst, P.yd, P.g.kd, c.act, c.slope, ws, st);
+    case ConvPath::HeadDgrad: return run_head_dgrad(c.src, P.yd, c.w, c.dst, P.xd, P.g.kd, c.accumulate, st);
+    case ConvPath::Quad: return run_thin_quad(P.quad, c.src, c.dst, c.w, P.g.kd, st);
+    case ConvPath::Gather: break;
+    }
+    if (c.pack && c.pack->buf && P.gp.pack_need > c.pack->bytes)
+        return fail(DCV_EWORKSPACE, "%s: packed-weight buffer too small (%zu needed, %zu given)", P.op.tag, P.gp.pack_need, c.pack->bytes);
+    const int rc = run_gather(P.op, P.gp, o, c.pack, ws, st);
+    if (rc == DCV_OK && stat_parts) *stat_parts = P.gp.stat_parts;
+    return rc;
+}
+
+static int conv_call(const ConvCall& c, void* ws, size_t ws_bytes, void* stream) {
+    CallOpts o; ConvPlan P;
+    int rc = call_opts(c.g, &o, "conv");
+    if (rc == DCV_OK) rc = plan_conv(c, o, &P);
+    return rc == DCV_OK ? run_conv(c, P, o, ws, ws_bytes, stream) : rc;
+}
+
+// the weight gradient of a conv / convT call as a wgrad GEMM:
+//   conv : dw[co][ci][k] = sum dy[n,co,o] x[n,ci,o*s-p+k]  -> dense = dy, gathered = x
+//   convT: dw[ci][co][k] = sum x[n,ci,i] dy[n,co,i*s-p+k]  -> dense = x,  gathered = dy
+static int plan_wgrad_call(const dcv_conv_geom* g, const float* x, const dcv_dims5* xd, const float* dy, const dcv_dims5* dyd, float* dw, const CallOpts& o,
+                           WgradOp* op, WgradPlan* P) {
+    dcv_conv_geom g2; dcv_dims5 y2;
+    if (latent_form(g, xd, dyd, &g2, &y2)) { g = &g2; dyd = &y2; }
+    const int rc = check_geom(g, xd, dyd, "conv_bwd_weight");
+    if (rc != DCV_OK) return rc;
+    if (o.bnview && !g->transposed) return fail(DCV_EUNSUPPORTED, "conv_bwd_weight: BatchNorm on load reads the dense operand: the input of a transposed convolution");
+    const int k[3] = {g->kd, g->kh, g->kw}, s[3] = {g->sd, g->sh, g->sw}, p[3] = {g->pd, g->ph, g->pw};
+    for (int d = 0; d < 3; ++d) { op->k[d] = k[d]; op->s[d] = s[d]; op->p[d] = p[d]; }
+    if (!g->transposed) { op->D = dy; op->dd = *dyd; op->G = x; op->gd = *xd; op->tag = "conv_bwd_weight"; }
+    else { op->D = x; op->dd = *xd; op->G = dy; op->gd = *dyd; op->tag = "convT_bwd_weight"; }
+    op->R = dw;
+    return plan_wgrad(*op, o, P);
+}
+
+static int wgrad_call(const dcv_conv_geom* g, const float* x, const dcv_dims5* xd, const float* dy, const dcv_dims5* dyd, float* dw,
+                      void* ws, size_t ws_bytes, void* stream, const CallOpts& o) {
+    WgradOp op; WgradPlan P;
+    int rc = plan_wgrad_call(g, x, xd, dy, dyd, dw, o, &op, &P);
+    if (rc != DCV_OK) return rc;
+    if (!x || !dy || !dw || !ws) return fail(DCV_EINVAL, "conv_bwd_weight: null pointer");
+    if (o.bnview && !P.bn)
+        return fail(DCV_EUNSUPPORTED, "conv_backward_weight_bn: not the 3-channel 3x3 transposed head on 64-wide rows with 128 k input channels and a 16-byte aligned BatchNorm input");
+    if (P.need > ws_bytes) return fail(DCV_EWORKSPACE, "%s: workspace too small (%zu needed, %zu given)", op.tag, P.need, ws_bytes);
+    return run_wgrad(op, P, o, ws, static_cast<hipStream_t>(stream));
+}
+
+// Sizes: for the inputs a query cannot see (a stats buffer, a caller-owned pack, a gated epilogue, a BatchNorm view) the largest need of the plans they lead to.
+// A stats buffer can only switch the ragged split-K off, a pack only moves the packed weights out of the workspace, a BatchNorm view only drops K splits.
+static int plan_sizes(const dcv_conv_geom* g, const dcv_dims5* x, const dcv_dims5* y, int which, bool stats, ConvPlan* P) {
+    CallOpts o; ConvCall c;
+    c.which = which; c.g = g; c.xd = x; c.yd = y; c.stats = stats;
+    const int rc = call_opts(g, &o, "conv");
+    return rc != DCV_OK ? rc : plan_conv(c, o, P, true);
 }
 
 size_t dcv_conv_workspace_bytes(const dcv_conv_geom* g, const dcv_dims5* x, const dcv_dims5* y, int which) {
-    size_t need = 0;
-    if (which == 2) {
-        dcv_conv_geom g2;
-        dcv_dims5 y2;
-        if (latent_form(g, x, y, &g2, &y2)) return dcv_conv_workspace_bytes(&g2, x, &y2, 2);
-        if (check_geom(g, x, y, "conv_ws") != DCV_OK) return 0;
-        const int k[3] = {g->kd, g->kh, g->kw}, s[3] = {g->sd, g->sh, g->sw}, p[3] = {g->pd, g->ph, g->pw};
-        const dcv_dims5& D = g->transposed ? *x : *y;
-        const dcv_dims5& G = g->transposed ? *y : *x;
-        if (run_wgrad(nullptr, D, nullptr, G, nullptr, k, s, p, nullptr, 0, nullptr, "ws", &need) != DCV_OK) return 0;
-        return need;
-    }
-    if (conv_dispatch(which, g, nullptr, x, nullptr, nullptr, y, 0, 0.f, 0, nullptr, 0, nullptr, &need) != DCV_OK) return 0;
-    return need;
+    if (which != 2) { ConvPlan P; return plan_sizes(g, x, y, which, false, &P) == DCV_OK ? P.ws_need : 0; }
+    CallOpts o; WgradOp op; WgradPlan P, t;
+    if (call_opts(g, &o, "conv") != DCV_OK || plan_wgrad_call(g, nullptr, x, nullptr, y, nullptr, o, &op, &P) != DCV_OK) return 0;
+    // thinj / stem3d need 16-byte aligned operands: a call with other ones takes the tiled kernels
+    if ((P.kind == WK::ThinJ || P.kind == WK::Stem3d) && plan_tiled_wgrad(op, o, &t) == DCV_OK) return std::max(P.need, t.need);
+    return P.need;
 }
 
 size_t dcv_conv_backward_data_bn_workspace_bytes(const dcv_dims5* dx, int cbn) {
@@ -4791,68 +4786,67 @@ int dcv_conv_backward_data_bn(const dcv_conv_geom* g, const float* dy, const dcv
         return fail(DCV_EINVAL, "conv_backward_data_bn: null pointer");
     *fused = 0;
     if (act != DCV_ACT_NONE && act != DCV_ACT_LEAKY) return fail(DCV_EUNSUPPORTED, "conv_backward_data_bn: the BatchNorm's activation must be none or (Leaky)ReLU");
-    if (eff_precision() != 0 && !(g && g->mfma == 1)) return fail(DCV_EUNSUPPORTED, "conv_backward_data_bn: fp32 path only");
+    CallOpts o;
+    int rc = call_opts(g, &o, "conv_backward_data_bn");
+    if (rc != DCV_OK) return rc;
+    if (o.precision != 0) return fail(DCV_EUNSUPPORTED, "conv_backward_data_bn: fp32 path only");
     const size_t pbytes = align_up((size_t)dxd->n * dxd->d * ((dxd->h + 3) / 4) * cbn * 2 * sizeof(float), 256);
     if (ws2_bytes < dcv_conv_backward_data_bn_workspace_bytes(dxd, cbn)) return fail(DCV_EWORKSPACE, "conv_backward_data_bn: second workspace too small");
-    HeadBnRequest hb;
-    memset(&hb, 0, sizeof(hb));
-    hb.mode = 1;
-    hb.bx = bn_x; hb.bxd = *bn_xd; hb.bdx = bn_dx; hb.bdxd = *bn_dxd;
-    hb.gamma = gamma; hb.beta = beta; hb.mean = save_mean; hb.invstd = save_invstd;
-    hb.partial = static_cast<float*>(ws2); hb.partial_bytes = pbytes;
     float* cst = reinterpret_cast<float*>(static_cast<char*>(ws2) + pbytes);
-    hb.cst = cst;
-    hb.cbn = cbn; hb.slope = act == DCV_ACT_LEAKY ? slope : 1.f;
-    t_headbn = &hb;
-    int rc = conv_dispatch(1, g, dy, dxd, w, dx, dyd, DCV_ACT_NONE, 0.f, 0, ws, ws_bytes, stream, nullptr, nullptr, 0, nullptr, nullptr, pack);
-    t_headbn = nullptr;
-    if (rc != DCV_OK || !hb.used) return rc;      // not the head's geometry: the plain data gradient ran, dx is complete, *fused stays 0
+    HeadBnRequest hb{1, bn_x, *bn_xd, bn_dx, *bn_dxd, gamma, beta, save_mean, save_invstd, cst, static_cast<float*>(ws2), pbytes, cbn, act == DCV_ACT_LEAKY ? slope : 1.f};
+    o.headbn = &hb;
+    ConvCall c; ConvPlan P;
+    c.which = 1; c.g = g; c.xd = dxd; c.yd = dyd; c.src = dy; c.w = w; c.dst = dx; c.pack = pack;
+    if ((rc = plan_conv(c, o, &P)) != DCV_OK) return rc;
+    const bool fuse = P.path == ConvPath::Gather && P.gp.cls.size() == 1 && P.gp.cls[0].kind == GK::HeadBn;
+    // head_bn_kernel<1> — or, for any other geometry, the plain data gradient: dx is complete, *fused stays 0
+    if ((rc = run_conv(c, P, o, ws, ws_bytes, stream)) != DCV_OK || !fuse) return rc;
     const double count = (double)bn_xd->n * bn_xd->d * bn_xd->h * bn_xd->w;
-    hipLaunchKernelGGL(head_bn_finalize_kernel, dim3(cbn), dim3(256), 0, static_cast<hipStream_t>(stream), hb.partial, hb.nwg, cbn, count, gamma, save_invstd, dgamma, dbeta, cst);
+    hipLaunchKernelGGL(head_bn_finalize_kernel, dim3(cbn), dim3(256), 0, static_cast<hipStream_t>(stream), hb.partial, (int)P.gp.cls[0].grid.x, cbn, count, gamma, save_invstd, dgamma, dbeta, cst);
     DCV_LAUNCH_CHECK();
     hb.mode = 2;
-    hb.used = 0;
     dcv_wpack pk2;
-    const dcv_wpack* pk2p = nullptr;
-    if (pack && pack->buf) { pk2 = *pack; pk2.ready = 1; pk2p = &pk2; }      // the first call packed the weights
-    t_headbn = &hb;
-    rc = conv_dispatch(1, g, dy, dxd, w, dx, dyd, DCV_ACT_NONE, 0.f, 0, ws, ws_bytes, stream, nullptr, nullptr, 0, nullptr, nullptr, pk2p);
-    t_headbn = nullptr;
-    if (rc != DCV_OK) return rc;
-    if (!hb.used) return fail(DCV_EINVAL, "conv_backward_data_bn: internal: the second pass did not take the fused kernel");
+    if (pack && pack->buf) { pk2 = *pack; pk2.ready = 1; c.pack = &pk2; }      // the first pass packed the weights
+    if ((rc = run_conv(c, P, o, ws, ws_bytes, stream)) != DCV_OK) return rc;
     *fused = 1;
     return DCV_OK;
 }
 
 size_t dcv_conv_packed_bytes(const dcv_conv_geom* g, const dcv_dims5* x, const dcv_dims5* y, int which) {
-    size_t need = 0;
-    if (which != 0 && which != 1) return 0;
-    if (conv_dispatch(which, g, nullptr, x, nullptr, nullptr, y, 0, 0.f, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, &need) != DCV_OK) return 0;
-    return need;
+    ConvPlan P;
+    return (which == 0 || which == 1) && plan_sizes(g, x, y, which, false, &P) == DCV_OK ? P.gp.pack_need : 0;
 }
 
 int dcv_conv_forward(const dcv_conv_geom* g, const float* x, const dcv_dims5* xd, const float* w, float* y, const dcv_dims5* yd,
                      int act, float slope, const dcv_wpack* pack, void* ws, size_t ws_bytes, void* stream) {
-    return conv_dispatch(0, g, x, xd, w, y, yd, act, slope, 0, ws, ws_bytes, stream, nullptr, nullptr, 0, nullptr, nullptr, pack);
+    ConvCall c;
+    c.g = g; c.xd = xd; c.yd = yd; c.src = x; c.w = w; c.dst = y; c.act = act; c.slope = slope; c.pack = pack;
+    return conv_call(c, ws, ws_bytes, stream);
 }
 
 size_t dcv_conv_stats_bytes(const dcv_conv_geom* g, const dcv_dims5* x, const dcv_dims5* y) {
-    size_t need = 0;
-    if (conv_dispatch(0, g, nullptr, x, nullptr, nullptr, y, 0, 0.f, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, &need) != DCV_OK) return 0;
-    return need;
+    ConvPlan P;
+    return plan_sizes(g, x, y, 0, true, &P) == DCV_OK && P.op.stats ? P.gp.stat_need : 0;
 }
 
 int dcv_conv_forward_stats(const dcv_conv_geom* g, const float* x, const dcv_dims5* xd, const float* w, float* y, const dcv_dims5* yd,
                            float* stat, size_t stat_bytes, int* nparts, int* pitch, const dcv_wpack* pack, void* ws, size_t ws_bytes, void* stream) {
     if (!stat || !nparts || !pitch) return fail(DCV_EINVAL, "conv_forward_stats: null pointer");
-    const TileCfg tc = pick_gather_tile(yd ? yd->c : 1);
-    *pitch = yd ? (yd->c + tc.bn - 1) / tc.bn * tc.bn : 0;
-    return conv_dispatch(0, g, x, xd, w, y, yd, DCV_ACT_NONE, 0.f, 0, ws, ws_bytes, stream, nullptr, stat, stat_bytes, nparts, nullptr, pack);
+    CallOpts o; ConvCall c; ConvPlan P;
+    int rc = call_opts(g, &o, "conv");
+    if (rc != DCV_OK) return rc;
+    c.g = g; c.xd = xd; c.yd = yd; c.src = x; c.w = w; c.dst = y; c.pack = pack;
+    c.stats = true; c.stat = stat; c.stat_bytes = stat_bytes;
+    if ((rc = plan_conv(c, o, &P)) != DCV_OK) return rc;
+    *pitch = P.gp.OCp;
+    return run_conv(c, P, o, ws, ws_bytes, stream, nparts);
 }
 
 int dcv_conv_backward_data(const dcv_conv_geom* g, const float* dy, const dcv_dims5* dyd, const float* w, float* dx, const dcv_dims5* dxd,
                            int accumulate, const dcv_wpack* pack, void* ws, size_t ws_bytes, void* stream) {
-    return conv_dispatch(1, g, dy, dxd, w, dx, dyd, DCV_ACT_NONE, 0.f, accumulate, ws, ws_bytes, stream, nullptr, nullptr, 0, nullptr, nullptr, pack);
+    ConvCall c;
+    c.which = 1; c.g = g; c.xd = dxd; c.yd = dyd; c.src = dy; c.w = w; c.dst = dx; c.accumulate = accumulate; c.pack = pack;
+    return conv_call(c, ws, ws_bytes, stream);
 }
 
 int dcv_conv_backward_data_gated(const dcv_conv_geom* g, const float* dy, const dcv_dims5* dyd, const float* w, float* dx, const dcv_dims5* dxd,
@@ -4862,85 +4856,17 @@ int dcv_conv_backward_data_gated(const dcv_conv_geom* g, const float* dy, const 
     if (act != DCV_ACT_LEAKY) return fail(DCV_EUNSUPPORTED, "conv_backward_data_gated: only (Leaky)ReLU derivatives can be read off the input");
     if (!same_shape(*xd, *dxd) || xd->sn != dxd->sn || xd->sc != dxd->sc || xd->sd != dxd->sd || xd->sh != dxd->sh || xd->sw != dxd->sw)
         return fail(DCV_EUNSUPPORTED, "conv_backward_data_gated: x and dx must share shape and strides");
-    return conv_dispatch(1, g, dy, dxd, w, dx, dyd, DCV_ACT_NONE, 0.f, accumulate, ws, ws_bytes, stream, nullptr, nullptr, 0, nullptr, nullptr, pack, nullptr, x, slope);
+    ConvCall c;
+    c.which = 1; c.g = g; c.xd = dxd; c.yd = dyd; c.src = dy; c.w = w; c.dst = dx; c.accumulate = accumulate; c.pack = pack;
+    c.gate = x; c.gate_slope = slope;
+    return conv_call(c, ws, ws_bytes, stream);
 }
 
 int dcv_conv_backward_weight(const dcv_conv_geom* g, const float* x, const dcv_dims5* xd, const float* dy, const dcv_dims5* dyd,
                              float* dw, void* ws, size_t ws_bytes, void* stream) {
-    if (g && (g->mfma < 0 || g->mfma > 3)) return fail(DCV_EINVAL, "conv_bwd_weight: dcv_conv_geom.mfma must be 0, 1, 2 or 3");
-    PrecisionScope prec_scope(g);
-    {
-        dcv_conv_geom g2;
-        dcv_dims5 y2;
-        if (latent_form(g, xd, dyd, &g2, &y2)) return dcv_conv_backward_weight(&g2, x, xd, dy, &y2, dw, ws, ws_bytes, stream);
-    }
-    int rc = check_geom(g, xd, dyd, "conv_bwd_weight");
-    if (rc != DCV_OK) return rc;
-    if (!x || !dy || !dw || !ws) return fail(DCV_EINVAL, "conv_bwd_weight: null pointer");
-    const int k[3] = {g->kd, g->kh, g->kw}, s[3] = {g->sd, g->sh, g->sw}, p[3] = {g->pd, g->ph, g->pw};
-    // conv : dw[co][ci][k] = sum dy[n,co,o] x[n,ci,o*s-p+k]  -> dense = dy, gathered = x
-    // convT: dw[ci][co][k] = sum x[n,ci,i] dy[n,co,i*s-p+k]  -> dense = x,  gathered = dy
-    if (!g->transposed)
-        return run_wgrad(dy, *dyd, x, *xd, dw, k, s, p, ws, ws_bytes, static_cast<hipStream_t>(stream), "conv_bwd_weight", nullptr);
-    return run_wgrad(x, *xd, dy, *dyd, dw, k, s, p, ws, ws_bytes, static_cast<hipStream_t>(stream), "convT_bwd_weight", nullptr);
-}
-
-// The geometry BOTH normalise-on-load kernels take (the forward must only leave the BatchNorm output unwritten where the weight gradient can do without it too):
-// the 3x3 / 1 / 1 transposed head with 3 output channels on 64-wide rows, 128 k input channels, whole 32-channel BatchNorm groups, 16-byte aligned BatchNorm input
-static bool head_on_load_ok(const dcv_conv_geom* g, const dcv_dims5* xd, const dcv_dims5* yd, int cbn, const float* bn_x, const dcv_dims5* bn_xd) {
-    return g->transposed && g->kd == 1 && g->kh == 3 && g->kw == 3 && g->sd == 1 && g->sh == 1 && g->sw == 1 && g->pd == 0 && g->ph == 1 && g->pw == 1 &&
-           yd->c == 3 && xd->c % 128 == 0 && xd->w == 64 && yd->w == 64 && xd->h == yd->h && xd->h % 4 == 0 && xd->sw == 1 && (g->mfma == 0 || g->mfma == 1) &&
-           cbn % 32 == 0 && cbn > 0 && cbn <= xd->c && bn_xd && bn_xd->sc % 4 == 0 && bn_xd->sh % 4 == 0 && bn_xd->sn % 4 == 0 && bn_xd->sh == xd->sh &&
-           (reinterpret_cast<uintptr_t>(bn_x) & 15) == 0 && xd->sc % 4 == 0 && xd->sh % 4 == 0 && xd->sn % 4 == 0;
-}
-
-static int bn_view_of(BnView* v, int cbn, const float* bn_x, const dcv_dims5* bn_xd, const float* gamma, const float* beta, const float* mean, const float* invstd,
-                      int bn_act, float bn_slope, const dcv_dims5* xd, const char* tag) {
-    if (!bn_x || !bn_xd || !gamma || !beta || !mean || !invstd || !xd) return fail(DCV_EINVAL, "%s: null pointer", tag);
-    if (bn_act != DCV_ACT_NONE && bn_act != DCV_ACT_LEAKY) return fail(DCV_EUNSUPPORTED, "%s: the BatchNorm's activation must be none or (Leaky)ReLU", tag);
-    if (eff_precision() != 0) return fail(DCV_EUNSUPPORTED, "%s: fp32 path only", tag);
-    if (cbn < 1 || cbn > xd->c || bn_xd->c != cbn || bn_xd->n != xd->n || bn_xd->d != 1 || xd->d != 1 || bn_xd->h != xd->h || bn_xd->w != xd->w || bn_xd->sw != 1 ||
-        bn_xd->sn < 0 || bn_xd->sc < 0 || bn_xd->sh < 0 || (int64_t)cbn * bn_xd->sc + (int64_t)bn_xd->h * bn_xd->sh >= (1ll << 29))
-        return fail(DCV_EUNSUPPORTED, "%s: the BatchNorm input must match the operand's first channels (2-D, unit column stride)", tag);
-    memset(v, 0, sizeof(*v));
-    v->bx = bn_x; v->gamma = gamma; v->beta = beta; v->mean = mean; v->invstd = invstd;
-    v->bx_sn = bn_xd->sn; v->bx_sc = (int32_t)bn_xd->sc; v->bx_sh = (int32_t)bn_xd->sh; v->cbn = cbn; v->act = bn_act; v->slope = bn_slope;
-    return DCV_OK;
-}
-
-int dcv_conv_forward_bn(const dcv_conv_geom* g, const float* x, const dcv_dims5* xd, const float* w, float* y, const dcv_dims5* yd, int act, float slope,
-                        const dcv_wpack* pack, void* ws, size_t ws_bytes, int cbn, const float* bn_x, const dcv_dims5* bn_xd, const float* gamma, const float* beta,
-                        const float* save_mean, const float* save_invstd, int bn_act, float bn_slope, void* stream) {
-    // only the RGB head's geometry has the kernel: refuse everything else BEFORE anything runs (the caller then materialises the BatchNorm output: dcv_bn_apply)
-    if (!g || !xd || !yd) return fail(DCV_EINVAL, "conv_forward_bn: null pointer");
-    if (!head_on_load_ok(g, xd, yd, cbn, bn_x, bn_xd) || (x && (reinterpret_cast<uintptr_t>(x) & 15) != 0))
-        return fail(DCV_EUNSUPPORTED, "conv_forward_bn: not the 3-channel 3x3 transposed head on 64-wide rows with 128 k input channels");
-    BnView v;
-    int rc = bn_view_of(&v, cbn, bn_x, bn_xd, gamma, beta, save_mean, save_invstd, bn_act, bn_slope, xd, "conv_forward_bn");
-    if (rc != DCV_OK) return rc;
-    t_bnview = &v;
-    rc = conv_dispatch(0, g, x, xd, w, y, yd, act, slope, 0, ws, ws_bytes, stream, nullptr, nullptr, 0, nullptr, nullptr, pack);
-    t_bnview = nullptr;
-    if (rc == DCV_OK && !v.used) return fail(DCV_EINVAL, "conv_forward_bn: internal: the dispatch did not reach the head's kernel (the output was computed from an unwritten operand)");
-    return rc;
-}
-
-int dcv_conv_backward_weight_bn(const dcv_conv_geom* g, const float* x, const dcv_dims5* xd, const float* dy, const dcv_dims5* dyd, float* dw, int accumulate,
-                                void* ws, size_t ws_bytes, int cbn, const float* bn_x, const dcv_dims5* bn_xd, const float* gamma, const float* beta,
-                                const float* save_mean, const float* save_invstd, int bn_act, float bn_slope, void* stream) {
-    if (!g || !xd || !dyd) return fail(DCV_EINVAL, "conv_backward_weight_bn: null pointer");
-    if (!head_on_load_ok(g, xd, dyd, cbn, bn_x, bn_xd))
-        return fail(DCV_EUNSUPPORTED, "conv_backward_weight_bn: not the 3-channel 3x3 transposed head on 64-wide rows with 128 k input channels");
-    BnView v;
-    int rc = bn_view_of(&v, cbn, bn_x, bn_xd, gamma, beta, save_mean, save_invstd, bn_act, bn_slope, xd, "conv_backward_weight_bn");
-    if (rc != DCV_OK) return rc;
-    t_bnview = &v;
-    t_wgrad_acc = accumulate ? 1 : 0;
-    rc = dcv_conv_backward_weight(g, x, xd, dy, dyd, dw, ws, ws_bytes, stream);
-    t_wgrad_acc = 0;
-    t_bnview = nullptr;
-    if (rc == DCV_OK && !v.used) return fail(DCV_EINVAL, "conv_backward_weight_bn: internal: the dispatch did not reach the head's kernel");
-    return rc;
+    CallOpts o;
+    const int rc = call_opts(g, &o, "conv_bwd_weight");
+    return rc == DCV_OK ? wgrad_call(g, x, xd, dy, dyd, dw, ws, ws_bytes, stream, o) : rc;
 }
 
 // dw = (accumulate ? dw : 0) + corr(x, dy): a weight used twice in one backward (a discriminator on the real and the fake batch, trainer.py:299-309) or whose
@@ -4948,10 +4874,58 @@ int dcv_conv_backward_weight_bn(const dcv_conv_geom* g, const float* x, const dc
 // instead of by a separate elementwise add
 int dcv_conv_backward_weight_acc(const dcv_conv_geom* g, const float* x, const dcv_dims5* xd, const float* dy, const dcv_dims5* dyd, float* dw, int accumulate,
                                  void* ws, size_t ws_bytes, void* stream) {
-    t_wgrad_acc = accumulate ? 1 : 0;
-    const int rc = dcv_conv_backward_weight(g, x, xd, dy, dyd, dw, ws, ws_bytes, stream);
-    t_wgrad_acc = 0;
-    return rc;
+    CallOpts o;
+    const int rc = call_opts(g, &o, "conv_bwd_weight");
+    o.wgrad_acc = accumulate ? 1 : 0;
+    return rc == DCV_OK ? wgrad_call(g, x, xd, dy, dyd, dw, ws, ws_bytes, stream, o) : rc;
+}
+
+// The view of the normalise-on-load kernels (thin_rows_kernel, thinj_wgrad_kernel): the operand's first cbn channels are act(BatchNorm(bn_x))
+static int bn_opts(const dcv_conv_geom* g, CallOpts* o, BnView* v, int cbn, const float* bn_x, const dcv_dims5* bn_xd, const float* gamma, const float* beta,
+                   const float* mean, const float* invstd, int bn_act, float bn_slope, const dcv_dims5* xd, const char* tag) {
+    const int rc = call_opts(g, o, tag);
+    if (rc != DCV_OK) return rc;
+    if (!bn_x || !bn_xd || !gamma || !beta || !mean || !invstd || !xd) return fail(DCV_EINVAL, "%s: null pointer", tag);
+    if (bn_act != DCV_ACT_NONE && bn_act != DCV_ACT_LEAKY) return fail(DCV_EUNSUPPORTED, "%s: the BatchNorm's activation must be none or (Leaky)ReLU", tag);
+    if (o->precision != 0) return fail(DCV_EUNSUPPORTED, "%s: fp32 path only", tag);
+    if (cbn < 1 || cbn > xd->c || bn_xd->c != cbn || bn_xd->n != xd->n || bn_xd->d != 1 || xd->d != 1 || bn_xd->h != xd->h || bn_xd->w != xd->w || bn_xd->sw != 1 ||
+        bn_xd->sn < 0 || bn_xd->sc < 0 || bn_xd->sh < 0 || (int64_t)cbn * bn_xd->sc + (int64_t)bn_xd->h * bn_xd->sh >= (1ll << 29))
+        return fail(DCV_EUNSUPPORTED, "%s: the BatchNorm input must match the operand's first channels (2-D, unit column stride)", tag);
+    memset(v, 0, sizeof(*v));
+    v->bx = bn_x; v->gamma = gamma; v->beta = beta; v->mean = mean; v->invstd = invstd;
+    v->bx_sn = bn_xd->sn; v->bx_sc = (int32_t)bn_xd->sc; v->bx_sh = (int32_t)bn_xd->sh; v->cbn = cbn; v->act = bn_act; v->slope = bn_slope;
+    o->bnview = v;
+    return DCV_OK;
+}
+
+int dcv_conv_forward_bn(const dcv_conv_geom* g, const float* x, const dcv_dims5* xd, const float* w, float* y, const dcv_dims5* yd, int act, float slope,
+                        const dcv_wpack* pack, void* ws, size_t ws_bytes, int cbn, const float* bn_x, const dcv_dims5* bn_xd, const float* gamma, const float* beta,
+                        const float* save_mean, const float* save_invstd, int bn_act, float bn_slope, void* stream) {
+    if (!g || !xd || !yd) return fail(DCV_EINVAL, "conv_forward_bn: null pointer");
+    CallOpts o; BnView v; ConvCall c; ConvPlan P;
+    int rc = bn_opts(g, &o, &v, cbn, bn_x, bn_xd, gamma, beta, save_mean, save_invstd, bn_act, bn_slope, xd, "conv_forward_bn");
+    if (rc != DCV_OK) return rc;
+    c.g = g; c.xd = xd; c.yd = yd; c.src = x; c.w = w; c.dst = y; c.act = act; c.slope = slope; c.pack = pack;
+    if ((rc = plan_conv(c, o, &P)) != DCV_OK) return rc;
+    // The BatchNorm output stays unwritten, so the weight gradient dcv_conv_backward_weight_bn later runs on the same operands must read it on load too:
+    // refuse, before anything runs, unless both plans take their normalise-on-load kernels (the caller then materialises the output: dcv_bn_apply)
+    bool on_load = P.path == ConvPath::Gather && !P.gp.cls.empty();
+    for (const ClassPlan& cp : P.gp.cls) on_load = on_load && cp.kind == GK::RowsBn;
+    WgradOp wop; WgradPlan wp;
+    if (!on_load || plan_wgrad_call(g, x, xd, nullptr, yd, nullptr, o, &wop, &wp) != DCV_OK || !wp.bn)
+        return fail(DCV_EUNSUPPORTED, "conv_forward_bn: not the 3-channel 3x3 transposed head on 64-wide rows with 128 k input channels and a 16-byte aligned BatchNorm input");
+    return run_conv(c, P, o, ws, ws_bytes, stream);
+}
+
+int dcv_conv_backward_weight_bn(const dcv_conv_geom* g, const float* x, const dcv_dims5* xd, const float* dy, const dcv_dims5* dyd, float* dw, int accumulate,
+                                void* ws, size_t ws_bytes, int cbn, const float* bn_x, const dcv_dims5* bn_xd, const float* gamma, const float* beta,
+                                const float* save_mean, const float* save_invstd, int bn_act, float bn_slope, void* stream) {
+    if (!g || !xd || !dyd) return fail(DCV_EINVAL, "conv_backward_weight_bn: null pointer");
+    CallOpts o; BnView v;
+    const int rc = bn_opts(g, &o, &v, cbn, bn_x, bn_xd, gamma, beta, save_mean, save_invstd, bn_act, bn_slope, xd, "conv_backward_weight_bn");
+    if (rc != DCV_OK) return rc;
+    o.wgrad_acc = accumulate ? 1 : 0;
+    return wgrad_call(g, x, xd, dy, dyd, dw, ws, ws_bytes, stream, o);
 }
 
 }  // extern "C"

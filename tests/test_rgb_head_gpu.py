@@ -254,3 +254,44 @@ def test_round6_entries_refuse_bad_arguments(dev):
     # ... and the same call with good arguments runs and reports the fused path
     N.check(bwd(ptr(dy), ops.ACT_LEAKY, need2), "dcv_conv_backward_data_bn")
     assert fused.value == 1 and bool(torch.isfinite(bdx).all()) and bool(torch.isfinite(dx[:, cbn:]).all())
+
+
+_REFUSAL_CHILD = r"""
+import ctypes as C, sys, torch
+from dcvgan_amd import native as N, ops
+from dcvgan_amd.native import dims5, ptr, stream_ptr
+dev = torch.device("cuda:0")
+n, h, cbn, C_ = 3, 32, 64, 128
+w = torch.randn(C_, 3, 3, 3, device=dev) * 0.1
+bx = torch.randn(n, cbn, h, 64, device=dev)
+v = torch.ones(cbn, device=dev)
+holey = torch.full((n, C_, h, 64), float("nan"), device=dev)
+y = torch.full((n, 3, h, 64), 7.0, device=dev)
+geom = ops.conv_geom(w, (1, 1), (1, 1), True)
+L = N.lib()
+xd, yd, bxd = dims5(holey), dims5(y), dims5(bx)
+need = max(L.dcv_conv_workspace_bytes(C.byref(geom), C.byref(xd), C.byref(yd), 0), L.dcv_conv_workspace_bytes(C.byref(geom), C.byref(xd), C.byref(yd), 2))
+ws = torch.empty(need, dtype=torch.uint8, device=dev)
+torch.cuda.synchronize()
+before = L.dcv_launch_count()
+rc = L.dcv_conv_forward_bn(C.byref(geom), ptr(holey), C.byref(xd), ptr(w), ptr(y), C.byref(yd), ops.ACT_TANH, 0.0, None, ptr(ws), need,
+                           cbn, ptr(bx), C.byref(bxd), ptr(v), ptr(v), ptr(v), ptr(v), ops.ACT_LEAKY, 0.0, stream_ptr())
+torch.cuda.synchronize()
+assert rc == N.DCV_EUNSUPPORTED, (rc, L.dcv_last_error())
+assert L.dcv_launch_count() == before
+assert bool((y == 7.0).all())
+print("REFUSED")
+"""
+
+
+def test_forward_bn_refuses_when_the_weight_gradient_cannot_normalise_on_load(dev):
+    """With the RGB head's weight-gradient kernel switched off (DCV_NO_THINJ_WGRAD), dcv_conv_backward_weight_bn would have no normalise-on-load form, so
+    dcv_conv_forward_bn must refuse before anything runs — the head geometry of test_head_forward_and_weight_gradient_normalise_on_load, in a fresh
+    process because the switches are read once per process."""
+    import os
+    import subprocess
+    import sys
+    env = dict(os.environ, DCV_NO_THINJ_WGRAD="1")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", _REFUSAL_CHILD], cwd=root, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "REFUSED" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
