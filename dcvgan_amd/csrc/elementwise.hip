@@ -777,7 +777,7 @@ struct AdamPack {
     int64_t n[ADAM_MT];
     int32_t first_block[ADAM_MT + 1];   // prefix sum of the tensors' block counts (4096 elements per block)
 };
-__global__ __launch_bounds__(256) void adam_multi_kernel(const AdamPack k, int nt, const AdamScalars sc) {
+__device__ __forceinline__ void adam_multi_body(const AdamPack& k, int nt, const AdamScalars& sc) {
     int t = 0;
     while (t + 1 < nt && (int)blockIdx.x >= k.first_block[t + 1]) ++t;
     const int64_t base = (int64_t)((int)blockIdx.x - k.first_block[t]) * 4096;
@@ -794,6 +794,133 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamPack k, int n
         adam_update(pi, g[i], mi, vi, sc);
         m[i] = mi; v[i] = vi; p[i] = pi;
     }
+}
+__global__ __launch_bounds__(256) void adam_multi_kernel(const AdamPack k, int nt, const AdamScalars sc) { adam_multi_body(k, nt, sc); }
+
+// ------------------------------------------------------------------------- //
+// Gradient guard: global norm, clip coefficient, non-finite skip and loss-scale update, all decided on the device
+// ------------------------------------------------------------------------- //
+// Stage 1 (guard_partial_kernel): adam_multi_kernel's block mapping over the gradients (4096 elements per 256-thread block, pointer table by value).  A thread
+// squares and adds its (at most) 16 elements in fp32 and counts those whose exponent bits are all ones; the block combines both in double, in block_sum's fixed
+// order, and stores ONE partial sum and ONE count.  Stage 2 (guard_decide_kernel): one workgroup adds the partials in a fixed order and writes the decision into
+// the state array (DCV_GUARD_* in dcvgan_hip.h).  No atomics anywhere: the same gradients give the same bits.
+struct GuardPack {
+    const float* g[ADAM_MT];
+    int64_t n[ADAM_MT];
+    int32_t first_block[ADAM_MT + 1];
+};
+__device__ __forceinline__ void guard_take(float x, float& ss, int& bad) {
+    ss += x * x;
+    bad += ((__float_as_uint(x) & 0x7f800000u) == 0x7f800000u) ? 1 : 0;
+}
+__global__ __launch_bounds__(256) void guard_partial_kernel(const GuardPack k, int nt, int block0, double* __restrict__ part, uint32_t* __restrict__ cnt) {
+    __shared__ double red[8];
+    int t = 0;
+    while (t + 1 < nt && (int)blockIdx.x >= k.first_block[t + 1]) ++t;
+    const int64_t base = (int64_t)((int)blockIdx.x - k.first_block[t]) * 4096;
+    const float* __restrict__ g = k.g[t];
+    const int64_t n = k.n[t];
+    float ss = 0.f;
+    int bad = 0;
+    if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {      // base (hence every block's first element) on a 16-byte boundary: 4 x 16-byte loads per thread
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int64_t i = base + (int64_t)(e * 256 + threadIdx.x) * 4;
+            if (i + 4 <= n) {
+                const float4 x = *reinterpret_cast<const float4*>(g + i);
+                guard_take(x.x, ss, bad); guard_take(x.y, ss, bad); guard_take(x.z, ss, bad); guard_take(x.w, ss, bad);
+            } else {
+                for (int64_t j = i; j < n; ++j) guard_take(g[j], ss, bad);      // the tensor's last 1..3 elements
+            }
+        }
+    } else {
+#pragma unroll 4
+        for (int e = 0; e < 16; ++e) {
+            const int64_t i = base + e * 256 + threadIdx.x;
+            if (i >= n) break;
+            guard_take(g[i], ss, bad);
+        }
+    }
+    double acc[2] = {(double)ss, (double)bad};      // (counts up to 4096: exact)
+    block_sum<2>(acc, red);
+    if (threadIdx.x == 0) {
+        part[block0 + blockIdx.x] = acc[0];
+        cnt[block0 + blockIdx.x] = (uint32_t)acc[1];
+    }
+}
+
+struct GuardRule {
+    double grad_scale, max_norm, growth, backoff;
+    int32_t skip_nonfinite, dynamic, growth_interval;
+};
+__global__ __launch_bounds__(256) void guard_decide_kernel(const double* __restrict__ part, const uint32_t* __restrict__ cnt, int nb, const GuardRule r, float* __restrict__ state) {
+    __shared__ double red[8];
+    double acc[2] = {0.0, 0.0};
+    for (int i = threadIdx.x; i < nb; i += 256) { acc[0] += part[i]; acc[1] += (double)cnt[i]; }
+    block_sum<2>(acc, red);
+    if (threadIdx.x != 0) return;
+    const double ss = acc[0];
+    const float scale = state[DCV_GUARD_LOSS_SCALE];      // the scale the measured backward ran with
+    const double norm = sqrt(ss) * r.grad_scale / (double)scale;
+    const bool bad = acc[1] > 0.0 || !isfinite(ss) || !isfinite((float)norm);
+    double coef = 1.0;
+    if (!bad && r.max_norm > 0.0) coef = fmin(1.0, r.max_norm / (norm + 1e-6));      // torch.nn.utils.clip_grad_norm_
+    const bool skip = bad && r.skip_nonfinite;
+    state[DCV_GUARD_GRAD_NORM] = (float)norm;
+    state[DCV_GUARD_CLIP_COEF] = (float)coef;
+    state[DCV_GUARD_FACTOR] = (float)(r.grad_scale * coef / (double)scale);
+    state[DCV_GUARD_SKIPPED] = skip ? 1.f : 0.f;
+    state[DCV_GUARD_SKIPPED_TOTAL] += skip ? 1.f : 0.f;
+    state[DCV_GUARD_NONFINITE] = (float)acc[1];
+    if (r.dynamic) {      // torch.amp.GradScaler's update (amp_update_scale): fp32 scale times double factor, rounded once; a growth that would overflow is not taken
+        float tracker = state[DCV_GUARD_GROWTH_TRACKER], s = scale;
+        if (bad) {
+            s = (float)((double)s * r.backoff);
+            tracker = 0.f;
+        } else {
+            tracker += 1.f;
+            if (tracker >= (float)r.growth_interval) {
+                const float grown = (float)((double)s * r.growth);
+                if (isfinite(grown)) s = grown;
+                tracker = 0.f;
+            }
+        }
+        state[DCV_GUARD_LOSS_SCALE] = s;
+        state[DCV_GUARD_GROWTH_TRACKER] = tracker;
+    }
+}
+
+// The guarded Adam step.  guard_adam_prepare_kernel (one thread) reads the guard's decision; unless the step is skipped it advances the DEVICE step count and forms
+// the AdamScalars from it in double — adam_scalars() below, on the device — with the guard's factor as gscale.  The update kernel reads them from the step block.
+struct AdamStepBlock {      // 16 x 4 bytes, caller-owned (DCV_ADAM_STEP_BLOCK_BYTES); [0] is the step count a host may read back
+    int32_t step, skip;
+    AdamScalars sc;
+    int32_t pad[6];
+};
+static_assert(sizeof(AdamStepBlock) == 64, "AdamStepBlock is the 64-byte block the header documents");
+__global__ void guard_adam_prepare_kernel(AdamStepBlock* __restrict__ b, const float* __restrict__ state, double lr, double beta1, double beta2, double eps, double weight_decay) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int skip = state[DCV_GUARD_SKIPPED] != 0.f;
+    b->skip = skip;
+    if (skip) return;
+    const int step = b->step + 1;
+    b->step = step;
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    AdamScalars k;
+    k.w1 = (float)(1.0 - beta1);
+    k.b2 = (float)beta2;
+    k.w2 = (float)(1.0 - beta2);
+    k.eps = (float)eps;
+    k.wd = (float)weight_decay;
+    k.step_size = (float)(lr / bc1);
+    k.bc2_sqrt = (float)sqrt(bc2);
+    k.gscale = state[DCV_GUARD_FACTOR];
+    b->sc = k;
+}
+__global__ __launch_bounds__(256) void adam_multi_guarded_kernel(const AdamPack k, int nt, const AdamStepBlock* __restrict__ b) {
+    if (b->skip) return;      // before any access to p, m or v
+    const AdamScalars sc = b->sc;
+    adam_multi_body(k, nt, sc);
 }
 
 // ------------------------------------------------------------------------- //
@@ -1383,6 +1510,78 @@ int dcv_adam_step_multi(int n_tensors, float* const* p, const float* const* g, f
         k.first_block[nt] = blocks;
         if (blocks == 0) continue;
         hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), k, nt, sc);
+        DCV_LAUNCH_CHECK();
+    }
+    return DCV_OK;
+}
+
+// blocks of stage 1 <= total / 4096 + one ragged block per tensor; a double and a count for each
+static int64_t guard_max_blocks(int64_t total_elements, int n_tensors) { return total_elements / 4096 + n_tensors; }
+
+size_t dcv_grad_guard_workspace_bytes(int64_t total_elements, int n_tensors) {
+    if (total_elements < 0 || n_tensors < 0) { fail(DCV_EINVAL, "grad_guard_workspace_bytes: bad arguments"); return 0; }
+    return align_up((size_t)std::max<int64_t>(1, guard_max_blocks(total_elements, n_tensors)) * (sizeof(double) + sizeof(uint32_t)), 256);
+}
+
+int dcv_grad_guard_measure(int n_tensors, const float* const* g, const int64_t* numel, double grad_scale, double max_norm, int skip_nonfinite, int dynamic,
+                           double growth_factor, double backoff_factor, int growth_interval, float* state, void* ws, size_t ws_bytes, void* stream) {
+    if (n_tensors < 0 || (n_tensors > 0 && (!g || !numel)) || !state || !ws || !(grad_scale > 0.0) || (dynamic && (!(growth_factor > 0.0) || !(backoff_factor > 0.0) || growth_interval < 1)))
+        return fail(DCV_EINVAL, "grad_guard_measure: bad arguments");
+    int64_t nb = 0;
+    for (int t = 0; t < n_tensors; ++t) {
+        if (!g[t] || numel[t] < 0) return fail(DCV_EINVAL, "grad_guard_measure: null tensor");
+        nb += (numel[t] + 4095) / 4096;
+    }
+    if (nb > INT32_MAX) return fail(DCV_EINVAL, "grad_guard_measure: too many elements");
+    if ((size_t)nb * (sizeof(double) + sizeof(uint32_t)) > ws_bytes) return fail(DCV_EWORKSPACE, "grad_guard_measure: workspace too small");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double* part = static_cast<double*>(ws);
+    uint32_t* cnt = reinterpret_cast<uint32_t*>(part + nb);
+    int block0 = 0;
+    for (int t0 = 0; t0 < n_tensors; t0 += ADAM_MT) {
+        GuardPack k;
+        memset(&k, 0, sizeof(k));
+        const int nt = std::min(ADAM_MT, n_tensors - t0);
+        int blocks = 0;
+        for (int t = 0; t < nt; ++t) {
+            k.g[t] = g[t0 + t]; k.n[t] = numel[t0 + t];
+            k.first_block[t] = blocks;
+            blocks += (int)((numel[t0 + t] + 4095) / 4096);
+        }
+        k.first_block[nt] = blocks;
+        if (blocks == 0) continue;
+        hipLaunchKernelGGL(guard_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, block0, part, cnt);
+        DCV_LAUNCH_CHECK();
+        block0 += blocks;
+    }
+    const GuardRule r{grad_scale, max_norm, growth_factor, backoff_factor, skip_nonfinite ? 1 : 0, dynamic ? 1 : 0, growth_interval};
+    hipLaunchKernelGGL(guard_decide_kernel, dim3(1), dim3(256), 0, s, part, cnt, (int)nb, r, state);
+    DCV_LAUNCH_CHECK();
+    return DCV_OK;
+}
+
+int dcv_adam_step_multi_guarded(int n_tensors, float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* numel,
+                                double lr, double beta1, double beta2, double eps, double weight_decay, int32_t* step_block, const float* state, void* stream) {
+    if (n_tensors < 0 || (n_tensors > 0 && (!p || !g || !m || !v || !numel)) || !step_block || !state) return fail(DCV_EINVAL, "adam_step_multi_guarded: bad arguments");
+    for (int t = 0; t < n_tensors; ++t)
+        if (!p[t] || !g[t] || !m[t] || !v[t] || numel[t] < 0) return fail(DCV_EINVAL, "adam_step_multi_guarded: null tensor");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    AdamStepBlock* b = reinterpret_cast<AdamStepBlock*>(step_block);
+    hipLaunchKernelGGL(guard_adam_prepare_kernel, dim3(1), dim3(1), 0, s, b, state, lr, beta1, beta2, eps, weight_decay);
+    DCV_LAUNCH_CHECK();
+    for (int t0 = 0; t0 < n_tensors; t0 += ADAM_MT) {
+        AdamPack k;
+        memset(&k, 0, sizeof(k));
+        const int nt = std::min(ADAM_MT, n_tensors - t0);
+        int blocks = 0;
+        for (int t = 0; t < nt; ++t) {
+            k.p[t] = p[t0 + t]; k.g[t] = g[t0 + t]; k.m[t] = m[t0 + t]; k.v[t] = v[t0 + t]; k.n[t] = numel[t0 + t];
+            k.first_block[t] = blocks;
+            blocks += (int)((numel[t0 + t] + 4095) / 4096);
+        }
+        k.first_block[nt] = blocks;
+        if (blocks == 0) continue;
+        hipLaunchKernelGGL(adam_multi_guarded_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, b);
         DCV_LAUNCH_CHECK();
     }
     return DCV_OK;

@@ -121,6 +121,10 @@ _SIGS = {
     "dcv_cl_bn_act_backward": (C.c_int, [_P, _D, _P, _D, _P, _D, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_float, _P, _P, _P, C.c_size_t, _P]),
     "dcv_adam_step_multi": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, _P]),
     "dcv_adam_step": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, _P]),
+    # the gradient guard (added symbols only: the ABI version stays 4)
+    "dcv_grad_guard_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "dcv_grad_guard_measure": (C.c_int, [C.c_int, _P, _P, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _P, _P, C.c_size_t, _P]),
+    "dcv_adam_step_multi_guarded": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, _P]),
     # the fp16 build of the channels-last path (same signatures; ABI 3)
     "dcv_clf16_packed_bytes": (C.c_size_t, [_G, _D, _D, C.c_int]),
     "dcv_clf16_conv_workspace_bytes": (C.c_size_t, [_G, _D, _D, C.c_int]),

@@ -15,6 +15,10 @@ backward" is explicit state: a post-accumulate-grad hook on every parameter mark
 the bucket dirty, the reduction clears the mark — so the trainer's double
 ``opt_ggen.step()`` reduces once, and nothing depends on object ids or tensor
 version counters.
+
+``GradGuard`` (optional, off by default) gives the optimisers registered with it a global gradient norm, clipping, a
+skip of non-finite steps and (dynamic) loss scaling without a host read: see its docstring.  ``Adam(guard=None)`` is the
+unguarded code path, unchanged.
 """
 from __future__ import annotations
 
@@ -26,14 +30,113 @@ import torch
 from .native import NativeError, _require, check, lib, ptr, stream_ptr
 
 
+class GradGuard:
+    """Global gradient norm, clipping, non-finite skip and loss scaling for the ``Adam`` optimisers registered with it (``Adam(..., guard=g)``), measured, decided
+    and applied on the device: nothing here reads a value on the host or runs a torch kernel.
+
+        loss.backward(guard.root(loss))      # the root cotangent IS the current loss scale (a 0-d device tensor)
+        guard.measure()                      # where a torch trainer calls scaler.unscale_ / clip_grad_norm_: once per backward
+        opt_a.step(); opt_b.step()           # every step on this measurement applies — or skips on — the same decision
+
+    ``measure()`` reads every registered parameter's ``.grad`` once (dcv_grad_guard_measure) and leaves norm, clip coefficient, the factor Adam multiplies the
+    gradients by, the skip flag and the next loss scale in ``state`` (layout: DCV_GUARD_* in include/dcvgan_hip.h).  The decision rule is torch's:
+    ``clip_grad_norm_``'s coefficient min(1, max_norm / (norm + 1e-6)) and ``torch.amp.GradScaler``'s skip / backoff / growth, with one difference: finite gradients
+    whose sum of squares overflows fp32 count as non-finite.  For data-parallel members the gradients are reduced first and the norm is that of the averaged gradient,
+    so every rank decides the same from the same bits."""
+
+    FIELDS = ("loss_scale", "growth_tracker", "grad_norm", "clip_coef", "factor", "skipped", "skipped_total", "nonfinite")
+
+    def __init__(self, max_norm: Optional[float] = None, skip_nonfinite: bool = True, loss_scale: float = 1.0, dynamic: bool = False,
+                 growth_factor: float = 2.0, backoff_factor: float = 0.5, growth_interval: int = 2000):
+        import math
+        if max_norm is not None and not (float(max_norm) > 0.0 and math.isfinite(float(max_norm))):
+            raise ValueError(f"GradGuard: max_norm must be a positive finite number or None, got {max_norm!r}")
+        if not (float(loss_scale) > 0.0 and math.isfinite(float(loss_scale))):
+            raise ValueError(f"GradGuard: loss_scale must be positive and finite, got {loss_scale!r}")
+        if not float(growth_factor) > 1.0:
+            raise ValueError(f"GradGuard: growth_factor must be > 1, got {growth_factor!r}")
+        if not 0.0 < float(backoff_factor) < 1.0:
+            raise ValueError(f"GradGuard: backoff_factor must be in (0, 1), got {backoff_factor!r}")
+        if int(growth_interval) != growth_interval or int(growth_interval) < 1:
+            raise ValueError(f"GradGuard: growth_interval must be a positive integer, got {growth_interval!r}")
+        self.max_norm = None if max_norm is None else float(max_norm)
+        self.skip_nonfinite, self.dynamic = bool(skip_nonfinite), bool(dynamic)
+        self.init_scale = float(loss_scale)
+        self.growth_factor, self.backoff_factor, self.growth_interval = float(growth_factor), float(backoff_factor), int(growth_interval)
+        self.optimizers: List["Adam"] = []
+        self._dp: List["DataParallelAdam"] = []
+        self.state: Optional[torch.Tensor] = None
+        self.measurements = 0
+        self._ws: Optional[torch.Tensor] = None
+        self._tables = None
+
+    def _register(self, opt: "Adam"):
+        self.optimizers.append(opt)
+        dev = opt.params[0].device
+        if self.state is None and dev.type == "cuda":      # (a host tensor -> device copy, once, before training: no kernel)
+            self.state = torch.tensor([self.init_scale] + [0.0] * (len(self.FIELDS) - 1), dtype=torch.float32).to(dev)
+        elif self.state is not None and dev != self.state.device:
+            raise NativeError(f"GradGuard: optimisers on {self.state.device} and {dev} cannot share a guard")
+
+    def _need_state(self) -> torch.Tensor:
+        if self.state is None:
+            raise NativeError("GradGuard: no optimiser with HIP device parameters is registered — the guard runs on the GPU only (there is no CPU fallback)")
+        return self.state
+
+    def root(self, loss: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The cotangent for ``loss.backward(...)``: the loss scale of this backward, a 0-d view of the device state."""
+        return self._need_state()[0]
+
+    def stats(self):
+        """0-d device views of the state (they follow the next ``measure()``; copy what has to outlive it)."""
+        s = self._need_state()
+        return {k: s[self.FIELDS.index(k)] for k in ("grad_norm", "clip_coef", "skipped", "skipped_total", "loss_scale", "nonfinite")}
+
+    @torch.no_grad()
+    def measure(self):
+        state = self._need_state()
+        for w in self._dp:                   # data parallel: the norm of the REDUCED gradient (no-op when the bucket is clean)
+            w.reduce_gradients()
+            w.inner.grad_scale = 1.0 / w.world
+        scales = {o.grad_scale for o in self.optimizers}
+        if len(scales) != 1:
+            raise NativeError(f"GradGuard: the registered optimisers disagree on grad_scale ({sorted(scales)})")
+        gs, ns, keep = [], [], []
+        for o in self.optimizers:
+            for p in o.params:
+                g = p.grad
+                if g is None or g.numel() == 0:
+                    continue
+                _require(g, "GradGuard gradient")
+                g = g.contiguous()
+                gs.append(g.data_ptr()); ns.append(g.numel()); keep.append(g)
+        key = (tuple(gs), tuple(ns))
+        if self._tables is None or self._tables[0] != key:
+            n = len(gs)
+            self._tables = (key, (C.c_void_p * max(n, 1))(*gs), (C.c_int64 * max(n, 1))(*ns), n)
+        _, garr, narr, n = self._tables
+        L = lib()
+        need = L.dcv_grad_guard_workspace_bytes(sum(ns), n)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=state.device)
+        check(L.dcv_grad_guard_measure(n, garr, narr, scales.pop(), self.max_norm if self.max_norm is not None else 0.0, int(self.skip_nonfinite), int(self.dynamic),
+                                       self.growth_factor, self.backoff_factor, self.growth_interval, ptr(state), ptr(self._ws), self._ws.numel(), stream_ptr()),
+              "dcv_grad_guard_measure")
+        self.measurements += 1
+
+
 class Adam:
-    def __init__(self, params: Iterable[torch.nn.Parameter], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0):
+    def __init__(self, params: Iterable[torch.nn.Parameter], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                 guard: Optional[GradGuard] = None):
         self.params: List[torch.nn.Parameter] = [p for p in params]
         if not self.params:
             raise ValueError("optimizer got an empty parameter list")
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
         self.state = {}
         self.grad_scale = 1.0
+        self.guard = guard
+        if guard is not None:
+            guard._register(self)
 
     def zero_grad(self, set_to_none: bool = True):
         for p in self.params:
@@ -42,8 +145,44 @@ class Adam:
             elif p.grad is not None:
                 p.grad.zero_()
 
+    def _step_guarded(self):
+        """The step under a GradGuard: the step count lives on the device (a skipped step must not advance it, and the host does not know), one 64-byte step block
+        per set of parameters that started together — ``state[p]["step"]`` is its first word — and one dcv_adam_step_multi_guarded call per block."""
+        guard = self.guard
+        if guard.measurements == 0:
+            raise NativeError("Adam(guard=...): step() before any guard.measure() — there is no decision to apply")
+        L = lib()
+        st = stream_ptr()
+        groups, touched, fresh = {}, [], None
+        for p in self.params:
+            g = p.grad
+            if g is None:
+                continue
+            _require(p.data, "Adam parameter")
+            if not p.data.is_contiguous():
+                raise NativeError("Adam: parameters must be contiguous")
+            g = g.contiguous()
+            s = self.state.get(p)
+            if s is None:
+                if fresh is None:
+                    fresh = torch.zeros(16, dtype=torch.int32, device=p.device)      # DCV_ADAM_STEP_BLOCK_BYTES
+                s = self.state[p] = {"step": fresh[0], "step_block": fresh, "exp_avg": torch.zeros_like(p.data), "exp_avg_sq": torch.zeros_like(p.data)}
+            touched.append(p)
+            grp = groups.setdefault(s["step_block"].data_ptr(), ([], [], [], [], [], []))
+            grp[0].append(p.data.data_ptr()); grp[1].append(g.data_ptr()); grp[2].append(s["exp_avg"].data_ptr()); grp[3].append(s["exp_avg_sq"].data_ptr())
+            grp[4].append(p.numel()); grp[5].append(g)
+        for block, (ps, gs, ms, vs, ns, _) in groups.items():
+            n = len(ps)
+            arr = lambda xs: (C.c_void_p * n)(*xs)
+            check(L.dcv_adam_step_multi_guarded(n, arr(ps), arr(gs), arr(ms), arr(vs), (C.c_int64 * n)(*ns), self.lr, self.betas[0], self.betas[1],
+                                                self.eps, self.weight_decay, C.c_void_p(block), ptr(guard.state), st), "dcv_adam_step_multi_guarded")
+        if touched:
+            torch.autograd.graph.increment_version(touched)
+
     @torch.no_grad()
     def step(self):
+        if self.guard is not None:
+            return self._step_guarded()
         L = lib()
         st = stream_ptr()
         ps, gs, ms, vs, ns, keep = [], [], [], [], [], []
@@ -328,10 +467,17 @@ class DataParallelAdam:
         self.bucket = bucket if bucket is not None else GradBucket(group)
         self.bucket.add(inner.params)
         self.world = self.bucket.world
+        if getattr(inner, "guard", None) is not None:      # guard.measure() reduces this wrapper's bucket first and measures the averaged gradient (grad_scale = 1 / world)
+            inner.guard._dp.append(self)
+            inner.grad_scale = 1.0 / self.world
 
     @property
     def params(self):
         return self.inner.params
+
+    @property
+    def guard(self):
+        return getattr(self.inner, "guard", None)      # (the wrapper also drives optimisers that know no guard)
 
     def zero_grad(self, set_to_none: bool = True):
         self.inner.zero_grad(set_to_none)

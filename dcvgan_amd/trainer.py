@@ -47,18 +47,22 @@ def build_loss(cfg: StepConfig):
     return Lm.AdversarialLoss() if cfg.loss == "adversarial-loss" else Lm.HingeLoss()
 
 
-def build_optimizers(cfg: StepConfig, models, data_parallel: bool = False, overlap: Optional[bool] = None):
+def build_optimizers(cfg: StepConfig, models, data_parallel: bool = False, overlap: Optional[bool] = None, guard: Optional[dict] = None):
     """train.py:169-176.  Data parallel: the optimisers stepped after the same backward share one gradient
     bucket — D phase (trainer.py:319-322) and G phase (trainer.py:356-359) — so an iteration has two collectives.
     `overlap` (default: the environment's DCV_DP_OVERLAP, else off): per-model chunks whose collectives start from the hook of the chunk's last gradient, on a
-    communication stream, while the rest of the backward runs (optim.GradBucket(overlap=True)); off by default until an N > 1 run has measured it."""
+    communication stream, while the rest of the backward runs (optim.GradBucket(overlap=True)); off by default until an N > 1 run has measured it.
+    `guard`: keyword arguments of optim.GradGuard, e.g. dict(max_norm=10.0) — one guard per phase with the buckets' grouping (D: idis + vdis + gdis, G: ggen + cgen),
+    reachable as `opts[name].guard`; StepRunner then measures after each backward and every step applies the guard's decision.  None (default): no guard."""
     opts = {}
     if overlap is None:
         overlap = os.environ.get("DCV_DP_OVERLAP") is not None
     buckets = {"D": optim.GradBucket(overlap=overlap), "G": optim.GradBucket(overlap=overlap)} if data_parallel else None
+    guards = {"D": optim.GradGuard(**guard), "G": optim.GradGuard(**guard)} if guard is not None else {"D": None, "G": None}
     for name in MODEL_NAMES:
-        o = optim.Adam(models[name].parameters(), lr=cfg.lr[name], betas=(0.5, 0.999), weight_decay=cfg.decay[name])
-        opts[name] = optim.DataParallelAdam(o, buckets["D" if name.endswith("dis") else "G"]) if data_parallel else o
+        phase = "D" if name.endswith("dis") else "G"
+        o = optim.Adam(models[name].parameters(), lr=cfg.lr[name], betas=(0.5, 0.999), weight_decay=cfg.decay[name], guard=guards[phase])
+        opts[name] = optim.DataParallelAdam(o, buckets[phase]) if data_parallel else o
     return opts
 
 
@@ -92,6 +96,9 @@ class StepRunner:
         # B = 70: 37 GB after 5 iterations, 146 GB allocated / 191 GB reserved after 150).  Two iterations keep the GPU's queues full and the memory flat.
         self.max_ahead = max(1, int(os.environ.get("DCV_MAX_ITERATIONS_AHEAD", "2")))
         self._inflight = collections.deque()
+        # optim.GradGuard of each phase (build_optimizers(guard=...)); None — also for optimisers that know no guard — leaves the iteration as it is without one
+        self._guard_dis = getattr(optimizers["idis"], "guard", None)
+        self._guard_gen = getattr(optimizers["ggen"], "guard", None)
 
     def _mark(self, name):
         if self.phase_marks is not None:
@@ -148,8 +155,17 @@ class StepRunner:
             one = self._ones[loss.device] = torch.ones((), dtype=loss.dtype, device=loss.device)
         return one
 
+    def _guard_report(self, out, guard, phase):
+        """grad_norm_<phase> / skipped_<phase> of the guard's last measurement: a snapshot of its state (one dcv_axpby launch), since the state itself moves on with the
+        next measurement while the host runs ahead."""
+        snap = ops._axpby(guard.state.view(1, -1), 1.0, None, 0.0, torch.empty((1, guard.state.numel()), dtype=torch.float32, device=guard.state.device))[0]
+        norm, skipped = snap[guard.FIELDS.index("grad_norm")], snap[guard.FIELDS.index("skipped")]
+        out["grad_norm_" + phase] = norm.cpu().item() if self.sync_losses else norm
+        out["skipped_" + phase] = skipped.cpu().item() if self.sync_losses else skipped
+
     def step(self, xc_real: torch.Tensor, xg_real: torch.Tensor, t_rand: int):
         c, m, o = self.cfg, self.models, self.opt
+        guard_dis, guard_gen = self._guard_dis, self._guard_gen
         ggen, cgen, idis, vdis, gdis = (m[k] for k in MODEL_NAMES)
         self.iteration += 1
         if xc_real.is_cuda:
@@ -175,8 +191,10 @@ class StepRunner:
         loss_gdis = self.loss.compute_dis_loss(y_real[2], y_fake[2])
         loss_dis = ops.sum_scalars(loss_idis, loss_vdis, loss_gdis) if loss_idis.is_cuda else loss_idis + loss_vdis + loss_gdis      # trainer.py:315
         if self.iteration % c.num_gen_update == 0:
-            loss_dis.backward(self._root(loss_dis))
+            loss_dis.backward(guard_dis.root(loss_dis) if guard_dis is not None else self._root(loss_dis))
             self._mark("D: backward (D lanes, then the generators' dead backward)")
+            if guard_dis is not None:
+                guard_dis.measure()
             o["idis"].step(); o["vdis"].step(); o["gdis"].step()
             self._mark("D: Adam")
         else:
@@ -185,6 +203,8 @@ class StepRunner:
             out = {"loss_idis": loss_idis.cpu().item(), "loss_vdis": loss_vdis.cpu().item(), "loss_gdis": loss_gdis.cpu().item()}
         else:
             out = {"loss_idis": loss_idis.detach(), "loss_vdis": loss_vdis.detach(), "loss_gdis": loss_gdis.detach()}
+        if guard_dis is not None:
+            self._guard_report(out, guard_dis, "dis")
         del y_real, y_fake, xg_fake, xc_fake, loss_dis
         # ---- generator phase (trainer.py:338-363) ----
         ggen.train(); cgen.train()
@@ -196,13 +216,17 @@ class StepRunner:
         loss_gen = self.loss.compute_gen_loss(*y_fake)
         self._mark("G: discriminators forward on the fakes")
         if self.iteration % c.num_dis_update == 0:
-            loss_gen.backward(self._root(loss_gen))
+            loss_gen.backward(guard_gen.root(loss_gen) if guard_gen is not None else self._root(loss_gen))
             self._mark("G: backward (D lanes, then the generators)")
+            if guard_gen is not None:
+                guard_gen.measure()
             o["ggen"].step(); o["cgen"].step(); o["ggen"].step()  # ggen twice — trainer.py:357-359
             self._mark("G: Adam")
         else:
             loss_gen.detach_()
         out["loss_gen"] = loss_gen.cpu().item() if self.sync_losses else loss_gen.detach()     # trainer.py:363
+        if guard_gen is not None:
+            self._guard_report(out, guard_gen, "gen")
         if xc_real.is_cuda:
             e = torch.cuda.Event()
             e.record(torch.cuda.current_stream())      # (the lanes and the companion stream have joined the main stream by now)

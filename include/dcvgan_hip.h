@@ -63,7 +63,7 @@ typedef struct dcv_conv_geom {
 } dcv_conv_geom;
 
 const char* dcv_last_error(void);
-/* ABI version.  4 (round 6): dcv_scale_dev, dcv_conv_backward_data_bn(_workspace_bytes), dcv_conv_forward_bn, dcv_conv_backward_weight_bn, dcv_bn_forward_stats_only, dcv_bn_apply exist (no struct changed).  3 (round 5): dcv_conv_backward_weight_acc / dcv_cl_conv_backward_weight_acc, dcv_cl_conv_backward_data_gated, dcv_clf16_*, dcv_normal_fill_many exist (no struct changed).
+/* ABI version.  Still 4: dcv_grad_guard_workspace_bytes, dcv_grad_guard_measure and dcv_adam_step_multi_guarded were added without changing any struct or existing entry.  4 (round 6): dcv_scale_dev, dcv_conv_backward_data_bn(_workspace_bytes), dcv_conv_forward_bn, dcv_conv_backward_weight_bn, dcv_bn_forward_stats_only, dcv_bn_apply exist (no struct changed).  3 (round 5): dcv_conv_backward_weight_acc / dcv_cl_conv_backward_weight_acc, dcv_cl_conv_backward_data_gated, dcv_clf16_*, dcv_normal_fill_many exist (no struct changed).
  * 2 (round 4): dcv_conv_geom has the 13th field `mfma`, dcv_wpack the 4th field `precision`, dcv_abi_struct_sizes exists.
  * A host compares dcv_version() and dcv_abi_struct_sizes() with its own declarations BEFORE the first call that passes a struct
  * (dcvgan_amd/native.py does, and refuses to load on a mismatch): the library cannot see the size of what a pointer points to. */
@@ -296,6 +296,37 @@ int dcv_adam_step(float* p, const float* g, float* m, float* v, int64_t n,
 /* the same update for n_tensors parameter tensors of one optimiser (one shared step count) in ceil(n/24) launches */
 int dcv_adam_step_multi(int n_tensors, float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* numel,
                         double lr, double beta1, double beta2, double eps, double weight_decay, int step, double grad_scale, void* stream);
+
+/* ---- gradient guard: global norm, clipping, non-finite skip, loss scale — decided on the device ------ *
+ * `state` is DCV_GUARD_STATE_FLOATS floats in device memory, owned by the caller, who initialises it once
+ * (loss scale, everything else 0) and afterwards only reads it:                                            */
+#define DCV_GUARD_LOSS_SCALE 0     /* the scale the NEXT backward multiplies the loss by (its root cotangent)          */
+#define DCV_GUARD_GROWTH_TRACKER 1 /* finite measurements since the scale last changed (dynamic scaling)              */
+#define DCV_GUARD_GRAD_NORM 2      /* L2 norm of the TRUE gradients: sqrt(sum g^2) * grad_scale / (scale of the measured backward) */
+#define DCV_GUARD_CLIP_COEF 3      /* min(1, max_norm / (norm + 1e-6)); 1 without clipping or on a non-finite measurement */
+#define DCV_GUARD_FACTOR 4         /* grad_scale * clip_coef / scale: what the guarded Adam multiplies g by (before weight decay) */
+#define DCV_GUARD_SKIPPED 5        /* 1 if the steps on this measurement are skipped, else 0                          */
+#define DCV_GUARD_SKIPPED_TOTAL 6  /* measurements that ended in a skip so far                                        */
+#define DCV_GUARD_NONFINITE 7      /* inf / NaN elements in the last measurement                                      */
+#define DCV_GUARD_STATE_FLOATS 8
+/* bytes of `ws` for a measurement over n_tensors tensors of total_elements elements in all (0 + DCV_EINVAL text for negative arguments) */
+size_t dcv_grad_guard_workspace_bytes(int64_t total_elements, int n_tensors);
+/* One measurement, ceil(n_tensors / 24) + 1 launches, no atomics (bitwise repeatable): per-block partial sums of squares (fp32 within a thread's 16 elements,
+ * double above) and counts of elements whose exponent bits are all ones, then one workgroup that adds them in a fixed order and writes GRAD_NORM .. NONFINITE.
+ * The measurement is NON-FINITE if any element is, or if the sum of squares is not finite (finite elements whose squares overflow fp32 count as non-finite);
+ * it is SKIPPED if it is non-finite and skip_nonfinite is set.  max_norm <= 0: no clipping.  `dynamic` then updates the loss scale as torch.amp.GradScaler does:
+ * non-finite: scale *= backoff_factor, tracker = 0; else tracker += 1 and, when it reaches growth_interval, scale *= growth_factor, tracker = 0.  FACTOR uses
+ * the scale as it was BEFORE this update, i.e. the one the measured backward ran with.  Call it once per backward. */
+int dcv_grad_guard_measure(int n_tensors, const float* const* g, const int64_t* numel, double grad_scale, double max_norm, int skip_nonfinite, int dynamic,
+                           double growth_factor, double backoff_factor, int growth_interval, float* state, void* ws, size_t ws_bytes, void* stream);
+/* dcv_adam_step_multi with the step count and the decision on the device.  `step_block` is DCV_ADAM_STEP_BLOCK_BYTES of device memory, zeroed by the caller before
+ * the first step and shared by tensors with one step count: step_block[0] is that count; the rest is scratch of the call (skip flag, the update's scalars).
+ * A one-thread kernel reads state[DCV_GUARD_SKIPPED]; unless set it increments step_block[0] and forms the bias corrections from it in double, with
+ * state[DCV_GUARD_FACTOR] in grad_scale's place; the update kernels (unchanged arithmetic) read them.  A skipped step touches no p, m, v and no step count.
+ * 1 + ceil(n_tensors / 24) launches. */
+#define DCV_ADAM_STEP_BLOCK_BYTES 64
+int dcv_adam_step_multi_guarded(int n_tensors, float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* numel,
+                                double lr, double beta1, double beta2, double eps, double weight_decay, int32_t* step_block, const float* state, void* stream);
 
 /* ---- bf16 channels-last ("CL16") data path -------------------------------------------------- *
  * BASELINE.json configs[2] ("surreal-depth1, bf16 MFMA") and configs[4] ("fp16 MFMA") name 16-bit variants of the same step
