@@ -1636,89 +1636,64 @@ __global__ __launch_bounds__(256) void cl_pack_patch_kernel(const float* __restr
 }
 
 struct ClTile { int bn, bm; };
-// (oc, positions) tile of a destination with OC channels.  Two more tiles exist and are OFF by default (DCV_CL_TILES: bit 0 = 128 x 256, bit 1 = 96-wide), both
-// measured neutral in round 5 (profiles/r05_ab_cl16.txt, call 7: layer table 32.6 / 32.7 / 32.6 / 32.8 ms, iteration 41.7-42.2 ms for all four settings):
-// 128 x 256 on 8 waves (512 threads) issues 3 LDS-DMA instructions per wave and 8 MFMAs instead of 4 — worth 0-7 % per layer, the 8-wave barrier takes it back;
-// 96 x 256 (channel counts that are multiples of 96 but not of 128: the geometry generator at ngf 96) saves the padded quarter of a 128-wide tile but runs at 168
-// registers = two workgroups per CU.
-static int cl_tile_opts() {
-    static const int v = getenv("DCV_CL_TILES") ? atoi(getenv("DCV_CL_TILES")) : 0;
-    return v;
+
+// The DCV_CL_* switches of tools/ab.sh (A/B only: a variant is off when its variable is set) and the measured-neutral alternatives; read once, not per call, and by
+// the planners only (cl_plan, cl_wgrad_plan and what they call): a plan says everything a switch can reach.
+struct ClToggles {
+    // DCV_CL_TILES: two more (oc, positions) tiles, OFF by default (bit 0 = 128 x 256, bit 1 = 96-wide), both measured neutral in round 5 (profiles/r05_ab_cl16.txt,
+    // call 7: layer table 32.6 / 32.7 / 32.6 / 32.8 ms, iteration 41.7-42.2 ms for all four settings): 128 x 256 on 8 waves (512 threads) issues 3 LDS-DMA instructions
+    // per wave and 8 MFMAs instead of 4 — worth 0-7 % per layer, the 8-wave barrier takes it back; 96 x 256 (channel counts that are multiples of 96 but not of 128:
+    // the geometry generator at ngf 96) saves the padded quarter of a 128-wide tile but runs at 168 registers = two workgroups per CU.  Bit 2: 64 x 256 (below).
+    int tiles;
+    int patch_np;           // DCV_CL_PATCH_NP: 256 = eight waves, one workgroup per CU
+    int64_t wgrad_wgs;      // DCV_CL_WGRAD_WGS: the weight gradient's workgroup target (cl_wgrad_plan)
+    bool no_col2im, no_patch, no_splitk, no_thin3, no_stem3, no_widen3, direct_epilogue;
+    bool wgrad_no_packed, wgrad_no_narrow, wgrad_flat, old_wgrad_reduce, no_postab_cache;
+#ifdef DCV_DEBUG_TIMING      // timing-experiment builds only: the shipped library cannot be told to drop its stores
+    int debug;              // DCV_CL_DEBUG = 1: no epilogue stores
+#endif
+    ClToggles() {
+        auto on = [](const char* n) { return getenv(n) != nullptr; };
+        auto num = [](const char* n, long long dflt) { const char* v = getenv(n); return v ? atoll(v) : dflt; };
+        tiles = (int)num("DCV_CL_TILES", 0); patch_np = (int)num("DCV_CL_PATCH_NP", 0); wgrad_wgs = num("DCV_CL_WGRAD_WGS", 768);
+        no_col2im = on("DCV_CL_NO_COL2IM"); no_patch = on("DCV_CL_NO_PATCH"); no_splitk = on("DCV_CL_NO_SPLITK"); no_thin3 = on("DCV_CL_NO_THIN3");
+        no_stem3 = on("DCV_CL_NO_STEM3"); no_widen3 = on("DCV_CL_NO_WIDEN3"); direct_epilogue = on("DCV_CL_DIRECT_EPILOGUE");
+        wgrad_no_packed = on("DCV_CL_WGRAD_NO_PACKED"); wgrad_no_narrow = on("DCV_CL_WGRAD_NO_NARROW"); wgrad_flat = on("DCV_CL_WGRAD_FLAT");
+        old_wgrad_reduce = on("DCV_CL_OLD_WGRAD_REDUCE"); no_postab_cache = on("DCV_CL_NO_POSTAB_CACHE");
+#ifdef DCV_DEBUG_TIMING
+        debug = (int)num("DCV_CL_DEBUG", 0);
+#endif
+    }
+};
+static const ClToggles& cl_toggles() {
+    static const ClToggles t;
+    return t;
 }
+
+// (oc, positions) tile of a destination with OC channels
 static ClTile cl_pick_tile(int OC) {
-    if ((cl_tile_opts() & 2) && OC > 64 && OC % 96 == 0 && OC % 128 != 0) return {96, 256};
-    if (OC > 64) return (cl_tile_opts() & 1) ? ClTile{128, 256} : ClTile{128, 128};
+    const int opts = cl_toggles().tiles;
+    if ((opts & 2) && OC > 64 && OC % 96 == 0 && OC % 128 != 0) return {96, 256};
+    if (OC > 64) return (opts & 1) ? ClTile{128, 256} : ClTile{128, 128};
     // (64 x 128 since the end of round 5: the layer table is the same with either — 29.80 / 29.85 ms — the iteration with its three lanes 0.2 ms shorter, 3 of 3 pairs;
     //  bit 2 of DCV_CL_TILES brings 64 x 256 back)
-    if (OC > 32) return (cl_tile_opts() & 4) ? ClTile{64, 256} : ClTile{64, 128};
+    if (OC > 32) return (opts & 4) ? ClTile{64, 256} : ClTile{64, 128};
     return {32, 256};
-}
-
-static size_t cl_class_pack_bytes(const ClClass& c, int C, int OC) {
-    const ClTile tc = cl_pick_tile(OC);
-    const int OCp = (OC + tc.bn - 1) / tc.bn * tc.bn;
-    const int T = c.t[0].n * c.t[1].n * c.t[2].n;
-    if (T == 0) return 0;
-    const int nsteps = cl_thin(C) ? (T + 3) / 4 : T * (cl_cp(C) / 32);
-    return align_up((size_t)nsteps * OCp * 64, 256);
-}
-
-// src (gathered, RC channels) -> dst (OC channels); weight element (oc, rc, tap) at oc * ws_o + rc * ws_r + kidx
-struct ClPlan {
-    std::vector<ClClass> cls;
-    int RC, OC;
-    int64_t ws_o, ws_r;
-    int KH, KW;
-};
-
-static int cl_make_plan(int which, const dcv_conv_geom* g, const dcv_dims5* xd, const dcv_dims5* yd, ClPlan* pl) {
-    const int k[3] = {g->kd, g->kh, g->kw}, s[3] = {g->sd, g->sh, g->sw}, p[3] = {g->pd, g->ph, g->pw};
-    const int xi[3] = {xd->d, xd->h, xd->w}, yo[3] = {yd->d, yd->h, yd->w};
-    const int T = k[0] * k[1] * k[2];
-    if (k[0] > 4 || k[1] > 4 || k[2] > 4) return fail(DCV_EUNSUPPORTED, "cl conv: filters up to 4 taps per dim");
-    for (int d = 0; d < 3; ++d) {
-        const int want = g->transposed ? (xi[d] - 1) * s[d] - 2 * p[d] + k[d] : (xi[d] + 2 * p[d] - k[d]) / s[d] + 1;
-        if (want != yo[d]) return fail(DCV_EINVAL, "cl conv: output extent %d along dim %d, geometry gives %d", yo[d], d, want);
-    }
-    if (xd->c != g->cin || yd->c != g->cout || xd->n != yd->n) return fail(DCV_EINVAL, "cl conv: channel / batch mismatch");
-    const bool direct = (which == 0 && !g->transposed) || (which == 1 && g->transposed);
-    const dcv_dims5& src = (which == 0) ? *xd : *yd;
-    const dcv_dims5& dst = (which == 0) ? *yd : *xd;
-    pl->RC = src.c; pl->OC = dst.c; pl->KH = k[1]; pl->KW = k[2];
-    if (direct) {
-        pl->cls = cl_direct_classes(k, s, p, (which == 0) ? yo : xi, (which == 0) ? xi : yo);
-        pl->ws_o = (int64_t)pl->RC * T; pl->ws_r = T;
-    } else {
-        pl->cls = cl_scatter_classes(k, s, p, (which == 0) ? yo : xi, (which == 0) ? xi : yo);
-        pl->ws_o = T; pl->ws_r = (int64_t)pl->OC * T;
-    }
-    return DCV_OK;
-}
-
-// thin destination fed by a wide source: the GEMM + col2im form (above)
-static bool cl_thin_out(const ClPlan& pl, const dcv_conv_geom* g) {
-    const int T = g->kd * g->kh * g->kw;
-    static const bool off = getenv("DCV_CL_NO_COL2IM") != nullptr;
-    // (up to 64 GEMM columns: beyond that — the 4x4x4 data gradient into the 3-channel video, 192 columns — the gather form measured faster, 0.46 vs 1.12 ms)
-    return pl.OC <= 8 && !cl_thin(pl.RC) && T * pl.OC <= 64 && !off;
 }
 static inline int cl_pitch(int c) { return c <= 8 ? 8 : (c + 31) / 32 * 32; }
 
 // cl_patch_convt_kernel's plan.  Decided on SHAPES only (the packed weights carry its layout behind the tiled gather's, so a call the run-time conditions exclude —
 // accumulate, gate, a misaligned view — still has the other form's tiles)
 struct ClPatchPlan { bool ok; int NP, NI, PRI, RI, prows, bands, npatch, wlog, plog, C32, OCp, octiles; size_t pack_bytes; };
-static ClPatchPlan cl_patch_plan(int which, const dcv_conv_geom* g, const ClPlan& pl, const dcv_dims5& src, const dcv_dims5& dst) {
+static ClPatchPlan cl_patch_plan(bool direct, const dcv_conv_geom* g, int RC, int OC, const dcv_dims5& src, const dcv_dims5& dst) {
     ClPatchPlan r;
     memset(&r, 0, sizeof(r));
-    static const bool off = getenv("DCV_CL_NO_PATCH") != nullptr;      // A/B only
-    const bool direct = (which == 0 && !g->transposed) || (which == 1 && g->transposed);
-    if (off || direct || g->kd != 1 || g->kh != 4 || g->kw != 4 || g->sd != 1 || g->sh != 2 || g->sw != 2 || g->pd != 0 || g->ph != 1 || g->pw != 1) return r;
+    if (cl_toggles().no_patch || direct || g->kd != 1 || g->kh != 4 || g->kw != 4 || g->sd != 1 || g->sh != 2 || g->sw != 2 || g->pd != 0 || g->ph != 1 || g->pw != 1) return r;
     if (src.d != 1 || dst.d != 1 || dst.h != 2 * src.h || dst.w != 2 * src.w) return r;
     const int W = src.w, H = src.h;
     if ((W != 4 && W != 8 && W != 16 && W != 32) || H < 1 || (H & (H - 1))) return r;
-    if (pl.RC < 32 || pl.RC % 32 || pl.OC < 64 || pl.OC % 8) return r;      // (destination channels past the last whole 64: zero weights, never stored)
-    static const int np_env = getenv("DCV_CL_PATCH_NP") ? atoi(getenv("DCV_CL_PATCH_NP")) : 0;      // A/B only: 256 = eight waves, one workgroup per CU
-    const int NP = np_env == 256 ? 256 : 128;
+    if (RC < 32 || RC % 32 || OC < 64 || OC % 8) return r;      // (destination channels past the last whole 64: zero weights, never stored)
+    const int NP = cl_toggles().patch_np == 256 ? 256 : 128;
     r.NP = NP;
     if (H * W >= NP) { r.NI = 1; r.PRI = NP / W; if (r.PRI < 1 || H % r.PRI) return r; }
     else { r.NI = NP / (H * W); r.PRI = H; }
@@ -1728,15 +1703,10 @@ static ClPatchPlan cl_patch_plan(int which, const dcv_conv_geom* g, const ClPlan
     r.npatch = (src.n + r.NI - 1) / r.NI * r.bands;
     for (r.wlog = 0; (1 << r.wlog) < W; ++r.wlog) {}
     for (r.plog = 0; (1 << r.plog) < r.PRI * W; ++r.plog) {}
-    r.C32 = pl.RC / 32; r.OCp = (pl.OC + 63) / 64 * 64; r.octiles = r.OCp / 64;
+    r.C32 = RC / 32; r.OCp = (OC + 63) / 64 * 64; r.octiles = r.OCp / 64;
     r.pack_bytes = (size_t)r.octiles * r.C32 * 4 * CLP_B;
     r.ok = true;
     return r;
-}
-static size_t cl_generic_pack_bytes(const ClPlan& pl) {
-    size_t tot = 0;
-    for (const ClClass& c : pl.cls) tot += cl_class_pack_bytes(c, pl.RC, pl.OC);
-    return align_up(tot, 256);
 }
 
 static int cl_check_tensor(const dcv_dims5& d, const char* tag) {
@@ -1749,7 +1719,6 @@ static int64_t cl_extent_bytes(const dcv_dims5& d, int cpad) {
     return 2 * ((int64_t)(d.n - 1) * d.sn + (int64_t)(d.d - 1) * d.sd + (int64_t)(d.h - 1) * d.sh + (int64_t)(d.w - 1) * d.sw + cpad);
 }
 
-static void cl_launch_tile(const ClTile tc, const ClGatherPack& pk, bool thin, dim3 grid, hipStream_t s);
 // (Round 5, measured and not instantiated: NS = 3 and 4 — two / three K steps in flight behind counted vmcnt waits, at 3 or 2 workgroups per CU instead of 4 —
 // ran the surreal-depth1 layer table in 39.5 / 41.3 ms against 37.9 and the iteration in 49.3 / 51.4 ms against 47.2 (profiles/r05_ab_cl16.txt): what bounds the
 // loop is the issue cost of the LDS-DMA instructions, 4-5 per wave and K step against 8 MFMAs, not the distance of the prefetch; fewer waves per SIMD lose more.)
@@ -1760,8 +1729,7 @@ static void cl_launch_tile(const ClTile tc, const ClGatherPack& pk, bool thin, d
 struct ClSplitK { int KS, ks_per; size_t slab_bytes; int slab_m; };
 static ClSplitK cl_splitk_plan(int ncls, bool thin, int64_t M, int per_sample, int OCp, int nsteps, const ClTile tc, int ocs) {
     ClSplitK r = {0, 0, 0, 0};
-    static const bool off = getenv("DCV_CL_NO_SPLITK") != nullptr;      // A/B only
-    if (off || ncls != 1 || thin || ocs % 8 || per_sample > 4 || nsteps < 64) return r;
+    if (cl_toggles().no_splitk || ncls != 1 || thin || ocs % 8 || per_sample > 4 || nsteps < 64) return r;
     const int KS = std::min(8, nsteps / 8);
     const int64_t tiles_m = (M + tc.bm - 1) / tc.bm;
     r.ks_per = (nsteps + KS - 1) / KS;
@@ -1784,6 +1752,330 @@ static void cl_launch_tile(const ClTile tc, const ClGatherPack& pk, bool thin, d
     else cl_launch_gather<1, 2, 1, 4>(pk, thin, grid, s);
 }
 
+// What a decision may depend on besides the geometry and the two tensors' shapes and strides.  `sizing`: a size query or the pack writer — no tensors or buffers yet,
+// so their strides, extents and sizes are not checked, and the caller asks for the plans the pointers it cannot see could lead to (cl_plan_sizes).
+struct ClCall {
+    int act, accumulate;
+    bool gate, stat;                         // gated epilogue; BatchNorm sums asked for
+    size_t stat_bytes, ws_bytes;
+    bool src16, dst16, packed16, ws16;       // 16-byte alignment of the four pointers
+    bool sizing;
+};
+// The kernel(s) a forward / data-gradient call runs, in the order of preference
+enum class ClForm { Thin3x3, Col2im, Stem3d, Widen3x3, Patch, Gather };
+// one position class with taps: T taps in nsteps 32-deep K steps over M positions (0: packed but not launched), its weight tiles pack_off bytes into the packed buffer
+struct ClPlanClass { ClClass c; int T, nsteps; int64_t M; size_t pack_off; };
+// src (gathered, RC channels) -> dst (OC channels); weight element (oc, rc, tap) at oc * ws_o + rc * ws_r + kidx
+struct ClPlan {
+    int RC, OC, KH, KW; int64_t ws_o, ws_r;
+    bool direct, thin, thin_out;      // direct gather (else scatter form); thin source; thin destination fed by a wide source (one GEMM over the source + col2im, or cl_thin3x3_kernel)
+    int Cp, ocs;                      // padded gathered channels; channels stored per destination pixel
+    ClForm form; ClTile tile;
+    int OCp;                          // the GEMM's rows, padded to the tile: destination channels (thin destination: taps x channels)
+    std::vector<ClPlanClass> cls;     // pack order = launch order (thin destination: the one GEMM)
+    int nlaunch;
+    int64_t maxtm;                    // position tiles of the largest launched class
+    ClPatchPlan patch;
+    size_t pack_generic, pack_bytes;  // packed weights: the classes' tiles, behind them the patch-staged form's where the shapes allow it (patch.ok), + 256
+    ClSplitK sk;
+    size_t ws_need, stat_need;        // workspace; BatchNorm sums (0: this call leaves none)
+    int nparts, pitch, coalesce, dbg;
+    int zp;                           // thin destination: pixel pitch of Z
+    int64_t xb, yb;                   // the two tensors' extents
+    char note[160];                   // dcv_debug_last_kernel's text
+};
+
+// the geometry against the two shapes (x: the convolution's input, y: its output)
+static int cl_check_geom(const dcv_conv_geom* g, const dcv_dims5* xd, const dcv_dims5* yd) {
+    const int k[3] = {g->kd, g->kh, g->kw}, s[3] = {g->sd, g->sh, g->sw}, p[3] = {g->pd, g->ph, g->pw};
+    const int xi[3] = {xd->d, xd->h, xd->w}, yo[3] = {yd->d, yd->h, yd->w};
+    if (k[0] > 4 || k[1] > 4 || k[2] > 4) return fail(DCV_EUNSUPPORTED, "cl conv: filters up to 4 taps per dim");
+    for (int d = 0; d < 3; ++d) {
+        const int want = g->transposed ? (xi[d] - 1) * s[d] - 2 * p[d] + k[d] : (xi[d] + 2 * p[d] - k[d]) / s[d] + 1;
+        if (want != yo[d]) return fail(DCV_EINVAL, "cl conv: output extent %d along dim %d, geometry gives %d", yo[d], d, want);
+    }
+    if (xd->c != g->cin || yd->c != g->cout || xd->n != yd->n) return fail(DCV_EINVAL, "cl conv: channel / batch mismatch");
+    return DCV_OK;
+}
+
+// The one place a forward / data-gradient call is decided: its form, tile, classes, pack layout, buffer needs, and every refusal.
+static int cl_plan(int which, const dcv_conv_geom* g, const dcv_dims5* xd, const dcv_dims5* yd, const ClCall& o, ClPlan* P) {
+    const ClToggles& tg = cl_toggles();
+    int rc = cl_check_geom(g, xd, yd);
+    if (rc != DCV_OK) return rc;
+    const int k[3] = {g->kd, g->kh, g->kw}, s[3] = {g->sd, g->sh, g->sw}, p[3] = {g->pd, g->ph, g->pw};
+    const int xi[3] = {xd->d, xd->h, xd->w}, yo[3] = {yd->d, yd->h, yd->w};
+    const int T = k[0] * k[1] * k[2];
+    const dcv_dims5& src = (which == 0) ? *xd : *yd;
+    const dcv_dims5& dst = (which == 0) ? *yd : *xd;
+    if (!o.sizing && ((rc = cl_check_tensor(src, "cl conv source")) != DCV_OK || (rc = cl_check_tensor(dst, "cl conv destination")) != DCV_OK)) return rc;
+    const int RC = src.c, OC = dst.c;
+    const bool direct = (which == 0 && !g->transposed) || (which == 1 && g->transposed), thin = cl_thin(RC);
+    const int Cp = cl_cp(RC);
+    P->RC = RC; P->OC = OC; P->KH = k[1]; P->KW = k[2]; P->direct = direct; P->thin = thin; P->Cp = Cp;
+    P->ws_o = direct ? (int64_t)RC * T : T; P->ws_r = direct ? T : (int64_t)OC * T;
+    P->cls.clear(); P->nlaunch = 0; P->maxtm = 0; P->ws_need = P->stat_need = 0; P->nparts = P->pitch = P->coalesce = P->zp = 0; P->sk = {0, 0, 0, 0};
+    memset(&P->patch, 0, sizeof(P->patch));
+    P->note[0] = 0;
+#ifdef DCV_DEBUG_TIMING
+    P->dbg = tg.debug;
+#else
+    P->dbg = 0;
+#endif
+    // (up to 64 GEMM columns: beyond that — the 4x4x4 data gradient into the 3-channel video, 192 columns — the gather form measured faster, 0.46 vs 1.12 ms)
+    P->thin_out = OC <= 8 && !thin && T * OC <= 64 && !tg.no_col2im;
+    if (o.gate && (P->thin_out || thin)) return fail(DCV_EUNSUPPORTED, "cl conv: no gated epilogue in the thin forms");
+    const bool a16 = o.src16 && o.dst16;
+    if (P->thin_out) {
+        // Z = X (1x1) Wg, every source pixel once, then the taps of every destination pixel gathered from Z — or both fused
+        const int OCg = T * OC;
+        const int64_t Msrc = (int64_t)src.n * src.d * src.h * src.w;
+        P->tile = cl_pick_tile(OCg); P->OCp = (OCg + P->tile.bn - 1) / P->tile.bn * P->tile.bn; P->zp = cl_pitch(OCg); P->ocs = pad8(OCg);
+        P->cls.push_back(ClPlanClass{ClClass{}, 1, Cp / 32, Msrc, 0});
+        P->pack_generic = align_up((size_t)(Cp / 32) * P->OCp * 64, 256); P->pack_bytes = P->pack_generic + 256;
+        if (Msrc >= (1ll << 31)) return fail(DCV_EUNSUPPORTED, "cl conv: too many source pixels");
+        if ((int64_t)dst.n * dst.d * dst.h * dst.w >= (1ll << 31)) return fail(DCV_EUNSUPPORTED, "cl conv: too many destination pixels");
+        P->ws_need = (size_t)Msrc * P->zp * 2;
+        P->xb = cl_extent_bytes(src, Cp); P->yb = (int64_t)P->ws_need;
+        if (!o.sizing) {
+            if (o.ws_bytes < P->ws_need) return fail(DCV_EWORKSPACE, "cl conv: workspace too small for the thin-destination form (%zu needed, %zu given)", P->ws_need, o.ws_bytes);
+            if (src.w > 1 && src.sw < Cp) return fail(DCV_EINVAL, "cl conv: source pixel pitch %lld < padded channels %d", (long long)src.sw, Cp);
+            if (dst.w > 1 && dst.sw < 8) return fail(DCV_EINVAL, "cl conv: thin destination needs a pixel pitch of 8");
+            if (P->xb >= (1ll << 31) || P->ws_need >= (1ull << 31)) return fail(DCV_EUNSUPPORTED, "cl conv: tensors beyond 2 GB");
+        }
+        // fused form (cl_thin3x3_kernel): 2-D 3x3 / stride 1 / pad 1 scatter-form, 64-wide rows, rows in bands of 16, 32 / 64 / 128 source channels, <= 3 destination channels
+        if (!tg.no_thin3 && !o.accumulate && !direct && k[0] == 1 && k[1] == 3 && k[2] == 3 && s[0] == 1 && s[1] == 1 && s[2] == 1 && p[0] == 0 && p[1] == 1 && p[2] == 1 &&
+            src.d == 1 && dst.d == 1 && src.w == 64 && src.h % 16 == 0 && dst.w == 64 && dst.h == src.h && OC <= 3 && (RC == 32 || RC == 64 || RC == 128) &&
+            a16 && dst.sw >= 8 && src.sw >= RC && cl_extent_bytes(src, RC) < (1ll << 31) && cl_extent_bytes(dst, 8) < (1ll << 31)) {
+            P->form = ClForm::Thin3x3; P->xb = cl_extent_bytes(src, RC); P->yb = cl_extent_bytes(dst, 8);
+            snprintf(P->note, sizeof(P->note), "cl_thin3x3_kernel<%d> (fused GEMM + tap gather, thin destination, " CL_HALF_NAME " channels-last)", RC / 8);
+            return DCV_OK;
+        }
+        P->form = ClForm::Col2im;
+        P->coalesce = (o.ws16 && !tg.direct_epilogue) ? 1 : 0;      // Z owns its pixels (pitch zp >= pad8): whole 8-column groups, zeros past OCg
+        snprintf(P->note, sizeof(P->note), "cl_gather_kernel<%d x %d tile> as a 1x1 GEMM over the source + cl_col2im_kernel (thin destination, " CL_HALF_NAME " channels-last)", P->tile.bn, P->tile.bm);
+        return DCV_OK;
+    }
+    const ClTile tc = P->tile = cl_pick_tile(OC);
+    const int OCp = P->OCp = (OC + tc.bn - 1) / tc.bn * tc.bn;
+    size_t off = 0;
+    for (const ClClass& c : direct ? cl_direct_classes(k, s, p, (which == 0) ? yo : xi, (which == 0) ? xi : yo) : cl_scatter_classes(k, s, p, (which == 0) ? yo : xi, (which == 0) ? xi : yo)) {
+        const int Tc = c.t[0].n * c.t[1].n * c.t[2].n;
+        const bool empty = c.o_ext[0] <= 0 || c.o_ext[1] <= 0 || c.o_ext[2] <= 0;
+        if (Tc == 0) {      // nothing to add: fine where the destination keeps its contents
+            if (!empty && !o.accumulate && !o.sizing) return fail(DCV_EUNSUPPORTED, "cl conv: a position class without taps");
+            continue;
+        }
+        if (Tc > 64) return fail(DCV_EUNSUPPORTED, "cl conv: more than 64 taps");
+        const int64_t M = empty ? 0 : (int64_t)dst.n * c.o_ext[0] * c.o_ext[1] * c.o_ext[2];
+        if (M >= (1ll << 31)) return fail(DCV_EUNSUPPORTED, "cl conv: too many positions");
+        const int nsteps = thin ? (Tc + 3) / 4 : Tc * (Cp / 32);
+        P->cls.push_back(ClPlanClass{c, Tc, nsteps, M, off});
+        off += align_up((size_t)nsteps * OCp * 64, 256);
+        if (M) { ++P->nlaunch; P->maxtm = std::max<int64_t>(P->maxtm, (M + tc.bm - 1) / tc.bm); }
+    }
+    if (P->cls.size() > 4) return fail(DCV_EUNSUPPORTED, "cl conv: more than 4 position classes");
+    P->patch = cl_patch_plan(direct, g, RC, OC, src, dst);
+    P->pack_generic = off; P->pack_bytes = off + (P->patch.ok ? P->patch.pack_bytes : 0) + 256;
+    // stores are 4-channel groups; a destination that owns its whole pixel (not a channel slice of a wider buffer) gets all pad8(OC) channels written —
+    // zeros past OC — so nobody has to clear a fresh tensor's padding channels first
+    const int ocs = P->ocs = (dst.w > 1 ? dst.sw : pad8(OC)) >= pad8(OC) && OC % 8 ? pad8(OC) : (OC + 3) / 4 * 4;
+    // the gathered tensor's channel slice must be readable in whole K granules: pixel pitch >= padded channel count
+    if (!o.sizing && src.w > 1 && src.sw < (thin ? 8 : Cp)) return fail(DCV_EINVAL, "cl conv: source pixel pitch %lld < padded channels %d", (long long)src.sw, thin ? 8 : Cp);
+    if (!o.sizing && dst.w > 1 && dst.sw < ocs) return fail(DCV_EINVAL, "cl conv: destination pixel pitch %lld < %d stored channels", (long long)dst.sw, ocs);
+    const int64_t xb = P->xb = cl_extent_bytes(src, thin ? 8 : Cp), yb = P->yb = cl_extent_bytes(dst, ocs);
+    const bool fits = xb < (1ll << 31) && yb < (1ll << 31);
+    const bool hw4s2 = k[1] == 4 && k[2] == 4 && s[0] == 1 && s[1] == 2 && s[2] == 2 && p[0] == 0 && p[1] == 1 && p[2] == 1;
+    const bool k3s1 = k[0] == 1 && k[1] == 3 && k[2] == 3 && s[0] == 1 && s[1] == 1 && s[2] == 1 && p[0] == 0 && p[1] == 1 && p[2] == 1;
+    // fused 3-D stem (cl_stem3d_kernel): Conv3d(<= 8 -> 32, 4x4x4, stride (1, 2, 2), padding (0, 1, 1)) forward on 64 x 64 frames
+    if (thin && !o.accumulate && !o.stat && !o.gate && !tg.no_stem3 && which == 0 && !g->transposed && k[0] == 4 && hw4s2 &&
+        src.h == 64 && src.w == 64 && dst.h == 32 && dst.w == 32 && dst.d == src.d - 3 && OC == 32 && ocs == 32 && a16 && src.sw >= 8 && dst.sw >= 32 && fits) {
+        P->form = ClForm::Stem3d;
+        snprintf(P->note, sizeof(P->note), "cl_stem3d_kernel (fused, thin source, " CL_HALF_NAME " channels-last)");
+        return DCV_OK;
+    }
+    // fused form (cl_widen3x3_kernel): 2-D 3x3 / stride 1 / pad 1 direct form out of a thin source on 64-wide rows, 64 or 128 destination channels
+    if (thin && !o.accumulate && !o.stat && !tg.no_widen3 && direct && k3s1 && src.d == 1 && dst.d == 1 && src.w == 64 && src.h % 16 == 0 && dst.w == 64 && dst.h == src.h &&
+        (OC == 64 || OC == 128) && OC == ocs && a16 && src.sw >= 8 && dst.sw >= OC && fits) {
+        P->form = ClForm::Widen3x3;
+        snprintf(P->note, sizeof(P->note), "cl_widen3x3_kernel<%d> (fused, thin source, " CL_HALF_NAME " channels-last)", OC / 32);
+        return DCV_OK;
+    }
+    const bool stats = o.stat && which == 0 && o.act == DCV_ACT_NONE && !o.accumulate;
+    // patch-staged scatter form (cl_patch_convt_kernel): all four stride-parity classes of a 4x4 / stride-2 layer from one staged source patch
+    if (!thin && !o.accumulate && !o.gate && P->patch.ok && ocs == OC && a16 && o.packed16 && src.sw >= Cp && dst.sw >= OC && fits && P->patch.pack_bytes < (1ull << 31)) {
+        P->form = ClForm::Patch;
+        const size_t need = (size_t)P->patch.npatch * P->patch.OCp * 2 * sizeof(float);
+        if (stats && need <= o.stat_bytes) { P->stat_need = need; P->nparts = P->patch.npatch; P->pitch = P->patch.OCp; }
+        snprintf(P->note, sizeof(P->note), "cl_patch_convt_kernel<%d waves> (4 classes from one staged patch, %d x %d source, " CL_HALF_NAME " channels-last)", P->patch.NP / 32, src.h, src.w);
+        return DCV_OK;
+    }
+    P->form = ClForm::Gather;
+    if (!o.sizing && !fits) return fail(DCV_EUNSUPPORTED, "cl conv: tensors beyond 2 GB need per-sample descriptors");
+    // 16-byte row-order stores need whole 8-channel groups at 16-byte-aligned pixel bases (pitches are multiples of 8 elements: cl_check_tensor)
+    P->coalesce = (ocs % 8 == 0 && o.dst16 && !tg.direct_epilogue) ? 1 : 0;
+    if (o.gate && !P->coalesce) return fail(DCV_EUNSUPPORTED, "cl conv: the gated epilogue needs the row-order store form");
+    if (P->nlaunch == 0) return DCV_OK;
+    const size_t need = (size_t)P->nlaunch * P->maxtm * OCp * 2 * sizeof(float);
+    if (stats && need <= o.stat_bytes) { P->stat_need = need; P->nparts = (int)(P->nlaunch * P->maxtm); P->pitch = OCp; }
+    const ClPlanClass* first = nullptr;
+    for (const ClPlanClass& c : P->cls) if (c.M && !first) first = &c;
+    // split-K needs its slabs 16-byte aligned (a fact a caller cannot always control: unsplit then); a short workspace is the caller's error
+    if (!o.stat && !o.accumulate && !o.gate && o.ws16) P->sk = cl_splitk_plan(P->nlaunch, thin, first->M, (int)(first->M / dst.n), OCp, first->nsteps, tc, ocs);
+    if (P->sk.KS) {
+        P->ws_need = P->sk.slab_bytes;
+        if (!o.sizing && o.ws_bytes < P->ws_need) return fail(DCV_EWORKSPACE, "cl conv: workspace too small for the split-K form (%zu needed, %zu given)", P->ws_need, o.ws_bytes);
+        snprintf(P->note, sizeof(P->note), "cl_gather_kernel<%d x %d tile> (1 class, split-K x %d, " CL_HALF_NAME " channels-last)", tc.bn, tc.bm, P->sk.KS);
+    } else {
+        snprintf(P->note, sizeof(P->note), "cl_gather_kernel<%d x %d tile%s> (%d class%s, " CL_HALF_NAME " channels-last)", tc.bn, tc.bm, thin ? ", thin" : "", P->nlaunch, P->nlaunch == 1 ? "" : "es");
+    }
+    return DCV_OK;
+}
+
+// A query sees no pointers, no accumulate flag and no gate: the largest needs among the plans its shapes lead to — every pointer 16-byte aligned (the fused,
+// patch-staged and split-K forms) and none of them (the tiled gather, the GEMM + col2im pair).  The pack layout is the same in all of them.
+static int cl_plan_sizes(int which, const dcv_conv_geom* g, const dcv_dims5* xd, const dcv_dims5* yd, bool stats, ClPlan* P) {
+    if (!g || !xd || !yd || (which != 0 && which != 1)) return fail(DCV_EINVAL, "cl conv: null pointer or unknown pass");
+    ClCall o;
+    memset(&o, 0, sizeof(o));
+    o.act = DCV_ACT_NONE; o.stat = stats; o.stat_bytes = o.ws_bytes = ~(size_t)0; o.sizing = true;
+    ClPlan Q;
+    int rc = cl_plan(which, g, xd, yd, o, &Q);
+    if (rc != DCV_OK) return rc;
+    o.src16 = o.dst16 = o.packed16 = o.ws16 = true;
+    if ((rc = cl_plan(which, g, xd, yd, o, P)) != DCV_OK) return rc;
+    P->ws_need = std::max(P->ws_need, Q.ws_need); P->stat_need = std::max(P->stat_need, Q.stat_need);
+    return DCV_OK;
+}
+
+// Launches what the plan says, in its order; nothing here can fail but a HIP call.
+static int cl_launch(const ClPlan& P, const void* src_p, const dcv_dims5& src, const void* packed, void* dst_p, const dcv_dims5& dst, const dcv_conv_geom* g,
+                     int act, float slope, int accumulate, void* ws, float* stat, const void* gate, float gate_slope, hipStream_t st) {
+    const cl_h *x = static_cast<const cl_h*>(src_p), *wp = static_cast<const cl_h*>(packed);
+    cl_h* y = static_cast<cl_h*>(dst_p);
+    if (P.form == ClForm::Thin3x3) {
+        ClThin3Args t;
+        memset(&t, 0, sizeof(t));
+        t.x = x; t.y = y; t.wp = wp;
+        t.N = src.n; t.H = src.h; t.OC = P.OC; t.act = act; t.bands = src.h / 16; t.slope = slope;
+        t.x_sn = src.sn; t.y_sn = dst.sn; t.x_sh = (int32_t)src.sh; t.x_sw = (int32_t)src.sw; t.y_sh = (int32_t)dst.sh; t.y_sw = (int32_t)dst.sw;
+        t.x_bytes = (uint32_t)P.xb; t.y_bytes = (uint32_t)P.yb;
+        const unsigned nwg = (unsigned)((src.n + 7) / 8 * 8 * t.bands);
+        if (P.RC == 128) hipLaunchKernelGGL((cl_thin3x3_kernel<16>), dim3(nwg), dim3(256), 0, st, t);
+        else if (P.RC == 64) hipLaunchKernelGGL((cl_thin3x3_kernel<8>), dim3(nwg), dim3(256), 0, st, t);
+        else hipLaunchKernelGGL((cl_thin3x3_kernel<4>), dim3(nwg), dim3(256), 0, st, t);
+    } else if (P.form == ClForm::Col2im) {
+        // (1) Z = X (1x1) Wg : every source pixel once
+        const ClPlanClass& c0 = P.cls[0];
+        ClGatherPack pk;
+        memset(&pk, 0, sizeof(pk));
+        ClGatherArgs& a = pk.c[0];
+        a.x = x; a.y = static_cast<cl_h*>(ws); a.wp = wp;
+        a.M = (int)c0.M; a.OCp = P.OCp; a.T = c0.T; a.cblk = P.Cp / 32; a.nsteps = c0.nsteps; a.y_c = P.ocs; a.x_cmax = 2 * pad8(P.RC);
+        a.div_sp = make_fastdiv((uint32_t)(src.d * src.h * src.w)); a.div_hw = make_fastdiv((uint32_t)(src.h * src.w)); a.div_w = make_fastdiv((uint32_t)src.w);
+        ClDim one;
+        memset(&one, 0, sizeof(one));
+        one.n = 1; one.mul = 1; one.base = 0;
+        a.td = one; a.td.size = src.d; a.th = one; a.th.size = src.h; a.tw = one; a.tw.size = src.w;
+        a.x_sn = src.sn; a.x_sd = (int32_t)src.sd; a.x_sh = (int32_t)src.sh; a.x_sw = (int32_t)src.sw;
+        a.y_sn = (int64_t)src.d * src.h * src.w * P.zp; a.y_sd = src.h * src.w * P.zp; a.y_sh = src.w * P.zp; a.y_sw = P.zp; a.y_off = 0;
+        a.act = DCV_ACT_NONE; a.x_bytes = (uint32_t)P.xb; a.y_bytes = (uint32_t)P.yb; a.coalesce = P.coalesce;
+        for (int i = 1; i < 4; ++i) pk.c[i] = pk.c[0];
+        pk.ncls = 1; pk.tiles_oc = P.OCp / P.tile.bn; pk.tiles_m = (int)((c0.M + P.tile.bm - 1) / P.tile.bm);
+        cl_launch_tile(P.tile, pk, false, dim3((unsigned)((pk.tiles_m + 7) / 8 * 8 * pk.tiles_oc)), st);
+        DCV_LAUNCH_CHECK();
+        // (2) gather the taps of every destination pixel
+        ClCol2imArgs c;
+        memset(&c, 0, sizeof(c));
+        c.z = static_cast<const cl_h*>(ws); c.y = y;
+        c.OC = P.OC; c.zpitch = P.zp; c.T = g->kd * g->kh * g->kw; c.scatter = P.direct ? 0 : 1;
+        c.k[0] = g->kd; c.k[1] = g->kh; c.k[2] = g->kw; c.s[0] = g->sd; c.s[1] = g->sh; c.s[2] = g->sw; c.p[0] = g->pd; c.p[1] = g->ph; c.p[2] = g->pw;
+        c.sext[0] = src.d; c.sext[1] = src.h; c.sext[2] = src.w; c.dext[0] = dst.d; c.dext[1] = dst.h; c.dext[2] = dst.w;
+        c.act = act; c.slope = slope; c.accumulate = accumulate;
+        c.div_sp = make_fastdiv((uint32_t)(dst.d * dst.h * dst.w)); c.div_hw = make_fastdiv((uint32_t)(dst.h * dst.w)); c.div_w = make_fastdiv((uint32_t)dst.w);
+        c.y_sn = dst.sn; c.y_sd = (int32_t)dst.sd; c.y_sh = (int32_t)dst.sh; c.y_sw = (int32_t)dst.sw;
+        c.s_sp = src.d * src.h * src.w; c.s_hw = src.h * src.w; c.s_w = src.w;
+        c.total = (int64_t)dst.n * dst.d * dst.h * dst.w;
+        hipLaunchKernelGGL(cl_col2im_kernel, dim3((unsigned)((c.total + 255) / 256)), dim3(256), 0, st, c);
+    } else if (P.form == ClForm::Stem3d) {
+        ClStem3Args t;
+        memset(&t, 0, sizeof(t));
+        t.x = x; t.y = y; t.wp = wp;
+        t.N = src.n; t.OD = dst.d; t.act = act; t.slope = slope;
+        t.x_sn = src.sn; t.y_sn = dst.sn; t.x_sd = (int32_t)src.sd; t.x_sh = (int32_t)src.sh; t.x_sw = (int32_t)src.sw;
+        t.y_sd = (int32_t)dst.sd; t.y_sh = (int32_t)dst.sh; t.y_sw = (int32_t)dst.sw;
+        t.x_bytes = (uint32_t)P.xb; t.y_bytes = (uint32_t)P.yb;
+        const unsigned nwg = (unsigned)(src.n * 8 * dst.d);      // (sample, band) pairs are a multiple of 8: every XCD slot sequence is whole
+        hipLaunchKernelGGL(cl_stem3d_kernel, dim3(nwg), dim3(256), 0, st, t);
+    } else if (P.form == ClForm::Widen3x3) {
+        ClWiden3Args t;
+        memset(&t, 0, sizeof(t));
+        t.x = x; t.y = y; t.wp = wp;
+        t.N = src.n; t.H = src.h; t.OCp = P.OCp; t.act = act; t.bands = src.h / 16; t.slope = slope;
+        t.x_sn = src.sn; t.y_sn = dst.sn; t.x_sh = (int32_t)src.sh; t.x_sw = (int32_t)src.sw; t.y_sh = (int32_t)dst.sh; t.y_sw = (int32_t)dst.sw;
+        t.x_bytes = (uint32_t)P.xb; t.y_bytes = (uint32_t)P.yb;
+        const unsigned nwg = (unsigned)((src.n + 7) / 8 * 8 * t.bands);
+        if (P.OC == 128) hipLaunchKernelGGL((cl_widen3x3_kernel<4>), dim3(nwg), dim3(256), 0, st, t);
+        else hipLaunchKernelGGL((cl_widen3x3_kernel<2>), dim3(nwg), dim3(256), 0, st, t);
+    } else if (P.form == ClForm::Patch) {
+        const ClPatchPlan& pp = P.patch;
+        ClPatchArgs t;
+        memset(&t, 0, sizeof(t));
+        t.x = x; t.y = y; t.wp = reinterpret_cast<const cl_h*>(static_cast<const char*>(packed) + P.pack_generic);
+        t.N = src.n; t.H = src.h; t.W = src.w; t.C32 = pp.C32; t.OCp = pp.OCp; t.octiles = pp.octiles; t.NI = pp.NI; t.PRI = pp.PRI;
+        t.RI = pp.RI; t.prows = pp.prows; t.bands = pp.bands; t.npatch = pp.npatch; t.wlog = pp.wlog; t.plog = pp.plog; t.act = act; t.y_c = P.OC;
+        t.slope = slope; t.total = pp.npatch * pp.octiles;
+        t.x_sn = src.sn; t.y_sn = dst.sn; t.x_sh = (int32_t)src.sh; t.x_sw = (int32_t)src.sw; t.y_sh = (int32_t)dst.sh; t.y_sw = (int32_t)dst.sw;
+        t.x_bytes = (uint32_t)P.xb; t.y_bytes = (uint32_t)P.yb; t.w_bytes = (uint32_t)pp.pack_bytes;
+        if (P.stat_need) t.stat = stat;
+        if (pp.NP == 256) hipLaunchKernelGGL((cl_patch_convt_kernel<8>), dim3((unsigned)((t.total + 7) / 8 * 8)), dim3(512), 0, st, t);
+        else hipLaunchKernelGGL((cl_patch_convt_kernel<4>), dim3((unsigned)((t.total + 7) / 8 * 8)), dim3(256), 0, st, t);
+    } else {
+        if (P.nlaunch == 0) return DCV_OK;
+        // rows of position tiles a class does not have (classes of different sizes) must read as zero
+        if (P.stat_need) DCV_HIP_CHECK(hipMemsetAsync(stat, 0, P.stat_need, st));
+        ClGatherPack pk;
+        memset(&pk, 0, sizeof(pk));
+        int n = 0;
+        for (const ClPlanClass& pc : P.cls) {
+            if (!pc.M) continue;
+            const ClClass& c = pc.c;
+            ClGatherArgs& a = pk.c[n];
+            a.x = x; a.y = y; a.wp = reinterpret_cast<const cl_h*>(static_cast<const char*>(packed) + pc.pack_off);
+            a.M = (int)pc.M; a.OCp = P.OCp; a.T = pc.T; a.cblk = P.thin ? 0 : P.Cp / 32; a.nsteps = pc.nsteps; a.y_c = P.ocs; a.x_cmax = 2 * pad8(P.RC);
+            a.div_sp = make_fastdiv((uint32_t)(c.o_ext[0] * c.o_ext[1] * c.o_ext[2])); a.div_hw = make_fastdiv((uint32_t)(c.o_ext[1] * c.o_ext[2])); a.div_w = make_fastdiv((uint32_t)c.o_ext[2]);
+            a.td = c.t[0]; a.th = c.t[1]; a.tw = c.t[2];
+            a.x_sn = src.sn; a.x_sd = (int32_t)src.sd; a.x_sh = (int32_t)src.sh; a.x_sw = (int32_t)src.sw;
+            a.y_sn = dst.sn; a.y_sd = (int32_t)(dst.sd * c.out_mul[0]); a.y_sh = (int32_t)(dst.sh * c.out_mul[1]); a.y_sw = (int32_t)(dst.sw * c.out_mul[2]);
+            a.y_off = (int32_t)(dst.sd * c.out_off[0] + dst.sh * c.out_off[1] + dst.sw * c.out_off[2]);
+            a.act = act; a.slope = slope; a.accumulate = accumulate; a.coalesce = P.coalesce; a.pad2 = P.dbg;
+            if (gate) { a.gate = static_cast<const cl_h*>(gate); a.gate_slope = gate_slope; }
+            a.x_bytes = (uint32_t)P.xb; a.y_bytes = (uint32_t)P.yb;
+            for (int t = 0; t < pc.T; ++t) {
+                const int ud = t / (c.t[1].n * c.t[2].n), uh = (t / c.t[2].n) % c.t[1].n, uw = t % c.t[2].n;
+                a.toff[t] = (int32_t)(2 * ((int64_t)c.t[0].delta[ud] * src.sd + (int64_t)c.t[1].delta[uh] * src.sh + (int64_t)c.t[2].delta[uw] * src.sw));
+                a.tsel[t] = ud | (uh << 2) | (uw << 4);
+            }
+            if (P.stat_need) { a.stat = stat; a.stat_row0 = (int32_t)(n * P.maxtm); }
+            ++n;
+        }
+        const ClSplitK& sk = P.sk;
+        if (sk.KS) { pk.c[0].slab = static_cast<float*>(ws); pk.c[0].ks_per = sk.ks_per; pk.c[0].slab_m = sk.slab_m; }
+        for (int i = n; i < 4; ++i) pk.c[i] = pk.c[0];
+        pk.ncls = n; pk.tiles_oc = P.OCp / P.tile.bn; pk.tiles_m = (int)P.maxtm;
+        dim3 grid((unsigned)((P.maxtm + 7) / 8 * 8 * pk.tiles_oc * n));
+        if (sk.KS) grid.y = (unsigned)sk.KS;
+        cl_launch_tile(P.tile, pk, P.thin, grid, st);
+        if (sk.KS) {
+            DCV_LAUNCH_CHECK();
+            const int64_t tot = (int64_t)pk.c[0].M * (P.ocs / 8);
+            hipLaunchKernelGGL(cl_splitk_reduce_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, pk.c[0], sk.KS);
+        }
+    }
+    memcpy(g_last_kernel, P.note, sizeof(g_last_kernel));
+    DCV_LAUNCH_CHECK();
+    return DCV_OK;
+}
 
 // The position table of a weight-gradient call depends on the geometry and the two tensors' shapes / strides only: built once per (device, key) and kept
 // (16 bytes per dense position; the iteration's ~30 distinct layers hold ~0.5 GB at B = 100).  DCV_CL_NO_POSTAB_CACHE=1: rebuild into the workspace per call.
@@ -1805,34 +2097,44 @@ static bool cl_pixel_linear(const dcv_dims5& d, int64_t* pitch) {
 struct ClWgradPlan {
     int64_t M;
     int DC, GC, T, tiles_d, gblocks, gcb, ntpt, tiles_j, tiles, S, chunk, wtiles;
-    bool narrow;
+    bool narrow, xcd_map, old_reduce, cache;      // (the last three: DCV_CL_WGRAD_FLAT, DCV_CL_OLD_WGRAD_REDUCE, DCV_CL_NO_POSTAB_CACHE — A/B only)
     size_t tab_bytes, slab_bytes;
+    int64_t dpitch, dbytes, gbytes;               // the dense operand's pixel pitch; the two operands' extents (not for a size query)
 };
-static int cl_wgrad_plan(const dcv_conv_geom* g, const dcv_dims5& D, const dcv_dims5& G, ClWgradPlan* p) {
+// D: the dense operand, G: the gathered one.  `sizing` (dcv_cl_wgrad_workspace_bytes): shapes only, the tensors' strides and extents are not checked.
+static int cl_wgrad_plan(const dcv_conv_geom* g, const dcv_dims5& D, const dcv_dims5& G, bool sizing, ClWgradPlan* p) {
+    const ClToggles& tg = cl_toggles();
     p->M = (int64_t)D.n * D.d * D.h * D.w;
     if (p->M >= (1ll << 31) || p->M == 0) return fail(DCV_EUNSUPPORTED, "cl wgrad: position count");
     p->DC = D.c; p->GC = G.c; p->T = g->kd * g->kh * g->kw;
     if (p->T > 64) return fail(DCV_EUNSUPPORTED, "cl wgrad: more than 64 taps");
+    p->dpitch = p->dbytes = p->gbytes = 0;
+    if (!sizing) {
+        int rc;
+        if ((rc = cl_check_tensor(D, "cl wgrad dense operand")) != DCV_OK || (rc = cl_check_tensor(G, "cl wgrad gathered operand")) != DCV_OK) return rc;
+        if (!cl_pixel_linear(D, &p->dpitch)) return fail(DCV_EUNSUPPORTED, "cl wgrad: the dense operand must be pixel-linear (a whole tensor or a channel slice of one)");
+        p->dbytes = 2 * ((p->M - 1) * p->dpitch + pad8(D.c)); p->gbytes = cl_extent_bytes(G, pad8(G.c));
+        if (p->dbytes >= (1ll << 31) || p->gbytes >= (1ll << 31)) return fail(DCV_EUNSUPPORTED, "cl wgrad: tensors beyond 2 GB");
+        if (G.w > 1 && G.sw < pad8(G.c)) return fail(DCV_EINVAL, "cl wgrad: gathered operand's pixel pitch below its padded channel count");
+    }
     const int gcp = pad8(G.c);
     if (gcp >= 128) { p->gcb = 128; p->gblocks = (gcp + 127) / 128; p->ntpt = 1; }
     else { p->gcb = gcp; p->gblocks = 1; p->ntpt = 128 / gcp; }
     p->tiles_d = (pad8(D.c) + 127) / 128;
     p->tiles_j = (p->T + p->ntpt - 1) / p->ntpt * p->gblocks;
-    static const bool no_packed = getenv("DCV_CL_WGRAD_NO_PACKED") != nullptr;      // A/B only
-    if (!no_packed && gcp < 128 && 128 % gcp != 0) {      // packed columns: a tile's 128 columns run across tap boundaries (cl_wgrad_kernel, ntpt = 0)
+    if (!tg.wgrad_no_packed && gcp < 128 && 128 % gcp != 0) {      // packed columns: a tile's 128 columns run across tap boundaries (cl_wgrad_kernel, ntpt = 0)
         const int tj = (p->T * gcp + 127) / 128;
         if (tj < p->tiles_j) { p->ntpt = 0; p->tiles_j = tj; }
     }
     p->tiles = p->tiles_d * p->tiles_j;
     // narrow form (cl_wgrad_kernel<true>): a dense operand of <= 64 channels fills half of a 128-row tile: column tiles in pairs instead
-    static const bool no_narrow = getenv("DCV_CL_WGRAD_NO_NARROW") != nullptr;      // A/B only
-    p->narrow = !no_narrow && pad8(D.c) <= 64 && p->tiles_j >= 2;
+    p->narrow = !tg.wgrad_no_narrow && pad8(D.c) <= 64 && p->tiles_j >= 2;
     p->wtiles = p->narrow ? (p->tiles_j + 1) / 2 : p->tiles;
+    p->xcd_map = !tg.wgrad_flat; p->old_reduce = tg.old_wgrad_reduce; p->cache = !tg.no_postab_cache;
     // position splits: ~768 workgroups (three per CU) however few tiles the op has, at least 16 K steps (512 positions) each; measured over the
     // surreal-depth1 layer table with the first reduce kernel: 13.8 ms of weight gradients per iteration at 1024, 15.9 at 2048, 20.1 at 4096 (slab traffic); with the
     // slab-order reduce, whole iterations on one box: 48.6 / 48.2 / 48.9 / 48.6 ms at 640 / 768 / 896 / 1024 (surreal-depth1), 41.8 / 41.6 / 42.1 / 42.1 (isogd-depth)
-    static const int64_t target = getenv("DCV_CL_WGRAD_WGS") ? atoll(getenv("DCV_CL_WGRAD_WGS")) : 768;
-    int64_t S = (target + p->wtiles - 1) / p->wtiles;
+    int64_t S = (tg.wgrad_wgs + p->wtiles - 1) / p->wtiles;
     const int64_t maxS = std::max<int64_t>(1, p->M / 512);
     S = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(S, maxS), 2048));
     int64_t chunk = ((p->M + S - 1) / S + 31) / 32 * 32;
@@ -1855,399 +2157,100 @@ extern "C" {
 #ifdef DCV_CL_STAMP
 int dcv_cl_debug_read_stamps(unsigned long long* host, int zero) {
     if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_cl_stamps), sizeof(g_cl_stamps)) != hipSuccess) return -1;
-    if (zero) { static unsigned long long z[8]; (void)z; hipMemset(nullptr, 0, 0); void* p = nullptr; if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_cl_stamps)) == hipSuccess) (void)hipMemset(p, 0, sizeof(g_cl_stamps)); }
+    void* p = nullptr;
+    if (zero && hipGetSymbolAddress(&p, HIP_SYMBOL(g_cl_stamps)) == hipSuccess) (void)hipMemset(p, 0, sizeof(g_cl_stamps));
     return 0;
 }
 #endif
 
+// The three size queries: 0 (and dcv_last_error) where the planner refuses the shapes.  What they return is what the calls REQUIRE.
 size_t dcv_cl_packed_bytes(const dcv_conv_geom* g, const dcv_dims5* x, const dcv_dims5* y, int which) {
-    ClPlan pl;
-    if (!g || !x || !y || (which != 0 && which != 1) || cl_make_plan(which, g, x, y, &pl) != DCV_OK) return 0;
-    if (cl_thin_out(pl, g)) {
-        const int OCg = g->kd * g->kh * g->kw * pl.OC;
-        const ClTile tc = cl_pick_tile(OCg);
-        return align_up((size_t)(cl_cp(pl.RC) / 32) * ((OCg + tc.bn - 1) / tc.bn * tc.bn) * 64, 256) + 256;
-    }
-    // (+ the patch-staged form's tiles behind the tiled gather's, where the shapes allow that kernel: cl_patch_plan)
-    const ClPatchPlan pp = cl_patch_plan(which, g, pl, which == 0 ? *x : *y, which == 0 ? *y : *x);
-    return cl_generic_pack_bytes(pl) + (pp.ok ? pp.pack_bytes : 0) + 256;
+    ClPlan P;
+    return cl_plan_sizes(which, g, x, y, false, &P) == DCV_OK ? P.pack_bytes : 0;
 }
-
-// scratch a forward / backward-data call needs (the Z tensor of the thin-destination form; 0 otherwise)
+// scratch a forward / backward-data call needs: the Z tensor of the thin-destination forms, the slabs of a split-K call
 size_t dcv_cl_conv_workspace_bytes(const dcv_conv_geom* g, const dcv_dims5* x, const dcv_dims5* y, int which) {
-    ClPlan pl;
-    if (!g || !x || !y || (which != 0 && which != 1) || cl_make_plan(which, g, x, y, &pl) != DCV_OK) return 0;
-    if (!cl_thin_out(pl, g)) {
-        // split-K slabs of a single-class call with few position tiles (cl_splitk_plan; the run splits only if this much workspace is there)
-        size_t slab = 0;
-        if (pl.cls.size() == 1) {
-            const dcv_dims5& dst = (which == 0) ? *y : *x;
-            const ClClass& c = pl.cls[0];
-            const ClTile tc = cl_pick_tile(pl.OC);
-            const int OCp = (pl.OC + tc.bn - 1) / tc.bn * tc.bn, T = c.t[0].n * c.t[1].n * c.t[2].n;
-            const int nsteps = cl_thin(pl.RC) ? (T + 3) / 4 : T * (cl_cp(pl.RC) / 32);
-            slab = cl_splitk_plan(1, cl_thin(pl.RC), (int64_t)dst.n * c.o_ext[0] * c.o_ext[1] * c.o_ext[2], c.o_ext[0] * c.o_ext[1] * c.o_ext[2], OCp, nsteps, tc, 8).slab_bytes;
-        }
-        return 256 + slab;
-    }
-    const dcv_dims5& src = (which == 0) ? *x : *y;
-    return (size_t)src.n * src.d * src.h * src.w * cl_pitch(g->kd * g->kh * g->kw * pl.OC) * 2 + 512;
+    ClPlan P;
+    return cl_plan_sizes(which, g, x, y, false, &P) == DCV_OK ? P.ws_need + (P.thin_out ? 512 : 256) : 0;
+}
+// bytes of the per-tile BatchNorm sums dcv_cl_conv_forward_stats leaves (0: this geometry's form does not produce them)
+size_t dcv_cl_conv_stats_bytes(const dcv_conv_geom* g, const dcv_dims5* xd, const dcv_dims5* yd) {
+    ClPlan P;
+    return cl_plan_sizes(0, g, xd, yd, true, &P) == DCV_OK ? P.stat_need : 0;
 }
 
 int dcv_cl_pack_weights(const dcv_conv_geom* g, const dcv_dims5* x, const dcv_dims5* y, int which, const float* w, void* packed, size_t bytes, void* stream) {
-    ClPlan pl;
-    if (!g || !x || !y || !w || !packed) return fail(DCV_EINVAL, "cl_pack_weights: null pointer");
-    int rc = cl_make_plan(which, g, x, y, &pl);
+    if (!w || !packed) return fail(DCV_EINVAL, "cl_pack_weights: null pointer");
+    ClPlan P;
+    const int rc = cl_plan_sizes(which, g, x, y, false, &P);
     if (rc != DCV_OK) return rc;
-    if (cl_thin_out(pl, g)) {
+    if (bytes < P.pack_bytes) return fail(DCV_EWORKSPACE, "cl_pack_weights: buffer too small (%zu needed, %zu given)", P.pack_bytes, bytes);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (P.thin_out) {
         ClPackThinArgs ta;
         memset(&ta, 0, sizeof(ta));
-        ta.T = g->kd * g->kh * g->kw; ta.OC = pl.OC; ta.OCg = ta.T * pl.OC; ta.C = pl.RC;
-        const ClTile tg = cl_pick_tile(ta.OCg);
-        ta.OCgp = (ta.OCg + tg.bn - 1) / tg.bn * tg.bn;
-        ta.nsteps = cl_cp(pl.RC) / 32;
-        ta.ws_o = pl.ws_o; ta.ws_r = pl.ws_r;
-        ta.wp = static_cast<cl_h*>(packed);
+        ta.T = g->kd * g->kh * g->kw; ta.OC = P.OC; ta.OCg = ta.T * P.OC; ta.C = P.RC;
+        ta.OCgp = P.OCp; ta.nsteps = P.cls[0].nsteps; ta.ws_o = P.ws_o; ta.ws_r = P.ws_r; ta.wp = static_cast<cl_h*>(packed);
         const int64_t tot = (int64_t)ta.nsteps * ta.OCgp * 32;
-        if ((size_t)tot * 2 > bytes) return fail(DCV_EWORKSPACE, "cl_pack_weights: buffer too small");
-        hipLaunchKernelGGL(cl_pack_thin_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), w, ta);
+        hipLaunchKernelGGL(cl_pack_thin_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, w, ta);
         DCV_LAUNCH_CHECK();
         return DCV_OK;
     }
-    const ClTile tc = cl_pick_tile(pl.OC);
+    if (P.cls.empty()) return DCV_OK;
     ClPackArgs pa;
     memset(&pa, 0, sizeof(pa));
-    size_t off = 0;
     int n = 0;
     int64_t maxtot = 0;
-    pa.OC = pl.OC; pa.OCp = (pl.OC + tc.bn - 1) / tc.bn * tc.bn; pa.C = pl.RC; pa.cblk = cl_thin(pl.RC) ? 0 : cl_cp(pl.RC) / 32;
-    pa.ws_o = pl.ws_o; pa.ws_r = pl.ws_r;
-    for (const ClClass& c : pl.cls) {
-        const int T = c.t[0].n * c.t[1].n * c.t[2].n;
-        const size_t b = cl_class_pack_bytes(c, pl.RC, pl.OC);
-        if (T == 0) continue;
-        if (off + b > bytes) return fail(DCV_EWORKSPACE, "cl_pack_weights: buffer too small");
-        pa.wp[n] = reinterpret_cast<cl_h*>(static_cast<char*>(packed) + off);
-        pa.T[n] = T;
-        pa.nsteps[n] = cl_thin(pl.RC) ? (T + 3) / 4 : T * (cl_cp(pl.RC) / 32);
-        for (int t = 0; t < T; ++t) {
+    pa.OC = P.OC; pa.OCp = P.OCp; pa.C = P.RC; pa.cblk = P.thin ? 0 : P.Cp / 32; pa.ws_o = P.ws_o; pa.ws_r = P.ws_r;
+    for (const ClPlanClass& pc : P.cls) {
+        const ClClass& c = pc.c;
+        pa.wp[n] = reinterpret_cast<cl_h*>(static_cast<char*>(packed) + pc.pack_off);
+        pa.T[n] = pc.T; pa.nsteps[n] = pc.nsteps;
+        for (int t = 0; t < pc.T; ++t) {
             const int ud = t / (c.t[1].n * c.t[2].n), uh = (t / c.t[2].n) % c.t[1].n, uw = t % c.t[2].n;
-            pa.kidx[n][t] = (c.t[0].kidx[ud] * pl.KH + c.t[1].kidx[uh]) * pl.KW + c.t[2].kidx[uw];
+            pa.kidx[n][t] = (c.t[0].kidx[ud] * P.KH + c.t[1].kidx[uh]) * P.KW + c.t[2].kidx[uw];
         }
-        maxtot = std::max<int64_t>(maxtot, (int64_t)pa.nsteps[n] * pa.OCp * 32);
-        off += b;
-        if (++n > 4) return fail(DCV_EUNSUPPORTED, "cl_pack_weights: more than 4 position classes");
+        maxtot = std::max<int64_t>(maxtot, (int64_t)pc.nsteps * P.OCp * 32);
+        ++n;
     }
-    if (n == 0) return DCV_OK;
     pa.ncls = n;
-    hipLaunchKernelGGL(cl_pack_kernel, dim3((unsigned)((maxtot + 255) / 256), (unsigned)n), dim3(256), 0, static_cast<hipStream_t>(stream), w, pa);
+    hipLaunchKernelGGL(cl_pack_kernel, dim3((unsigned)((maxtot + 255) / 256), (unsigned)n), dim3(256), 0, st, w, pa);
     DCV_LAUNCH_CHECK();
-    const ClPatchPlan pp = cl_patch_plan(which, g, pl, which == 0 ? *x : *y, which == 0 ? *y : *x);
-    if (pp.ok) {
-        const size_t o2 = cl_generic_pack_bytes(pl);
-        if (o2 + pp.pack_bytes > bytes) return fail(DCV_EWORKSPACE, "cl_pack_weights: buffer too small");
+    if (P.patch.ok) {
         ClPackPatchArgs pq;
         memset(&pq, 0, sizeof(pq));
-        pq.wp = reinterpret_cast<cl_h*>(static_cast<char*>(packed) + o2);
-        pq.OC = pl.OC; pq.OCp = pp.OCp; pq.C = pl.RC; pq.C32 = pp.C32; pq.KW = pl.KW; pq.ws_o = pl.ws_o; pq.ws_r = pl.ws_r;
-        const int64_t tot = (int64_t)pp.OCp * pp.C32 * 16 * 32;
-        hipLaunchKernelGGL(cl_pack_patch_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), w, pq);
+        pq.wp = reinterpret_cast<cl_h*>(static_cast<char*>(packed) + P.pack_generic);
+        pq.OC = P.OC; pq.OCp = P.patch.OCp; pq.C = P.RC; pq.C32 = P.patch.C32; pq.KW = P.KW; pq.ws_o = P.ws_o; pq.ws_r = P.ws_r;
+        const int64_t tot = (int64_t)P.patch.OCp * P.patch.C32 * 16 * 32;
+        hipLaunchKernelGGL(cl_pack_patch_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, w, pq);
         DCV_LAUNCH_CHECK();
     }
     return DCV_OK;
 }
 
-// which: 0 forward (x -> y), 1 backward-data (dy -> dx); src / dst are bf16 channels-last
-static int cl_conv_thin_out(int which, const dcv_conv_geom* g, const ClPlan& pl, const void* src_p, const dcv_dims5& src, const void* packed, void* dst_p,
-                            const dcv_dims5& dst, int act, float slope, int accumulate, void* ws, size_t ws_bytes, hipStream_t st) {
-    const int T = g->kd * g->kh * g->kw, OCg = T * pl.OC, zp = cl_pitch(OCg), Cp = cl_cp(pl.RC);
-    const int64_t Msrc = (int64_t)src.n * src.d * src.h * src.w;
-    if (Msrc >= (1ll << 31)) return fail(DCV_EUNSUPPORTED, "cl conv: too many source pixels");
-    const size_t zbytes = (size_t)Msrc * zp * 2;
-    if (!ws || ws_bytes < zbytes) return fail(DCV_EWORKSPACE, "cl conv: workspace too small for the thin-destination form (%zu needed, %zu given)", zbytes, ws_bytes);
-    if (src.w > 1 && src.sw < Cp) return fail(DCV_EINVAL, "cl conv: source pixel pitch %lld < padded channels %d", (long long)src.sw, Cp);
-    if (dst.w > 1 && dst.sw < 8) return fail(DCV_EINVAL, "cl conv: thin destination needs a pixel pitch of 8");
-    const int64_t xb = cl_extent_bytes(src, Cp);
-    if (xb >= (1ll << 31) || zbytes >= (1ull << 31)) return fail(DCV_EUNSUPPORTED, "cl conv: tensors beyond 2 GB");
-    {
-        // fused form (cl_thin3x3_kernel): 2-D 3x3 / stride 1 / pad 1 scatter-form, 64-wide rows, rows in bands of 16, 32 / 64 / 128 source channels, <= 3 destination channels
-        static const bool no_fused = getenv("DCV_CL_NO_THIN3") != nullptr;      // A/B only
-        const bool direct3 = (which == 0 && !g->transposed) || (which == 1 && g->transposed);
-        const int C3 = pl.RC;
-        if (!no_fused && !accumulate && !direct3 && g->kd == 1 && g->kh == 3 && g->kw == 3 && g->sd == 1 && g->sh == 1 && g->sw == 1 && g->pd == 0 && g->ph == 1 && g->pw == 1 &&
-            src.d == 1 && dst.d == 1 && src.w == 64 && src.h % 16 == 0 && dst.w == 64 && dst.h == src.h && pl.OC <= 3 && (C3 == 32 || C3 == 64 || C3 == 128) &&
-            (reinterpret_cast<uintptr_t>(src_p) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst_p) & 15) == 0 && dst.sw >= 8 && src.sw >= C3) {
-            const int64_t xb3 = cl_extent_bytes(src, C3), yb3 = cl_extent_bytes(dst, 8);
-            if (xb3 < (1ll << 31) && yb3 < (1ll << 31)) {
-                ClThin3Args t;
-                memset(&t, 0, sizeof(t));
-                t.x = static_cast<const cl_h*>(src_p); t.y = static_cast<cl_h*>(dst_p); t.wp = static_cast<const cl_h*>(packed);
-                t.N = src.n; t.H = src.h; t.OC = pl.OC; t.act = act; t.bands = src.h / 16; t.slope = slope;
-                t.x_sn = src.sn; t.y_sn = dst.sn; t.x_sh = (int32_t)src.sh; t.x_sw = (int32_t)src.sw; t.y_sh = (int32_t)dst.sh; t.y_sw = (int32_t)dst.sw;
-                t.x_bytes = (uint32_t)xb3; t.y_bytes = (uint32_t)yb3;
-                const unsigned nwg = (unsigned)((src.n + 7) / 8 * 8 * t.bands);
-                if (C3 == 128) hipLaunchKernelGGL((cl_thin3x3_kernel<16>), dim3(nwg), dim3(256), 0, st, t);
-                else if (C3 == 64) hipLaunchKernelGGL((cl_thin3x3_kernel<8>), dim3(nwg), dim3(256), 0, st, t);
-                else hipLaunchKernelGGL((cl_thin3x3_kernel<4>), dim3(nwg), dim3(256), 0, st, t);
-                snprintf(g_last_kernel, sizeof(g_last_kernel), "cl_thin3x3_kernel<%d> (fused GEMM + tap gather, thin destination, " CL_HALF_NAME " channels-last)", C3 / 8);
-                DCV_LAUNCH_CHECK();
-                return DCV_OK;
-            }
-        }
-    }
-    const ClTile tc = cl_pick_tile(OCg);
-    const int OCgp = (OCg + tc.bn - 1) / tc.bn * tc.bn;
-    // (1) Z = X (1x1) Wg : every source pixel once
-    ClGatherPack pk;
-    memset(&pk, 0, sizeof(pk));
-    ClGatherArgs& a = pk.c[0];
-    a.x = static_cast<const cl_h*>(src_p); a.y = static_cast<cl_h*>(ws); a.wp = static_cast<const cl_h*>(packed);
-    a.M = (int)Msrc; a.OCp = OCgp; a.T = 1; a.cblk = Cp / 32; a.nsteps = Cp / 32; a.y_c = pad8(OCg); a.x_cmax = 2 * pad8(pl.RC);      // Z owns its pixels (pitch zp >= pad8): whole 8-column groups, zeros past OCg
-    a.div_sp = make_fastdiv((uint32_t)(src.d * src.h * src.w)); a.div_hw = make_fastdiv((uint32_t)(src.h * src.w)); a.div_w = make_fastdiv((uint32_t)src.w);
-    ClDim one;
-    memset(&one, 0, sizeof(one));
-    one.n = 1; one.mul = 1; one.base = 0;
-    a.td = one; a.td.size = src.d; a.th = one; a.th.size = src.h; a.tw = one; a.tw.size = src.w;
-    a.x_sn = src.sn; a.x_sd = (int32_t)src.sd; a.x_sh = (int32_t)src.sh; a.x_sw = (int32_t)src.sw;
-    a.y_sn = (int64_t)src.d * src.h * src.w * zp; a.y_sd = src.h * src.w * zp; a.y_sh = src.w * zp; a.y_sw = zp; a.y_off = 0;
-    a.act = DCV_ACT_NONE; a.x_bytes = (uint32_t)xb; a.y_bytes = (uint32_t)zbytes;
-    a.coalesce = (a.y_c % 8 == 0 && (reinterpret_cast<uintptr_t>(ws) & 15) == 0 && !getenv("DCV_CL_DIRECT_EPILOGUE")) ? 1 : 0;
-    for (int i = 1; i < 4; ++i) pk.c[i] = pk.c[0];
-    pk.ncls = 1; pk.tiles_oc = OCgp / tc.bn; pk.tiles_m = (int)((Msrc + tc.bm - 1) / tc.bm);
-    const dim3 grid((unsigned)((pk.tiles_m + 7) / 8 * 8 * pk.tiles_oc));
-    cl_launch_tile(tc, pk, false, grid, st);
-    DCV_LAUNCH_CHECK();
-    // (2) gather the taps of every destination pixel
-    ClCol2imArgs c;
-    memset(&c, 0, sizeof(c));
-    c.z = static_cast<const cl_h*>(ws); c.y = static_cast<cl_h*>(dst_p);
-    c.OC = pl.OC; c.zpitch = zp; c.T = T;
-    const bool direct = (which == 0 && !g->transposed) || (which == 1 && g->transposed);
-    c.scatter = direct ? 0 : 1;
-    c.k[0] = g->kd; c.k[1] = g->kh; c.k[2] = g->kw; c.s[0] = g->sd; c.s[1] = g->sh; c.s[2] = g->sw; c.p[0] = g->pd; c.p[1] = g->ph; c.p[2] = g->pw;
-    c.sext[0] = src.d; c.sext[1] = src.h; c.sext[2] = src.w; c.dext[0] = dst.d; c.dext[1] = dst.h; c.dext[2] = dst.w;
-    c.act = act; c.slope = slope; c.accumulate = accumulate;
-    c.div_sp = make_fastdiv((uint32_t)(dst.d * dst.h * dst.w)); c.div_hw = make_fastdiv((uint32_t)(dst.h * dst.w)); c.div_w = make_fastdiv((uint32_t)dst.w);
-    c.y_sn = dst.sn; c.y_sd = (int32_t)dst.sd; c.y_sh = (int32_t)dst.sh; c.y_sw = (int32_t)dst.sw;
-    c.s_sp = src.d * src.h * src.w; c.s_hw = src.h * src.w; c.s_w = src.w;
-    c.total = (int64_t)dst.n * dst.d * dst.h * dst.w;
-    if (c.total >= (1ll << 31)) return fail(DCV_EUNSUPPORTED, "cl conv: too many destination pixels");
-    hipLaunchKernelGGL(cl_col2im_kernel, dim3((unsigned)((c.total + 255) / 256)), dim3(256), 0, st, c);
-    snprintf(g_last_kernel, sizeof(g_last_kernel), "cl_gather_kernel<%d x %d tile> as a 1x1 GEMM over the source + cl_col2im_kernel (thin destination, " CL_HALF_NAME " channels-last)", tc.bn, tc.bm);
-    DCV_LAUNCH_CHECK();
-    return DCV_OK;
-}
-
+// which: 0 forward (x -> y), 1 backward-data (dy -> dx); src / dst are bf16 channels-last.  Plans (every refusal), then launches.
 // `stat` (forward, no activation, no accumulation, a full-channel destination): per-tile BatchNorm sums from the epilogue, *nparts rows of *pitch channels x {sum, sum^2};
-// *nparts stays 0 where the form does not produce them (thin destinations) and the caller's BatchNorm op takes its own statistics.
+// *nparts stays 0 where the form does not produce them (thin destinations) or stat_bytes is short, and the caller's BatchNorm op takes its own statistics.
 static int cl_conv_run(int which, const dcv_conv_geom* g, const void* src_p, const dcv_dims5* xd, const void* packed, void* dst_p, const dcv_dims5* yd,
                        int act, float slope, int accumulate, void* ws, size_t ws_bytes, void* stream,
                        float* stat = nullptr, size_t stat_bytes = 0, int* nparts = nullptr, int* pitch = nullptr, const void* gate = nullptr, float gate_slope = 0.f) {
     if (nparts) *nparts = 0;
     if (pitch) *pitch = 0;
     if (!g || !xd || !yd || !src_p || !packed || !dst_p) return fail(DCV_EINVAL, "cl conv: null pointer");
-    ClPlan pl;
-    int rc = cl_make_plan(which, g, xd, yd, &pl);
+    auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const ClCall o = {act, accumulate, gate != nullptr, stat != nullptr, stat_bytes, ws ? ws_bytes : 0, a16(src_p), a16(dst_p), a16(packed), a16(ws), false};
+    ClPlan P;
+    int rc = cl_plan(which, g, xd, yd, o, &P);
     if (rc != DCV_OK) return rc;
-    const dcv_dims5& src = (which == 0) ? *xd : *yd;
-    const dcv_dims5& dst = (which == 0) ? *yd : *xd;
-    if ((rc = cl_check_tensor(src, "cl conv source")) != DCV_OK || (rc = cl_check_tensor(dst, "cl conv destination")) != DCV_OK) return rc;
-    if (gate && (cl_thin_out(pl, g) || cl_thin(pl.RC))) return fail(DCV_EUNSUPPORTED, "cl conv: no gated epilogue in the thin forms");
-    if (cl_thin_out(pl, g)) return cl_conv_thin_out(which, g, pl, src_p, src, packed, dst_p, dst, act, slope, accumulate, ws, ws_bytes, static_cast<hipStream_t>(stream));
-    const bool thin = cl_thin(pl.RC);
-    const int Cp = cl_cp(pl.RC);
-    // the gathered tensor's channel slice must be readable in whole K granules: pixel pitch >= padded channel count
-    if (src.w > 1 && src.sw < (thin ? 8 : Cp)) return fail(DCV_EINVAL, "cl conv: source pixel pitch %lld < padded channels %d", (long long)src.sw, thin ? 8 : Cp);
-    // stores are 4-channel groups; a destination that owns its whole pixel (not a channel slice of a wider buffer) gets all pad8(OC) channels written —
-    // zeros past OC — so nobody has to clear a fresh tensor's padding channels first
-    const int ocs = (dst.w > 1 ? dst.sw : pad8(pl.OC)) >= pad8(pl.OC) && pl.OC % 8 ? pad8(pl.OC) : (pl.OC + 3) / 4 * 4;
-    if (dst.w > 1 && dst.sw < ocs) return fail(DCV_EINVAL, "cl conv: destination pixel pitch %lld < %d stored channels", (long long)dst.sw, ocs);
-    if (thin && !accumulate && !stat && !gate) {
-        // fused 3-D stem (cl_stem3d_kernel): Conv3d(<= 8 -> 32, 4x4x4, stride (1, 2, 2), padding (0, 1, 1)) forward on 64 x 64 frames
-        static const bool no_stem = getenv("DCV_CL_NO_STEM3") != nullptr;      // A/B only
-        if (!no_stem && which == 0 && !g->transposed && g->kd == 4 && g->kh == 4 && g->kw == 4 && g->sd == 1 && g->sh == 2 && g->sw == 2 && g->pd == 0 && g->ph == 1 && g->pw == 1 &&
-            src.h == 64 && src.w == 64 && dst.h == 32 && dst.w == 32 && dst.d == src.d - 3 && pl.OC == 32 && ocs == 32 &&
-            (reinterpret_cast<uintptr_t>(src_p) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst_p) & 15) == 0 && src.sw >= 8 && dst.sw >= 32 &&
-            cl_extent_bytes(src, 8) < (1ll << 31) && cl_extent_bytes(dst, 32) < (1ll << 31)) {
-            ClStem3Args t;
-            memset(&t, 0, sizeof(t));
-            t.x = static_cast<const cl_h*>(src_p); t.y = static_cast<cl_h*>(dst_p); t.wp = static_cast<const cl_h*>(packed);
-            t.N = src.n; t.OD = dst.d; t.act = act; t.slope = slope;
-            t.x_sn = src.sn; t.y_sn = dst.sn; t.x_sd = (int32_t)src.sd; t.x_sh = (int32_t)src.sh; t.x_sw = (int32_t)src.sw;
-            t.y_sd = (int32_t)dst.sd; t.y_sh = (int32_t)dst.sh; t.y_sw = (int32_t)dst.sw;
-            t.x_bytes = (uint32_t)cl_extent_bytes(src, 8); t.y_bytes = (uint32_t)cl_extent_bytes(dst, 32);
-            const unsigned nwg = (unsigned)(src.n * 8 * dst.d);      // (sample, band) pairs are a multiple of 8: every XCD slot sequence is whole
-            hipLaunchKernelGGL(cl_stem3d_kernel, dim3(nwg), dim3(256), 0, static_cast<hipStream_t>(stream), t);
-            snprintf(g_last_kernel, sizeof(g_last_kernel), "cl_stem3d_kernel (fused, thin source, " CL_HALF_NAME " channels-last)");
-            DCV_LAUNCH_CHECK();
-            return DCV_OK;
-        }
-    }
-    if (thin && !accumulate && !stat) {
-        // fused form (cl_widen3x3_kernel): 2-D 3x3 / stride 1 / pad 1 direct form out of a thin source on 64-wide rows, 64 or 128 destination channels
-        static const bool no_fused = getenv("DCV_CL_NO_WIDEN3") != nullptr;      // A/B only
-        const bool direct3 = (which == 0 && !g->transposed) || (which == 1 && g->transposed);
-        if (!no_fused && direct3 && g->kd == 1 && g->kh == 3 && g->kw == 3 && g->sd == 1 && g->sh == 1 && g->sw == 1 && g->pd == 0 && g->ph == 1 && g->pw == 1 &&
-            src.d == 1 && dst.d == 1 && src.w == 64 && src.h % 16 == 0 && dst.w == 64 && dst.h == src.h && (pl.OC == 64 || pl.OC == 128) && pl.OC == ocs &&
-            (reinterpret_cast<uintptr_t>(src_p) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst_p) & 15) == 0 && src.sw >= 8 && dst.sw >= pl.OC &&
-            cl_extent_bytes(src, 8) < (1ll << 31) && cl_extent_bytes(dst, pl.OC) < (1ll << 31)) {
-            ClWiden3Args t;
-            memset(&t, 0, sizeof(t));
-            t.x = static_cast<const cl_h*>(src_p); t.y = static_cast<cl_h*>(dst_p); t.wp = static_cast<const cl_h*>(packed);
-            t.N = src.n; t.H = src.h; t.OCp = (pl.OC + cl_pick_tile(pl.OC).bn - 1) / cl_pick_tile(pl.OC).bn * cl_pick_tile(pl.OC).bn; t.act = act; t.bands = src.h / 16; t.slope = slope;
-            t.x_sn = src.sn; t.y_sn = dst.sn; t.x_sh = (int32_t)src.sh; t.x_sw = (int32_t)src.sw; t.y_sh = (int32_t)dst.sh; t.y_sw = (int32_t)dst.sw;
-            t.x_bytes = (uint32_t)cl_extent_bytes(src, 8); t.y_bytes = (uint32_t)cl_extent_bytes(dst, pl.OC);
-            const unsigned nwg = (unsigned)((src.n + 7) / 8 * 8 * t.bands);
-            hipStream_t st3 = static_cast<hipStream_t>(stream);
-            if (pl.OC == 128) hipLaunchKernelGGL((cl_widen3x3_kernel<4>), dim3(nwg), dim3(256), 0, st3, t);
-            else hipLaunchKernelGGL((cl_widen3x3_kernel<2>), dim3(nwg), dim3(256), 0, st3, t);
-            snprintf(g_last_kernel, sizeof(g_last_kernel), "cl_widen3x3_kernel<%d> (fused, thin source, " CL_HALF_NAME " channels-last)", pl.OC / 32);
-            DCV_LAUNCH_CHECK();
-            return DCV_OK;
-        }
-    }
-    if (!thin && !accumulate && !gate) {
-        // patch-staged scatter form (cl_patch_convt_kernel): all four stride-parity classes of a 4x4 / stride-2 layer from one staged source patch
-        const ClPatchPlan pp = cl_patch_plan(which, g, pl, src, dst);
-        const int64_t xb2 = cl_extent_bytes(src, Cp), yb2 = cl_extent_bytes(dst, ocs);
-        if (pp.ok && ocs == pl.OC && (reinterpret_cast<uintptr_t>(src_p) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst_p) & 15) == 0 &&
-            (reinterpret_cast<uintptr_t>(packed) & 15) == 0 && src.sw >= Cp && dst.sw >= pl.OC && xb2 < (1ll << 31) && yb2 < (1ll << 31) && pp.pack_bytes < (1ull << 31)) {
-            ClPatchArgs t;
-            memset(&t, 0, sizeof(t));
-            t.x = static_cast<const cl_h*>(src_p); t.y = static_cast<cl_h*>(dst_p);
-            t.wp = reinterpret_cast<const cl_h*>(static_cast<const char*>(packed) + cl_generic_pack_bytes(pl));
-            t.N = src.n; t.H = src.h; t.W = src.w; t.C32 = pp.C32; t.OCp = pp.OCp; t.octiles = pp.octiles; t.NI = pp.NI; t.PRI = pp.PRI;
-            t.RI = pp.RI; t.prows = pp.prows; t.bands = pp.bands; t.npatch = pp.npatch; t.wlog = pp.wlog; t.plog = pp.plog; t.act = act; t.y_c = pl.OC;
-            t.slope = slope; t.total = pp.npatch * pp.octiles;
-            t.x_sn = src.sn; t.y_sn = dst.sn; t.x_sh = (int32_t)src.sh; t.x_sw = (int32_t)src.sw; t.y_sh = (int32_t)dst.sh; t.y_sw = (int32_t)dst.sw;
-            t.x_bytes = (uint32_t)xb2; t.y_bytes = (uint32_t)yb2; t.w_bytes = (uint32_t)pp.pack_bytes;
-            if (stat && which == 0 && act == DCV_ACT_NONE && (size_t)pp.npatch * pp.OCp * 2 * sizeof(float) <= stat_bytes) {
-                t.stat = stat;
-                if (nparts) *nparts = pp.npatch;
-                if (pitch) *pitch = pp.OCp;
-            }
-            if (pp.NP == 256) hipLaunchKernelGGL((cl_patch_convt_kernel<8>), dim3((unsigned)((t.total + 7) / 8 * 8)), dim3(512), 0, static_cast<hipStream_t>(stream), t);
-            else hipLaunchKernelGGL((cl_patch_convt_kernel<4>), dim3((unsigned)((t.total + 7) / 8 * 8)), dim3(256), 0, static_cast<hipStream_t>(stream), t);
-            snprintf(g_last_kernel, sizeof(g_last_kernel), "cl_patch_convt_kernel<%d waves> (4 classes from one staged patch, %d x %d source, " CL_HALF_NAME " channels-last)", pp.NP / 32, src.h, src.w);
-            DCV_LAUNCH_CHECK();
-            return DCV_OK;
-        }
-    }
-    const ClTile tc = cl_pick_tile(pl.OC);
-    const int OCp = (pl.OC + tc.bn - 1) / tc.bn * tc.bn;
-    const int64_t xb = cl_extent_bytes(src, thin ? 8 : Cp), yb = cl_extent_bytes(dst, ocs);
-    if (xb >= (1ll << 31) || yb >= (1ll << 31)) return fail(DCV_EUNSUPPORTED, "cl conv: tensors beyond 2 GB need per-sample descriptors");
-    ClGatherPack pk;
-    memset(&pk, 0, sizeof(pk));
-    size_t off = 0;
-    int n = 0;
-    int64_t maxtm = 0;
-    for (const ClClass& c : pl.cls) {
-        const int T = c.t[0].n * c.t[1].n * c.t[2].n;
-        const size_t b = cl_class_pack_bytes(c, pl.RC, pl.OC);
-        if (T == 0 || c.o_ext[0] <= 0 || c.o_ext[1] <= 0 || c.o_ext[2] <= 0) {
-            if (T != 0) off += b;
-            if (T == 0 && c.o_ext[0] > 0 && c.o_ext[1] > 0 && c.o_ext[2] > 0 && !accumulate) return fail(DCV_EUNSUPPORTED, "cl conv: a position class without taps");
-            continue;
-        }
-        if (T > 64) return fail(DCV_EUNSUPPORTED, "cl conv: more than 64 taps");
-        ClGatherArgs& a = pk.c[n];
-        a.x = static_cast<const cl_h*>(src_p);
-        a.y = static_cast<cl_h*>(dst_p);
-        a.wp = reinterpret_cast<const cl_h*>(static_cast<const char*>(packed) + off);
-        off += b;
-        const int64_t M64 = (int64_t)dst.n * c.o_ext[0] * c.o_ext[1] * c.o_ext[2];
-        if (M64 >= (1ll << 31)) return fail(DCV_EUNSUPPORTED, "cl conv: too many positions");
-        a.M = (int)M64; a.OCp = OCp; a.T = T;
-        a.cblk = thin ? 0 : Cp / 32;
-        a.nsteps = thin ? (T + 3) / 4 : T * (Cp / 32);
-        a.y_c = ocs;
-        a.x_cmax = 2 * pad8(pl.RC);
-        a.div_sp = make_fastdiv((uint32_t)(c.o_ext[0] * c.o_ext[1] * c.o_ext[2]));
-        a.div_hw = make_fastdiv((uint32_t)(c.o_ext[1] * c.o_ext[2]));
-        a.div_w = make_fastdiv((uint32_t)c.o_ext[2]);
-        a.td = c.t[0]; a.th = c.t[1]; a.tw = c.t[2];
-        a.x_sn = src.sn; a.x_sd = (int32_t)src.sd; a.x_sh = (int32_t)src.sh; a.x_sw = (int32_t)src.sw;
-        a.y_sn = dst.sn;
-        a.y_sd = (int32_t)(dst.sd * c.out_mul[0]); a.y_sh = (int32_t)(dst.sh * c.out_mul[1]); a.y_sw = (int32_t)(dst.sw * c.out_mul[2]);
-        a.y_off = (int32_t)(dst.sd * c.out_off[0] + dst.sh * c.out_off[1] + dst.sw * c.out_off[2]);
-        a.act = act; a.slope = slope; a.accumulate = accumulate;
-        // 16-byte row-order stores need whole 8-channel groups at 16-byte-aligned pixel bases (pitches are multiples of 8 elements: cl_check_tensor)
-        static const bool no_coalesce = getenv("DCV_CL_DIRECT_EPILOGUE") != nullptr;      // A/B only
-        a.coalesce = (ocs % 8 == 0 && (reinterpret_cast<uintptr_t>(dst_p) & 15) == 0 && !no_coalesce) ? 1 : 0;
-        if (gate) {
-            if (!a.coalesce) return fail(DCV_EUNSUPPORTED, "cl conv: the gated epilogue needs the row-order store form");
-            a.gate = static_cast<const cl_h*>(gate); a.gate_slope = gate_slope;
-        }
-        a.x_bytes = (uint32_t)xb; a.y_bytes = (uint32_t)yb;
-        for (int t = 0; t < T; ++t) {
-            const int ud = t / (c.t[1].n * c.t[2].n), uh = (t / c.t[2].n) % c.t[1].n, uw = t % c.t[2].n;
-            a.toff[t] = (int32_t)(2 * ((int64_t)c.t[0].delta[ud] * src.sd + (int64_t)c.t[1].delta[uh] * src.sh + (int64_t)c.t[2].delta[uw] * src.sw));
-            a.tsel[t] = ud | (uh << 2) | (uw << 4);
-        }
-        maxtm = std::max<int64_t>(maxtm, (M64 + tc.bm - 1) / tc.bm);
-        if (++n > 4) return fail(DCV_EUNSUPPORTED, "cl conv: more than 4 position classes");
-    }
-    if (n == 0) return DCV_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (stat && which == 0 && act == DCV_ACT_NONE && !accumulate) {
-        const size_t need = (size_t)n * maxtm * OCp * 2 * sizeof(float);
-        if (need <= stat_bytes) {
-            // rows of position tiles a class does not have (classes of different sizes) must read as zero
-            DCV_HIP_CHECK(hipMemsetAsync(stat, 0, need, st));
-            for (int i = 0; i < n; ++i) { pk.c[i].stat = stat; pk.c[i].stat_row0 = (int32_t)(i * maxtm); }
-            if (nparts) *nparts = (int)(n * maxtm);
-            if (pitch) *pitch = OCp;
-        }
-    }
-#ifdef DCV_DEBUG_TIMING      // timing-experiment builds only: the shipped library cannot be told to drop its stores
-    static const int dbg = getenv("DCV_CL_DEBUG") ? atoi(getenv("DCV_CL_DEBUG")) : 0;      // 1: no epilogue stores
-#else
-    constexpr int dbg = 0;
-#endif
-    for (int i = 0; i < n; ++i) pk.c[i].pad2 = dbg;
-    ClSplitK sk = {0, 0, 0, 0};
-    if (!stat && !accumulate && !gate) sk = cl_splitk_plan(n, thin, pk.c[0].M, (int)pk.c[0].div_sp.div, OCp, pk.c[0].nsteps, tc, ocs);
-    if (sk.KS && (!ws || ws_bytes < sk.slab_bytes || (reinterpret_cast<uintptr_t>(ws) & 15))) sk.KS = 0;
-    if (sk.KS) { pk.c[0].slab = static_cast<float*>(ws); pk.c[0].ks_per = sk.ks_per; pk.c[0].slab_m = sk.slab_m; }
-    for (int i = n; i < 4; ++i) pk.c[i] = pk.c[0];
-    pk.ncls = n; pk.tiles_oc = OCp / tc.bn; pk.tiles_m = (int)maxtm;
-    dim3 grid((unsigned)((maxtm + 7) / 8 * 8 * pk.tiles_oc * n));
-    if (sk.KS) grid.y = (unsigned)sk.KS;
-    cl_launch_tile(tc, pk, thin, grid, st);
-    if (sk.KS) {
-        DCV_LAUNCH_CHECK();
-        const int64_t tot = (int64_t)pk.c[0].M * (ocs / 8);
-        hipLaunchKernelGGL(cl_splitk_reduce_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, pk.c[0], sk.KS);
-        snprintf(g_last_kernel, sizeof(g_last_kernel), "cl_gather_kernel<%d x %d tile> (1 class, split-K x %d, " CL_HALF_NAME " channels-last)", tc.bn, tc.bm, sk.KS);
-        DCV_LAUNCH_CHECK();
-        return DCV_OK;
-    }
-    snprintf(g_last_kernel, sizeof(g_last_kernel), "cl_gather_kernel<%d x %d tile%s> (%d class%s, " CL_HALF_NAME " channels-last)", tc.bn, tc.bm, thin ? ", thin" : "", n, n == 1 ? "" : "es");
-    DCV_LAUNCH_CHECK();
-    return DCV_OK;
+    rc = cl_launch(P, src_p, (which == 0) ? *xd : *yd, packed, dst_p, (which == 0) ? *yd : *xd, g, act, slope, accumulate, ws, stat, gate, gate_slope, static_cast<hipStream_t>(stream));
+    if (nparts && rc == DCV_OK) *nparts = P.nparts;
+    if (pitch && rc == DCV_OK) *pitch = P.pitch;
+    return rc;
 }
 
 int dcv_cl_conv_forward(const dcv_conv_geom* g, const void* x, const dcv_dims5* xd, const void* packed, void* y, const dcv_dims5* yd,
                         int act, float slope, void* ws, size_t ws_bytes, void* stream) {
     return cl_conv_run(0, g, x, xd, packed, y, yd, act, slope, 0, ws, ws_bytes, stream);
-}
-// bytes of the per-tile BatchNorm sums dcv_cl_conv_forward_stats leaves (0: this geometry's form does not produce them)
-size_t dcv_cl_conv_stats_bytes(const dcv_conv_geom* g, const dcv_dims5* xd, const dcv_dims5* yd) {
-    if (!g || !xd || !yd) return 0;
-    ClPlan pl;
-    if (cl_make_plan(0, g, xd, yd, &pl) != DCV_OK || cl_thin_out(pl, g)) return 0;
-    const ClTile tc = cl_pick_tile(pl.OC);
-    const int OCp = (pl.OC + tc.bn - 1) / tc.bn * tc.bn;
-    int n = 0;
-    int64_t maxtm = 0;
-    for (const ClClass& c : pl.cls) {
-        if (c.t[0].n * c.t[1].n * c.t[2].n == 0 || c.o_ext[0] <= 0 || c.o_ext[1] <= 0 || c.o_ext[2] <= 0) continue;
-        const int64_t M64 = (int64_t)yd->n * c.o_ext[0] * c.o_ext[1] * c.o_ext[2];
-        maxtm = std::max<int64_t>(maxtm, (M64 + tc.bm - 1) / tc.bm);
-        ++n;
-    }
-    return (size_t)n * maxtm * OCp * 2 * sizeof(float);
 }
 int dcv_cl_conv_forward_stats(const dcv_conv_geom* g, const void* x, const dcv_dims5* xd, const void* packed, void* y, const dcv_dims5* yd,
                               float* stat, size_t stat_bytes, int* nparts, int* pitch, void* ws, size_t ws_bytes, void* stream) {
@@ -2275,7 +2278,7 @@ int dcv_cl_conv_backward_data_gated(const dcv_conv_geom* g, const void* dy, cons
 size_t dcv_cl_wgrad_workspace_bytes(const dcv_conv_geom* g, const dcv_dims5* x, const dcv_dims5* y) {
     if (!g || !x || !y) return 0;
     ClWgradPlan p;
-    if (cl_wgrad_plan(g, g->transposed ? *x : *y, g->transposed ? *y : *x, &p) != DCV_OK) return 0;
+    if (cl_wgrad_plan(g, g->transposed ? *x : *y, g->transposed ? *y : *x, true, &p) != DCV_OK) return 0;
     return p.tab_bytes + p.slab_bytes + 512;
 }
 
@@ -2283,22 +2286,15 @@ size_t dcv_cl_wgrad_workspace_bytes(const dcv_conv_geom* g, const dcv_dims5* x, 
 static int cl_conv_backward_weight(const dcv_conv_geom* g, const void* x, const dcv_dims5* xd, const void* dy, const dcv_dims5* dyd, float* dw, int accumulate,
                                    void* ws, size_t ws_bytes, void* stream) {
     if (!g || !x || !xd || !dy || !dyd || !dw || !ws) return fail(DCV_EINVAL, "cl_conv_backward_weight: null pointer");
-    ClPlan chk;
-    int rc = cl_make_plan(0, g, xd, dyd, &chk);      // validates the geometry
+    int rc = cl_check_geom(g, xd, dyd);
     if (rc != DCV_OK) return rc;
     const dcv_dims5& D = g->transposed ? *xd : *dyd;
     const dcv_dims5& G = g->transposed ? *dyd : *xd;
     const cl_h* dp = static_cast<const cl_h*>(g->transposed ? x : dy);
     const cl_h* gp = static_cast<const cl_h*>(g->transposed ? dy : x);
-    if ((rc = cl_check_tensor(D, "cl wgrad dense operand")) != DCV_OK || (rc = cl_check_tensor(G, "cl wgrad gathered operand")) != DCV_OK) return rc;
-    int64_t dpitch = 0;
-    if (!cl_pixel_linear(D, &dpitch)) return fail(DCV_EUNSUPPORTED, "cl wgrad: the dense operand must be pixel-linear (a whole tensor or a channel slice of one)");
     ClWgradPlan p;
-    if ((rc = cl_wgrad_plan(g, D, G, &p)) != DCV_OK) return rc;
+    if ((rc = cl_wgrad_plan(g, D, G, false, &p)) != DCV_OK) return rc;
     if (ws_bytes < p.tab_bytes + p.slab_bytes) return fail(DCV_EWORKSPACE, "cl wgrad: workspace too small (%zu needed, %zu given)", p.tab_bytes + p.slab_bytes, ws_bytes);
-    const int64_t dbytes = 2 * ((p.M - 1) * dpitch + pad8(D.c)), gbytes = cl_extent_bytes(G, pad8(G.c));
-    if (dbytes >= (1ll << 31) || gbytes >= (1ll << 31)) return fail(DCV_EUNSUPPORTED, "cl wgrad: tensors beyond 2 GB");
-    if (G.w > 1 && G.sw < pad8(G.c)) return fail(DCV_EINVAL, "cl wgrad: gathered operand's pixel pitch below its padded channel count");
     hipStream_t st = static_cast<hipStream_t>(stream);
     ClPosEntry* tab = static_cast<ClPosEntry*>(ws);
     float* slab = reinterpret_cast<float*>(static_cast<char*>(ws) + p.tab_bytes);
@@ -2306,10 +2302,9 @@ static int cl_conv_backward_weight(const dcv_conv_geom* g, const void* x, const 
     // key either finds a complete table or builds its own (the loser of the insert frees its copy); a failed launch / synchronise frees the copy and leaves
     // no entry behind.  The cache is bounded (CL_TAB_CACHE_MAX keys: the three GPU configs hold ~30 each); past the bound a call builds into its workspace.
     bool build = true, keep = false;
-    static const bool no_cache = getenv("DCV_CL_NO_POSTAB_CACHE") != nullptr;
     ClTabKey key;
     memset(&key, 0, sizeof(key));
-    if (!no_cache) {
+    if (p.cache) {
         DCV_HIP_CHECK(hipGetDevice(&key.dev));
         const int32_t v[24] = {g->kd, g->kh, g->kw, g->sd, g->sh, g->sw, g->pd, g->ph, g->pw, D.n, D.d, D.h, D.w, G.d, G.h, G.w, (int32_t)G.sd, (int32_t)G.sh, (int32_t)G.sw, 0, 0, 0, 0, 0};
         memcpy(key.v, v, sizeof(v));
@@ -2355,15 +2350,14 @@ static int cl_conv_backward_weight(const dcv_conv_geom* g, const void* x, const 
         memset(&a, 0, sizeof(a));
         a.d = dp; a.g = gp; a.tab = tab; a.slab = slab;
         a.M = (int)p.M; a.chunk = p.chunk;
-        a.d_pitch2 = (int32_t)(2 * dpitch); a.d_cbytes = 2 * pad8(D.c); a.g_cbytes = 2 * pad8(G.c); a.T = p.T;
+        a.d_pitch2 = (int32_t)(2 * p.dpitch); a.d_cbytes = 2 * pad8(D.c); a.g_cbytes = 2 * pad8(G.c); a.T = p.T;
         a.tiles_d = p.tiles_d; a.gblocks = p.gblocks; a.gcb8 = p.gcb / 8; a.ntpt = p.ntpt;
-        a.d_bytes = (uint32_t)dbytes; a.g_bytes = (uint32_t)gbytes;
+        a.d_bytes = (uint32_t)p.dbytes; a.g_bytes = (uint32_t)p.gbytes;
         for (int t = 0; t < p.T; ++t) {
             const int kd = t / (g->kh * g->kw), kh = (t / g->kw) % g->kh, kw = t % g->kw;
             a.toff[t] = (int32_t)(2 * ((int64_t)kd * G.sd + (int64_t)kh * G.sh + (int64_t)kw * G.sw));
         }
-        static const bool flat = getenv("DCV_CL_WGRAD_FLAT") != nullptr;      // A/B only
-        a.tiles = p.tiles; a.S = p.S; a.xcd_map = flat ? 0 : 1; a.wtiles = p.wtiles;
+        a.tiles = p.tiles; a.S = p.S; a.xcd_map = p.xcd_map ? 1 : 0; a.wtiles = p.wtiles;
         if (p.narrow) hipLaunchKernelGGL((cl_wgrad_kernel<true>), dim3((unsigned)(p.wtiles * p.S)), dim3(256), 0, st, a);
         else hipLaunchKernelGGL((cl_wgrad_kernel<false>), dim3((unsigned)(p.wtiles * p.S)), dim3(256), 0, st, a);
         DCV_LAUNCH_CHECK();
@@ -2374,9 +2368,8 @@ static int cl_conv_backward_weight(const dcv_conv_geom* g, const void* x, const 
         a.slab = slab; a.dw = dw; a.S = p.S; a.tiles = p.tiles; a.tiles_d = p.tiles_d; a.gblocks = p.gblocks; a.gcb = p.gcb; a.ntpt = p.ntpt; a.T = p.T;
         a.DC = D.c; a.GC = G.c; a.ws_d = (int64_t)G.c * p.T; a.accumulate = accumulate ? 1 : 0;
         const int64_t tot = (int64_t)D.c * G.c * p.T;
-        static const bool old_reduce = getenv("DCV_CL_OLD_WGRAD_REDUCE") != nullptr;      // A/B only
         const int64_t nel = (int64_t)p.tiles * (128 * 128);
-        if (old_reduce) {
+        if (p.old_reduce) {
             a.lpe = (p.S >= 32 && tot * 64 < (1ll << 31)) ? 64 : 1;
             hipLaunchKernelGGL(cl_wgrad_reduce_kernel, dim3((unsigned)((tot * a.lpe + 255) / 256)), dim3(256), 0, st, a);
         } else if (p.S >= 64) {

@@ -544,3 +544,42 @@ def test_out_view_that_is_not_a_multiple_of_8_channels_must_be_trailing():
     cat = ops_cl.ConcatBuffer(2, 8, 12, (8, 8), DEV)              # ... the trailing member of a concatenation may have any width
     y = ops_cl.conv(x, w, g, out=cat.second)
     assert y.shape[1] == 12 and torch.isfinite(y.float()).all()
+
+
+def test_short_buffers_are_refused_before_any_launch_cl16():
+    """What dcv_cl_conv_workspace_bytes and dcv_cl_packed_bytes return is required.  The latent layer (Conv2d 256 -> 256, 4x4, stride 2, padding 1 on 4 x 4 planes: one
+    class, 128 K steps, 4 positions per sample) runs split-K x 8 with the query's workspace; without one it is refused — it used to run unsplit, in another summation
+    order — and so is a pack into a buffer one byte short, on the 128 -> 64 layer whose pack has the patch-staged tail: nothing launched, nothing written."""
+    import ctypes as C
+    from dcvgan_amd import native as N, ops, ops_cl
+    from dcvgan_amd.native import dims5, ptr, stream_ptr
+    L = N.lib()
+    g0 = torch.Generator().manual_seed(11)
+    x = ops_cl.from_f32(r16(torch.randn(4, 256, 4, 4, generator=g0)).to(DEV))
+    w = r16(torch.randn(256, 256, 4, 4, generator=g0) * 0.05).to(DEV)
+    geo = ops.conv_geom(w, (2, 2), (1, 1), False)
+    y = ops_cl.cl_empty((4, 256, 2, 2), DEV)
+    xd, yd = dims5(x), dims5(y)
+    pk = ops_cl._packed(w, 0, geo, xd, yd, tuple(x.shape))
+    wsp, wsn = ops._ws("clconv", L.dcv_cl_conv_workspace_bytes(C.byref(geo), C.byref(xd), C.byref(yd), 0), DEV)
+    N.check(L.dcv_cl_conv_forward(C.byref(geo), ptr(x), C.byref(xd), ptr(pk), ptr(y), C.byref(yd), 0, 0.0, wsp, wsn, stream_ptr()), "conv")
+    assert "split-K" in L.dcv_debug_last_kernel().decode(), L.dcv_debug_last_kernel()
+    torch.cuda.synchronize()
+    assert rel(y.float(), F.conv2d(ops_cl.to_f32(x).cpu(), w.cpu(), None, 2, 1)) < 5e-3
+    y.fill_(float("nan"))
+    n0 = N.launch_count()
+    assert L.dcv_cl_conv_forward(C.byref(geo), ptr(x), C.byref(xd), ptr(pk), ptr(y), C.byref(yd), 0, 0.0, wsp, 0, stream_ptr()) == N.DCV_EWORKSPACE
+    assert L.dcv_cl_conv_forward(C.byref(geo), ptr(x), C.byref(xd), ptr(pk), ptr(y), C.byref(yd), 0, 0.0, None, 0, stream_ptr()) == N.DCV_EWORKSPACE
+    torch.cuda.synchronize()
+    assert N.launch_count() == n0 and bool(torch.isnan(y.float()).all())
+    # the pack
+    wt = r16(torch.randn(128, 64, 4, 4, generator=g0) * 0.05).to(DEV)
+    gt = ops.conv_geom(wt, (2, 2), (1, 1), True)
+    xt, yt = dims5(ops_cl.cl_empty((2, 128, 16, 16), DEV)), dims5(ops_cl.cl_empty((2, 64, 32, 32), DEV))
+    nb = L.dcv_cl_packed_bytes(C.byref(gt), C.byref(xt), C.byref(yt), 0)
+    buf = torch.full((nb,), 0x5A, dtype=torch.uint8, device=DEV)
+    assert L.dcv_cl_pack_weights(C.byref(gt), C.byref(xt), C.byref(yt), 0, ptr(wt), ptr(buf), nb - 1, stream_ptr()) == N.DCV_EWORKSPACE
+    torch.cuda.synchronize()
+    assert N.launch_count() == n0 and bool((buf == 0x5A).all())
+    N.check(L.dcv_cl_pack_weights(C.byref(gt), C.byref(xt), C.byref(yt), 0, ptr(wt), ptr(buf), nb, stream_ptr()), "pack")
+    assert N.launch_count() == n0 + 2      # the tiled gather's tiles, then the patch-staged form's
