@@ -8,6 +8,8 @@
 
 namespace dcv {
 
+extern thread_local char g_last_kernel[160];   // dcv_debug_last_kernel's text (conv_mfma.hip)
+
 struct RowView {
     int64_t sn, sc, sd, sh, sw;
 };
@@ -699,6 +701,69 @@ __global__ __launch_bounds__(SMALL_NT) void bn_bwd_small_kernel(ChanMap m, const
 static bool bn_small_ok(const RowMap& m, const ChanMap& cm) {
     static const bool off = getenv("DCV_NO_BN_SMALL") != nullptr;
     return !off && m.vec == 4 && m.inner != 1 && cm.per_chan <= (int64_t)SMALL_NT * SMALL_K && cm.per_chan >= 64 && m.C >= 32 && m.groups < (1ll << 28);
+}
+
+// ------------------------------------------------------------------------- //
+// Synchronised BatchNorm (data parallel, fp32 path).  The statistics and the backward's two sums cover the batch of ALL ranks: each rank
+// leaves its own fp64 sums in a "row" of 2C + 1 doubles ({s0[c]}, {s1[c]}, count), the rows of all ranks are exchanged by the caller
+// (one collective per BatchNorm group and pass), and every rank then adds the same table in rank order — the same bits everywhere.
+// The passes over the tensors are the kernels above (bn_stats_kernel, bn_bwd_reduce_*, BnApply, BnBwdApply); only these folds are new.
+// ------------------------------------------------------------------------- //
+// row = the channel's `split` partials added in index order (bn_finalize_kernel's / bn_bwd_finalize_kernel's order), and the count
+__global__ void bn_sync_fold_kernel(const double* __restrict__ partial, int C, int split, double count, double* __restrict__ row) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c == 0) row[2 * (int64_t)C] = count;
+    if (c >= C) return;
+    double s0 = 0, s1 = 0;
+    for (int k = 0; k < split; ++k) { s0 += partial[((int64_t)c * split + k) * 2]; s1 += partial[((int64_t)c * split + k) * 2 + 1]; }
+    row[c] = s0;
+    row[C + c] = s1;
+}
+
+// row from the conv epilogue's per-tile fp32 sums stat[part][pitch][2], added in bn_partials_finalize_kernel's order (one block per channel)
+__global__ __launch_bounds__(256) void bn_sync_partials_kernel(const float* __restrict__ stat, int nparts, int pitch, int C, double count, double* __restrict__ row) {
+    __shared__ double red[8];
+    const int c = blockIdx.x;
+    double acc[2] = {0.0, 0.0};
+    for (int p = threadIdx.x; p < nparts; p += 256) {
+        const float2 v = *reinterpret_cast<const float2*>(stat + ((int64_t)p * pitch + c) * 2);
+        acc[0] += (double)v.x;
+        acc[1] += (double)v.y;
+    }
+    block_sum<2>(acc, red);
+    if (threadIdx.x == 0) {
+        if (c == 0) row[2 * (int64_t)C] = count;
+        row[c] = acc[0];
+        row[C + c] = acc[1];
+    }
+}
+
+// rows[world][2C + 1] -> the statistics of the whole batch: sums and counts added in rank order, then bn_finalize_channel with the global count
+__global__ void bn_sync_finalize_kernel(const double* __restrict__ rows, int world, int C, float eps, float momentum,
+                                        float* __restrict__ save_mean, float* __restrict__ save_invstd,
+                                        float* __restrict__ running_mean, float* __restrict__ running_var, int64_t* __restrict__ nbt) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c == 0 && nbt) *nbt += 1;
+    if (c >= C) return;
+    const int64_t len = 2 * (int64_t)C + 1;
+    double s0 = 0, s1 = 0, count = 0;
+    for (int r = 0; r < world; ++r) { s0 += rows[r * len + c]; s1 += rows[r * len + C + c]; count += rows[r * len + 2 * C]; }
+    bn_finalize_channel(c, s0, s1, count, eps, momentum, save_mean, save_invstd, running_mean, running_var);
+}
+
+// backward: dbeta / dgamma = this rank's own sums (the gradient bucket adds the ranks later); coef[c] = {sum dz, sum dz * xhat} over ALL rows in
+// rank order / the global count, for BnBwdApply
+__global__ void bn_sync_bwd_coef_kernel(const double* __restrict__ rows, int world, int rank, int C,
+                                        float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ coef) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const int64_t len = 2 * (int64_t)C + 1;
+    double s0 = 0, s1 = 0, count = 0;
+    for (int r = 0; r < world; ++r) { s0 += rows[r * len + c]; s1 += rows[r * len + C + c]; count += rows[r * len + 2 * C]; }
+    dbeta[c] = (float)rows[rank * len + c];
+    dgamma[c] = (float)rows[rank * len + C + c];
+    coef[2 * c] = (float)(s0 / count);
+    coef[2 * c + 1] = (float)(s1 / count);
 }
 
 // ------------------------------------------------------------------------- //
@@ -1442,6 +1507,97 @@ int dcv_bn_act_backward(const float* dy, const dcv_dims5* dyd, const float* x, c
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, s, partial, C, cm.split, count, dgamma, dbeta, coef);
     DCV_LAUNCH_CHECK();
     BnBwdApply f{dy, x, dx, rv(*dyd), rv(*xd), rv(*dxd), gamma, beta, save_mean, save_invstd, mask, coef, act, slope, training};
+    return launch_ew(m, f, s);
+}
+
+// ---- synchronised BatchNorm: see the kernels' comment.  Every argument and workspace check comes before the first launch. ----
+size_t dcv_bn_sync_row_doubles(int channels) { return channels > 0 ? 2 * (size_t)channels + 1 : 0; }
+
+int dcv_bn_sync_sums(const float* x, const dcv_dims5* xd, const float* stat, int nparts, int pitch, double* row, void* ws, size_t ws_bytes, void* stream) {
+    if (!x || !xd || !row || xd->c < 1 || numel(*xd) < 1 || (stat && (nparts < 1 || pitch < xd->c))) return fail(DCV_EINVAL, "bn_sync_sums: bad arguments");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int C = xd->c;
+    const double count = (double)xd->n * xd->d * xd->h * xd->w;
+    if (stat) {
+        hipLaunchKernelGGL(bn_sync_partials_kernel, dim3(C), dim3(256), 0, s, stat, nparts, pitch, C, count, row);
+        DCV_LAUNCH_CHECK();
+        snprintf(g_last_kernel, sizeof(g_last_kernel), "bn_sync_partials_kernel (%d conv-epilogue partials per channel -> rank row)", nparts);
+        return DCV_OK;
+    }
+    if (ws_bytes < dcv_bn_workspace_bytes(C) || !ws) return fail(DCV_EWORKSPACE, "bn_sync_sums: workspace too small");
+    const dcv_dims5* views[1] = {xd};
+    const void* ptrs[1] = {x};
+    RowMap m = make_rowmap(*xd, views, 1, ptrs);
+    if (m.groups >= (1ll << 32)) return fail(DCV_EUNSUPPORTED, "bn: tensor too large");
+    ChanMap cm = make_chanmap(m);
+    double* partial = static_cast<double*>(ws);
+    if (m.vec == 4) hipLaunchKernelGGL((bn_stats_kernel<4>), dim3(C * cm.split), dim3(256), 0, s, cm, x, rv(*xd), partial);
+    else hipLaunchKernelGGL((bn_stats_kernel<1>), dim3(C * cm.split), dim3(256), 0, s, cm, x, rv(*xd), partial);
+    DCV_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bn_sync_fold_kernel, dim3((C + 255) / 256), dim3(256), 0, s, partial, C, cm.split, count, row);
+    DCV_LAUNCH_CHECK();
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "bn_stats_kernel<%d> x %d blocks per channel + bn_sync_fold_kernel (rank row)", m.vec, cm.split);
+    return DCV_OK;
+}
+
+int dcv_bn_sync_finalize(const double* rows, int world, int channels, float eps, float momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                         float* save_mean, float* save_invstd, void* stream) {
+    if (!rows || world < 1 || channels < 1 || !save_mean || !save_invstd || (!running_mean) != (!running_var)) return fail(DCV_EINVAL, "bn_sync_finalize: bad arguments");
+    hipLaunchKernelGGL(bn_sync_finalize_kernel, dim3((channels + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), rows, world, channels, eps, momentum,
+                       save_mean, save_invstd, running_mean, running_var, num_batches_tracked);
+    DCV_LAUNCH_CHECK();
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "bn_sync_finalize_kernel (%d rank rows in rank order)", world);
+    return DCV_OK;
+}
+
+int dcv_bn_sync_backward_sums(const float* dy, const dcv_dims5* dyd, const float* x, const dcv_dims5* xd, const float* gamma, const float* beta,
+                              const float* save_mean, const float* save_invstd, const float* mask, int act, float slope, double* row,
+                              void* ws, size_t ws_bytes, void* stream) {
+    if (!dy || !dyd || !x || !xd || !gamma || !beta || !save_mean || !save_invstd || !row || !same_shape(*dyd, *xd) || numel(*xd) < 1)
+        return fail(DCV_EINVAL, "bn_sync_backward_sums: bad arguments");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int C = xd->c;
+    if (ws_bytes < dcv_bn_workspace_bytes(C) || !ws) return fail(DCV_EWORKSPACE, "bn_sync_backward_sums: workspace too small");
+    const dcv_dims5* views[2] = {dyd, xd};
+    const void* ptrs[2] = {dy, x};
+    RowMap m = make_rowmap(*xd, views, 2, ptrs);
+    if (m.groups >= (1ll << 32)) return fail(DCV_EUNSUPPORTED, "bn: tensor too large");
+    ChanMap cm = make_chanmap(m);
+    double* partial = static_cast<double*>(ws);
+    const bool rows_kernel = m.vec == 4 && m.inner != 1 && m.gpr % 256 == 0 && !ew_rows_off();
+    if (rows_kernel)
+        hipLaunchKernelGGL(bn_bwd_reduce_rows_kernel, dim3(C * cm.split), dim3(256), 0, s, cm, dy, rv(*dyd), x, rv(*xd), gamma, beta, save_mean, save_invstd, mask, act, slope, partial);
+    else if (m.vec == 4)
+        hipLaunchKernelGGL((bn_bwd_reduce_kernel<4>), dim3(C * cm.split), dim3(256), 0, s, cm, dy, rv(*dyd), x, rv(*xd), gamma, beta, save_mean, save_invstd, mask, act, slope, partial);
+    else
+        hipLaunchKernelGGL((bn_bwd_reduce_kernel<1>), dim3(C * cm.split), dim3(256), 0, s, cm, dy, rv(*dyd), x, rv(*xd), gamma, beta, save_mean, save_invstd, mask, act, slope, partial);
+    DCV_LAUNCH_CHECK();
+    const double count = (double)xd->n * xd->d * xd->h * xd->w;
+    hipLaunchKernelGGL(bn_sync_fold_kernel, dim3((C + 255) / 256), dim3(256), 0, s, partial, C, cm.split, count, row);
+    DCV_LAUNCH_CHECK();
+    if (rows_kernel) snprintf(g_last_kernel, sizeof(g_last_kernel), "bn_bwd_reduce_rows_kernel x %d blocks per channel + bn_sync_fold_kernel (rank row)", cm.split);
+    else snprintf(g_last_kernel, sizeof(g_last_kernel), "bn_bwd_reduce_kernel<%d> x %d blocks per channel + bn_sync_fold_kernel (rank row)", m.vec, cm.split);
+    return DCV_OK;
+}
+
+int dcv_bn_sync_backward_apply(const float* dy, const dcv_dims5* dyd, const float* x, const dcv_dims5* xd, float* dx, const dcv_dims5* dxd,
+                               const float* gamma, const float* beta, const float* save_mean, const float* save_invstd, const float* mask, int act, float slope,
+                               const double* rows, int world, int rank, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream) {
+    if (!dy || !dyd || !x || !xd || !dx || !dxd || !gamma || !beta || !save_mean || !save_invstd || !rows || world < 1 || rank < 0 || rank >= world || !dgamma || !dbeta
+        || !same_shape(*dyd, *xd) || !same_shape(*dyd, *dxd) || numel(*xd) < 1)
+        return fail(DCV_EINVAL, "bn_sync_backward_apply: bad arguments");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int C = xd->c;
+    if (ws_bytes < dcv_bn_workspace_bytes(C) || !ws) return fail(DCV_EWORKSPACE, "bn_sync_backward_apply: workspace too small");
+    const dcv_dims5* views[3] = {dyd, xd, dxd};
+    const void* ptrs[3] = {dy, x, dx};
+    RowMap m = make_rowmap(*xd, views, 3, ptrs);
+    if (m.groups >= (1ll << 32)) return fail(DCV_EUNSUPPORTED, "bn: tensor too large");
+    float* coef = reinterpret_cast<float*>(static_cast<char*>(ws) + (size_t)(2048 + C) * 2 * sizeof(double) * 2);      // where dcv_bn_act_backward keeps it
+    hipLaunchKernelGGL(bn_sync_bwd_coef_kernel, dim3((C + 255) / 256), dim3(256), 0, s, rows, world, rank, C, dgamma, dbeta, coef);
+    DCV_LAUNCH_CHECK();
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "bn_sync_bwd_coef_kernel (%d rank rows, own row %d) + BnBwdApply", world, rank);
+    BnBwdApply f{dy, x, dx, rv(*dyd), rv(*xd), rv(*dxd), gamma, beta, save_mean, save_invstd, mask, coef, act, slope, 1};
     return launch_ew(m, f, s);
 }
 

@@ -63,6 +63,13 @@ def batch_norm(bn, x, rng, act=(ops.ACT_NONE, 0.0), dropout=None, out=None, part
     mask = None
     if dropout is not None and dropout.training:
         mask = rng.dropout2d_mask(x.shape[0], x.shape[1], dropout.p, x.device)
+    sync = bn.__dict__.get("_dcv_sync_bn")     # optim.sync_batchnorm's mark (a plain attribute: an unmarked module pays this lookup and nothing else)
+    if sync is not None and training and sync.active:
+        if ops_cl.is_cl(x):
+            raise ops.N.NativeError("synchronised BatchNorm (optim.sync_batchnorm) is fp32-path only: this module received a 16-bit channels-last tensor")
+        return ops.sync_bn_act(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, True, act[0], act[1], mask,
+                               bn.momentum if bn.momentum is not None else 0.1, bn.eps, out=out, partials=partials, num_batches_tracked=bn.num_batches_tracked,
+                               link=link, group=sync)
     if ops_cl.is_cl(x):     # bf16 channels-last data path (ops_cl): statistics from its own pass over the bf16 tensor
         return ops_cl.bn_act(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, act[0], act[1], mask,
                              bn.momentum if bn.momentum is not None else 0.1, bn.eps, out=out, num_batches_tracked=bn.num_batches_tracked if training else None,

@@ -15,7 +15,7 @@ from torch.autograd import Function
 from . import native as N
 from .native import ACT_LEAKY, ACT_NONE, ACT_TANH, ConvGeom, check, dims5, lib, ptr, stream_ptr
 
-__all__ = ["invalidate_packed_weights", "conv", "bn_act", "act", "noise_add", "cat_channels", "temporal_diff", "gan_loss", "gru_sequence",
+__all__ = ["invalidate_packed_weights", "conv", "bn_act", "sync_bn_act", "act", "noise_add", "cat_channels", "temporal_diff", "gan_loss", "gru_sequence",
            "normal", "dropout2d_mask", "conv_geom", "ACT_NONE", "ACT_LEAKY", "ACT_TANH"]
 
 
@@ -610,6 +610,74 @@ def bn_act(x, gamma, beta, running_mean, running_var, training: bool, act: int =
         raise N.NativeError("bn_act: num_batches_tracked must be an int64 device tensor")
     return _BnAct.apply(x, gamma, beta, running_mean, running_var, mask, training, float(momentum), float(eps), act, float(slope),
                         None if out is None else _Out(out), None if partials is None else _Opaque(partials), num_batches_tracked, link)
+
+
+class _SyncBnAct(Function):
+    """Training-mode BatchNorm group over the batch of ALL ranks of `group` (optim.SyncBnGroup): each pass leaves this rank's fp64 sums in its row of a zeroed
+    (world, 2C + 1) table, one collective fills in the other ranks' rows, and every rank then adds the same table in rank order (include/dcvgan_hip.h)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, mask, training: bool, momentum: float, eps: float, act: int, slope: float, out=None,
+                partials=None, nbt=None, link=None, group=None):
+        N._require(x, "bn input")
+        L = lib()
+        Cn = x.shape[1]
+        if link is not None:
+            # dcv_conv_backward_data_bn would reduce over the local batch only, and a deferred output would be normalised by the head: the head takes its unfused route
+            link.deferred, link.x = False, None
+        y = _dest(out, x.shape, x.device)
+        stats = _empty((2, Cn), x.device)
+        xd, yd = dims5(x), dims5(y)
+        wsp, wsn = _ws("bn", L.dcv_bn_workspace_bytes(Cn), x.device)
+        rows = group.table(Cn, x.device)
+        stat, nparts, pitch = partials.v if partials is not None else (None, 0, 0)
+        check(L.dcv_bn_sync_sums(ptr(x), C.byref(xd), ptr(stat), nparts, pitch, ptr(rows[group.rank]), wsp, wsn, stream_ptr()), "dcv_bn_sync_sums")
+        group.exchange(rows)
+        check(L.dcv_bn_sync_finalize(ptr(rows), group.world, Cn, eps, momentum, ptr(running_mean), ptr(running_var), ptr(nbt), ptr(stats[0]), ptr(stats[1]), stream_ptr()),
+              "dcv_bn_sync_finalize")
+        check(L.dcv_bn_apply(ptr(x), C.byref(xd), ptr(y), C.byref(yd), ptr(gamma), ptr(beta), ptr(stats[0]), ptr(stats[1]), ptr(mask), act, slope, stream_ptr()), "dcv_bn_apply")
+        ctx.cfg = (act, slope, group)
+        ctx.save_for_backward(x, gamma, beta, stats, mask)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma, beta, stats, mask = ctx.saved_tensors
+        act, slope, group = ctx.cfg
+        L = lib()
+        dy = _dense(dy)
+        Cn = x.shape[1]
+        dx = _empty(x.shape, x.device)
+        dgb = _empty((2, Cn), x.device)
+        dyd, xd, dxd = dims5(dy), dims5(x), dims5(dx)
+        wsp, wsn = _ws("bn", L.dcv_bn_workspace_bytes(Cn), x.device)
+        rows = group.table(Cn, x.device)
+        check(L.dcv_bn_sync_backward_sums(ptr(dy), C.byref(dyd), ptr(x), C.byref(xd), ptr(gamma), ptr(beta), ptr(stats[0]), ptr(stats[1]), ptr(mask), act, slope,
+                                          ptr(rows[group.rank]), wsp, wsn, stream_ptr()), "dcv_bn_sync_backward_sums")
+        group.exchange(rows)
+        check(L.dcv_bn_sync_backward_apply(ptr(dy), C.byref(dyd), ptr(x), C.byref(xd), ptr(dx), C.byref(dxd), ptr(gamma), ptr(beta), ptr(stats[0]), ptr(stats[1]), ptr(mask),
+                                           act, slope, ptr(rows), group.world, group.rank, ptr(dgb[0]), ptr(dgb[1]), wsp, wsn, stream_ptr()), "dcv_bn_sync_backward_apply")
+        if _OWN_ACCUMULATION:
+            return (dx, deliver_small(gamma, dgb[0]), deliver_small(beta, dgb[1])) + (None,) * 13
+        return (dx, dgb[0], dgb[1]) + (None,) * 13
+
+
+def sync_bn_act(x, gamma, beta, running_mean, running_var, training: bool, act: int = ACT_NONE, slope: float = 0.0,
+                mask: Optional[torch.Tensor] = None, momentum: float = 0.1, eps: float = 1e-5, out=None, partials=None, num_batches_tracked=None, link=None, group=None):
+    """bn_act with the batch statistics — and the backward's two sums — taken over the batch of every rank of `group` (an optim.SyncBnGroup): the numerics of one
+    process that runs the concatenated batch.  fp32 path; eval mode has nothing to exchange and is bn_act itself.  dgamma / dbeta are this rank's own sums (the
+    gradient bucket adds the ranks); a `link` is left empty, so the linked convolution runs unfused."""
+    if group is None:
+        raise N.NativeError("sync_bn_act: group= (an optim.SyncBnGroup) is required")
+    if not training:
+        return bn_act(x, gamma, beta, running_mean, running_var, training, act, slope, mask, momentum, eps, out=out, partials=partials,
+                      num_batches_tracked=num_batches_tracked, link=link)
+    if x.dtype != torch.float32:
+        raise N.NativeError(f"sync_bn_act: synchronised BatchNorm is fp32-path only, got {x.dtype}")
+    if num_batches_tracked is not None and (num_batches_tracked.dtype != torch.int64 or not num_batches_tracked.is_cuda):
+        raise N.NativeError("sync_bn_act: num_batches_tracked must be an int64 device tensor")
+    return _SyncBnAct.apply(x, gamma, beta, running_mean, running_var, mask, training, float(momentum), float(eps), act, float(slope),
+                            None if out is None else _Out(out), None if partials is None else _Opaque(partials), num_batches_tracked, link, group)
 
 
 # --------------------------------------------------------------------------- #

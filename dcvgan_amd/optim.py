@@ -514,3 +514,89 @@ def broadcast_buffers(module: torch.nn.Module, src: int = 0, group=None):
     with torch.no_grad():
         for b in module.buffers():
             dist.broadcast(b.data, src, group=group)
+
+
+# --------------------------------------------------------------------------- #
+# Synchronised BatchNorm (fp32 path)
+# --------------------------------------------------------------------------- #
+class SyncBnGroup:
+    """The handle a marked BatchNorm module carries (`sync_batchnorm`): the ranks whose batches one BatchNorm group normalises together, and the exchange of their sums.
+
+    One collective per BatchNorm group and pass: an all-reduce(SUM) of a zeroed (world, 2C + 1) fp64 table in which this rank has filled only its own row.  Adding
+    zeros is exact, so this is an all-gather that gloo (on device tensors) and RCCL both have, and its result is the same table on every rank.  It is issued on the
+    current stream, without a host read.  The process group is the handle's own (`dist.new_group`): these collectives never share a communicator with a gradient
+    bucket's, plain or overlapped.  Every rank must run the same BatchNorm groups in the same host order — they do: every rank runs the same graph.
+    `force`: run the sync kernels in a world of one too (no collective): the cost tool and single-process tests."""
+
+    def __init__(self, ranks=None, force: bool = False, timeout=None):
+        import torch.distributed as dist
+        self.dist, self.force = dist, bool(force)
+        self.pg, self.world, self.rank = None, 1, 0
+        ranks = None if ranks is None else sorted(int(r) for r in ranks)
+        if dist.is_initialized() and dist.get_world_size() > 1 and (ranks is None or len(ranks) > 1):
+            ranks = ranks if ranks is not None else list(range(dist.get_world_size()))
+            # (every rank of the default group has to make this call, members or not: torch.distributed's rule for new_group)
+            self.pg = dist.new_group(ranks=ranks, **({"timeout": timeout} if timeout is not None else {}))
+            if dist.get_rank() in ranks:
+                self.world, self.rank = len(ranks), ranks.index(dist.get_rank())
+            else:
+                self.pg = None
+        self.collectives = 0      # counter for tests / tools
+
+    @property
+    def active(self) -> bool:
+        return self.world > 1 or self.force
+
+    def table(self, channels: int, device) -> torch.Tensor:
+        n = 2 * int(channels) + 1
+        if self.world == 1:
+            return torch.empty((1, n), dtype=torch.float64, device=device)      # the one row is written whole
+        return torch.zeros((self.world, n), dtype=torch.float64, device=device)
+
+    def exchange(self, rows: torch.Tensor) -> None:
+        if self.world == 1:
+            return
+        self.dist.all_reduce(rows, op=self.dist.ReduceOp.SUM, group=self.pg)
+        self.collectives += 1
+
+    def __deepcopy__(self, memo):
+        return self      # copies of a marked module (an EMA twin) exchange with the same ranks
+
+
+def _batchnorms(module_or_models):
+    mods = module_or_models.values() if isinstance(module_or_models, dict) else \
+        [module_or_models] if isinstance(module_or_models, torch.nn.Module) else list(module_or_models)
+    seen = set()
+    for m in mods:
+        for sub in m.modules():
+            if isinstance(sub, (torch.nn.BatchNorm2d, torch.nn.BatchNorm3d)) and id(sub) not in seen:
+                seen.add(id(sub))
+                yield sub
+
+
+def sync_batchnorm(module_or_models, group=None, force: bool = False) -> SyncBnGroup:
+    """Mark every BatchNorm2d / BatchNorm3d of a module (or of a dict / sequence of modules) for synchronised statistics: in training mode, with more than one rank
+    (or `force`), its statistics and its backward's reduction sums cover the batch of all ranks of `group` — the numerics of one process on the concatenated batch
+    (DESIGN §7a).  fp32 path only.  `group`: None (all ranks), a sequence of global ranks, or a SyncBnGroup made earlier (to share one communicator between calls).
+    Collective: every rank must call this (it makes a process group).  Returns the handle; `unsync_batchnorm` removes the marks."""
+    handle = group if isinstance(group, SyncBnGroup) else SyncBnGroup(group, force=force)
+    if isinstance(group, SyncBnGroup) and force:
+        handle.force = True
+    for bn in _batchnorms(module_or_models):
+        bn._dcv_sync_bn = handle
+    return handle
+
+
+def unsync_batchnorm(module_or_models) -> None:
+    """The inverse of `sync_batchnorm`: every BatchNorm of the module(s) keeps its statistics local again."""
+    for bn in _batchnorms(module_or_models):
+        bn.__dict__.pop("_dcv_sync_bn", None)
+
+
+def sync_bn_group_of(module_or_models) -> Optional[SyncBnGroup]:
+    """The handle of the first marked BatchNorm of the module(s), or None when nothing is marked."""
+    for bn in _batchnorms(module_or_models):
+        h = bn.__dict__.get("_dcv_sync_bn")
+        if h is not None:
+            return h
+    return None

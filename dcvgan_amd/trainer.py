@@ -28,8 +28,10 @@ from .configs import StepConfig
 MODEL_NAMES = ("ggen", "cgen", "idis", "vdis", "gdis")
 
 
-def build_models(cfg: StepConfig, device=None) -> Dict[str, torch.nn.Module]:
-    """train.py:117-165: positional constructor wiring + init_weights."""
+def build_models(cfg: StepConfig, device=None, sync_bn: bool = False) -> Dict[str, torch.nn.Module]:
+    """train.py:117-165: positional constructor wiring + init_weights.
+    `sync_bn` (data parallel, fp32 path; default off): every BatchNorm of the five models takes its statistics over the batch of all ranks
+    (optim.sync_batchnorm; a collective call, every rank makes it).  optim.sync_bn_group_of(models) returns the handle afterwards."""
     w = cfg.width
     ggen = G.GeometricVideoGenerator(cfg.dim_z_content, cfg.dim_z_motion, cfg.channel, cfg.geometric_info, w["ggen"], cfg.video_length)
     cgen = G.ColorVideoGenerator(ggen.channel, cfg.dim_z_color, cfg.geometric_info, w["cgen"], cfg.video_length)
@@ -40,6 +42,8 @@ def build_models(cfg: StepConfig, device=None) -> Dict[str, torch.nn.Module]:
     for m in models.values():
         m.apply(util.init_weights)
         m.to(device if device is not None else util.current_device())
+    if sync_bn:
+        optim.sync_batchnorm(models)
     return models
 
 

@@ -209,6 +209,31 @@ int dcv_bn_act_backward(const float* dy, const dcv_dims5* dyd, const float* x, c
                         const float* mask, int training, int act, float slope,
                         float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- synchronised BatchNorm (data parallel; fp32 path; added symbols only: the ABI version stays 4) ----
+ * Training-mode BatchNorm whose statistics and backward sums cover the batch of ALL ranks.  A "row" is 2*C + 1 doubles: {s0[c]}, {s1[c]}, count.
+ * Each rank writes its own row, the caller exchanges them into the table rows = double[world][2*C + 1] in device memory (one collective per BatchNorm
+ * group and pass, e.g. an all-reduce(SUM) of a zeroed table in which each rank filled its own row), and every rank then adds the same table in rank
+ * order in fp64: identical bits on every rank.  Forward:  sync_sums -> exchange -> sync_finalize -> dcv_bn_apply.
+ *                                              Backward: sync_backward_sums -> exchange -> sync_backward_apply.
+ * ws: dcv_bn_workspace_bytes(C).  Checks as in the entries above: DCV_EINVAL, DCV_EWORKSPACE before any launch, DCV_EUNSUPPORTED beyond 2^32 groups.
+ *  - sync_sums: sum x, sum x^2 and the element count of this rank's x.  stat == NULL: its own pass over x (the `split` partials of a channel are added in
+ *    index order); otherwise the producing convolution's epilogue partials (dcv_conv_forward_stats), added as dcv_bn_act_forward_stats adds them (ws unused).
+ *  - sync_finalize: per channel, the rows' sums and counts added in rank order, then save_mean / save_invstd, the running statistics (unbiased variance
+ *    with the GLOBAL count; may both be NULL) and num_batches_tracked += 1 (may be NULL) exactly as dcv_bn_act_forward leaves them.
+ *  - sync_backward_sums: sum dz, sum dz * xhat (dz = dy * act'(z) * mask) and the count of this rank.
+ *  - sync_backward_apply: dgamma / dbeta = this rank's OWN sums rows[rank] (a gradient all-reduce adds the ranks later, as for every other parameter);
+ *    dx = gamma * invstd * (dz - S0 / N - xhat * S1 / N) with S and N summed over all rows in rank order. */
+size_t dcv_bn_sync_row_doubles(int channels);
+int dcv_bn_sync_sums(const float* x, const dcv_dims5* xd, const float* stat, int nparts, int pitch, double* row, void* ws, size_t ws_bytes, void* stream);
+int dcv_bn_sync_finalize(const double* rows, int world, int channels, float eps, float momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                         float* save_mean, float* save_invstd, void* stream);
+int dcv_bn_sync_backward_sums(const float* dy, const dcv_dims5* dyd, const float* x, const dcv_dims5* xd, const float* gamma, const float* beta,
+                              const float* save_mean, const float* save_invstd, const float* mask, int act, float slope, double* row,
+                              void* ws, size_t ws_bytes, void* stream);
+int dcv_bn_sync_backward_apply(const float* dy, const dcv_dims5* dyd, const float* x, const dcv_dims5* xd, float* dx, const dcv_dims5* dxd,
+                               const float* gamma, const float* beta, const float* save_mean, const float* save_invstd, const float* mask, int act, float slope,
+                               const double* rows, int world, int rank, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- elementwise --------------------------------------------------------- */
 /* y = act(x)  /  dx = dy * act'(.) evaluated from the OUTPUT y
  * (nn.LeakyReLU generator.py:175, discriminator.py:84,90,186; nn.Tanh generator.py:78,276) */
