@@ -989,6 +989,92 @@ __global__ __launch_bounds__(256) void adam_multi_guarded_kernel(const AdamPack 
 }
 
 // ------------------------------------------------------------------------- //
+// EMA of model weights (the sampling twin): e += w (p - e), count, warm-up and skip decided on the device
+// ------------------------------------------------------------------------- //
+// ema_prepare_kernel (one thread, like guard_adam_prepare_kernel) reads the guard's decision; unless the update is skipped it takes the number of updates applied
+// so far from the block, forms the weight 1 - d_t in double, rounds it once and advances the count.  ema_multi_kernel has adam_multi_kernel's block mapping; a
+// tensor is either averaged (fp32) or copied dword for dword (BatchNorm running statistics, num_batches_tracked).  No atomics: the same inputs give the same bits.
+struct EmaBlock {      // 16 x 4 bytes, caller-owned (DCV_EMA_BLOCK_BYTES); [0] is the number of updates applied, which a host may read back
+    int32_t count, skip;
+    float w;
+    int32_t pad[13];
+};
+static_assert(sizeof(EmaBlock) == 64, "EmaBlock is the 64-byte block the header documents");
+struct EmaPack {
+    float* e[ADAM_MT];
+    const float* s[ADAM_MT];
+    int64_t n[ADAM_MT];
+    int32_t first_block[ADAM_MT + 1];
+    uint32_t copy_mask;      // bit t: tensor t is copied (mode 1), not averaged
+};
+__global__ void ema_prepare_kernel(EmaBlock* __restrict__ b, const float* __restrict__ state, double decay, int warmup) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int skip = state != nullptr && state[DCV_GUARD_SKIPPED] != 0.f;
+    b->skip = skip;
+    if (skip) return;
+    const int t = b->count;
+    const double d = warmup ? fmin(decay, (1.0 + (double)t) / (10.0 + (double)t)) : decay;
+    b->w = (float)(1.0 - d);
+    b->count = t + 1;
+}
+__device__ __forceinline__ float ema_one(float e, float p, float w) { return fmaf(w, p - e, e); }
+__global__ __launch_bounds__(256) void ema_multi_kernel(const EmaPack k, int nt, const EmaBlock* __restrict__ b) {
+    if (b->skip) return;      // before any access to a tensor
+    const float w = b->w;
+    int t = 0;
+    while (t + 1 < nt && (int)blockIdx.x >= k.first_block[t + 1]) ++t;
+    const int64_t base = (int64_t)((int)blockIdx.x - k.first_block[t]) * 4096;
+    float* __restrict__ e = k.e[t];
+    const float* __restrict__ s = k.s[t];
+    const int64_t n = k.n[t];
+    const bool vec = ((reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(s)) & 15) == 0;      // both bases (hence every block's first element) on 16-byte boundaries
+    if ((k.copy_mask >> t) & 1u) {      // bit patterns, no arithmetic
+        uint32_t* __restrict__ eu = reinterpret_cast<uint32_t*>(e);
+        const uint32_t* __restrict__ su = reinterpret_cast<const uint32_t*>(s);
+        if (vec) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int64_t i = base + (int64_t)(q * 256 + threadIdx.x) * 4;
+                if (i + 4 <= n) {
+                    *reinterpret_cast<uint4*>(eu + i) = *reinterpret_cast<const uint4*>(su + i);
+                } else {
+                    for (int64_t j = i; j < n; ++j) eu[j] = su[j];      // the tensor's last 1..3 dwords
+                }
+            }
+        } else {
+#pragma unroll 4
+            for (int q = 0; q < 16; ++q) {
+                const int64_t i = base + q * 256 + threadIdx.x;
+                if (i >= n) break;
+                eu[i] = su[i];
+            }
+        }
+        return;
+    }
+    if (vec) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t i = base + (int64_t)(q * 256 + threadIdx.x) * 4;
+            if (i + 4 <= n) {
+                const float4 p = *reinterpret_cast<const float4*>(s + i);
+                float4 x = *reinterpret_cast<const float4*>(e + i);
+                x.x = ema_one(x.x, p.x, w); x.y = ema_one(x.y, p.y, w); x.z = ema_one(x.z, p.z, w); x.w = ema_one(x.w, p.w, w);
+                *reinterpret_cast<float4*>(e + i) = x;
+            } else {
+                for (int64_t j = i; j < n; ++j) e[j] = ema_one(e[j], s[j], w);      // the tensor's last 1..3 elements
+            }
+        }
+    } else {
+#pragma unroll 4
+        for (int q = 0; q < 16; ++q) {
+            const int64_t i = base + q * 256 + threadIdx.x;
+            if (i >= n) break;
+            e[i] = ema_one(e[i], s[i], w);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------- //
 // GRU recurrence (dm <= 32): one 64-lane block per sample, lane u < dm owns unit u
 // ------------------------------------------------------------------------- //
 #define GRU_MAXD 32
@@ -1738,6 +1824,42 @@ int dcv_adam_step_multi_guarded(int n_tensors, float* const* p, const float* con
         k.first_block[nt] = blocks;
         if (blocks == 0) continue;
         hipLaunchKernelGGL(adam_multi_guarded_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, b);
+        DCV_LAUNCH_CHECK();
+    }
+    return DCV_OK;
+}
+
+int dcv_ema_update_multi(int n_tensors, float* const* ema, const float* const* src, const int64_t* numel, const int32_t* mode,
+                         double decay, int warmup, int32_t* ema_block, const float* guard_state, void* stream) {
+    if (n_tensors < 0 || (n_tensors > 0 && (!ema || !src || !numel || !mode)) || !(decay >= 0.0 && decay < 1.0) || !ema_block)
+        return fail(DCV_EINVAL, "ema_update_multi: bad arguments");
+    for (int t0 = 0; t0 < n_tensors; t0 += ADAM_MT) {      // every check before any launch
+        int64_t blocks = 0;
+        for (int t = t0; t < std::min(n_tensors, t0 + ADAM_MT); ++t) {
+            if (numel[t] < 0 || (numel[t] > 0 && (!ema[t] || !src[t]))) return fail(DCV_EINVAL, "ema_update_multi: null tensor or negative numel");
+            if (mode[t] != 0 && mode[t] != 1) return fail(DCV_EINVAL, "ema_update_multi: mode must be 0 (average) or 1 (copy)");
+            blocks += (numel[t] + 4095) / 4096;
+        }
+        if (blocks > INT32_MAX) return fail(DCV_EINVAL, "ema_update_multi: too many elements");
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    EmaBlock* b = reinterpret_cast<EmaBlock*>(ema_block);
+    hipLaunchKernelGGL(ema_prepare_kernel, dim3(1), dim3(1), 0, s, b, guard_state, decay, warmup ? 1 : 0);
+    DCV_LAUNCH_CHECK();
+    for (int t0 = 0; t0 < n_tensors; t0 += ADAM_MT) {
+        EmaPack k;
+        memset(&k, 0, sizeof(k));
+        const int nt = std::min(ADAM_MT, n_tensors - t0);
+        int blocks = 0;
+        for (int t = 0; t < nt; ++t) {
+            k.e[t] = ema[t0 + t]; k.s[t] = src[t0 + t]; k.n[t] = numel[t0 + t];
+            if (mode[t0 + t]) k.copy_mask |= 1u << t;
+            k.first_block[t] = blocks;
+            blocks += (int)((numel[t0 + t] + 4095) / 4096);
+        }
+        k.first_block[nt] = blocks;
+        if (blocks == 0) continue;
+        hipLaunchKernelGGL(ema_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, b);
         DCV_LAUNCH_CHECK();
     }
     return DCV_OK;

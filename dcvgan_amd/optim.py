@@ -220,6 +220,143 @@ class Adam:
             torch.autograd.graph.increment_version(touched)
 
 
+class ModelEma:
+    """Exponential moving averages of the generators' weights — the twins a GAN is sampled and evaluated from — kept on the device.
+
+        ema = ModelEma(models, names=("ggen", "cgen"), decay=0.999, warmup=True, guard=opt_ggen.guard)
+        ema.update()                         # once per iteration in which the generators were stepped, after their last step
+        sampling.generate_samples(ema.module("ggen"), ema.module("cgen"), ...)
+
+    A twin is a deep copy of the live model (same class, same ``state_dict`` keys, its own storage), in eval mode, without gradients; the twins share one random
+    stream (``ema.rng``) that is not the live models'.
+    ``update()`` is one dcv_ema_update_multi call per model on the current stream: parameters e += (1 - d_t)(p - e) with d_t = min(decay, (1 + t) / (10 + t)) under
+    ``warmup`` (t = updates applied so far, counted on the device), buffers (BatchNorm running statistics, num_batches_tracked) copied bit for bit.  With a
+    ``guard`` the update applies — or skips on — the guard's last measurement, like the optimiser steps on it: a skipped update changes no tensor and no count.
+    Nothing here reads a value on the host, runs a torch kernel or allocates in the steady state.  GPU only: ``update()`` on CPU models, non-fp32 or
+    non-contiguous parameters raises ``NativeError`` before any launch."""
+
+    def __init__(self, models, names=("ggen", "cgen"), decay: float = 0.999, warmup: bool = True, guard: Optional[GradGuard] = None):
+        if not 0.0 <= float(decay) < 1.0:
+            raise ValueError(f"ModelEma: decay must be in [0, 1), got {decay!r}")
+        self.names = tuple(names)
+        if not self.names:
+            raise ValueError("ModelEma: no model names")
+        self.decay, self.warmup, self.guard = float(decay), bool(warmup), guard
+        from .rng import PhiloxRng
+        self.live = {n: models[n] for n in self.names}
+        # ONE random stream for all twins, apart from the live models': a PhiloxRng is (seed, counter), so two of them would hand two twins the same values, and the
+        # colour twin's latent would repeat the geometry twin's.  On one stream the twins' draws interleave, as the live models' do on rng.default_rng().
+        self.rng = PhiloxRng()
+        self.twins = {n: self._twin(m, self.rng) for n, m in self.live.items()}
+        # (twin tensor, live tensor) in state_dict order, parameters first
+        self._pairs = {}
+        for n, m in self.live.items():
+            tp, tb = dict(self.twins[n].named_parameters()), dict(self.twins[n].named_buffers())
+            self._pairs[n] = [(tp[k], p) for k, p in m.named_parameters()] + [(tb[k], b) for k, b in m.named_buffers()]
+        self._n_params = {n: sum(1 for _ in m.parameters()) for n, m in self.live.items()}
+        self._tables = {}
+        dev = next(self.live[self.names[0]].parameters()).device
+        # per model: DCV_EMA_BLOCK_BYTES beside the models; word 0 is the number of updates applied (host tensor -> device copies, once: no kernel).  Host models get
+        # a host block: update() refuses them, but a checkpoint's count still loads and reads back.
+        self._blocks = {n: torch.zeros(16, dtype=torch.int32).to(dev) for n in self.names}
+
+    @staticmethod
+    def _twin(model: torch.nn.Module, twin_rng) -> torch.nn.Module:
+        import copy
+        rng = model.__dict__.pop("_rng", None)      # the live model's random source is not copied: the twins draw from the ModelEma's own stream
+        try:
+            twin = copy.deepcopy(model)
+        finally:
+            model.__dict__["_rng"] = rng
+        twin._rng = twin_rng
+        for t in list(twin.parameters()) + list(twin.buffers()):      # nothing cached for the live tensors (packed weights, bucket slices) may follow the copy
+            for k in [k for k in t.__dict__ if k.startswith("_dcv_")]:
+                del t.__dict__[k]
+        for p in twin.parameters():
+            p.requires_grad_(False)
+        return twin.eval()
+
+    def module(self, name: str) -> torch.nn.Module:
+        return self.twins[name]
+
+    def _table(self, name: str):
+        pairs = self._pairs[name]
+        key = tuple(t.data_ptr() for pair in pairs for t in pair)
+        tab = self._tables.get(name)
+        if tab is not None and tab[0] == key:
+            return tab
+        es, ss, ns, ms = [], [], [], []
+        for i, (e, s) in enumerate(pairs):
+            what = f"ModelEma({name}) " + ("parameter" if i < self._n_params[name] else "buffer")
+            for t in (e, s):
+                if not t.is_cuda:
+                    raise NativeError(f"{what}: expected a HIP device tensor, got {t.device} — the EMA runs on the GPU only (there is no CPU fallback)")
+                if t.device.index != torch.cuda.current_device():
+                    raise NativeError(f"{what}: tensor is on {t.device} but the current device is cuda:{torch.cuda.current_device()}")
+                if not t.is_contiguous():
+                    raise NativeError(f"{what}: tensors must be contiguous")
+            if e.dtype != s.dtype or e.shape != s.shape:
+                raise NativeError(f"{what}: the twin holds {e.dtype}{tuple(e.shape)}, the live model {s.dtype}{tuple(s.shape)}")
+            if i < self._n_params[name]:
+                if s.dtype != torch.float32:
+                    raise NativeError(f"{what}: expected float32, got {s.dtype}")
+                mode, dwords = 0, s.numel()
+            else:
+                if s.element_size() % 4:
+                    raise NativeError(f"{what}: buffers are copied as 32-bit words, got {s.dtype}")
+                mode, dwords = 1, s.numel() * (s.element_size() // 4)
+            if dwords == 0:
+                continue
+            es.append(e.data_ptr()); ss.append(s.data_ptr()); ns.append(dwords); ms.append(mode)
+        n = len(es)
+        tab = self._tables[name] = (key, n, (C.c_void_p * max(n, 1))(*es), (C.c_void_p * max(n, 1))(*ss), (C.c_int64 * max(n, 1))(*ns), (C.c_int32 * max(n, 1))(*ms),
+                                    [e for e, _ in pairs])
+        return tab
+
+    @torch.no_grad()
+    def update(self):
+        tabs = [self._table(n) for n in self.names]      # every refusal before the first launch
+        state = ptr(self.guard._need_state()) if self.guard is not None else None
+        L = lib()
+        st = stream_ptr()
+        for name, (_, n, es, ss, ns, ms, touched) in zip(self.names, tabs):
+            check(L.dcv_ema_update_multi(n, es, ss, ns, ms, self.decay, int(self.warmup), ptr(self._blocks[name]), state, st), "dcv_ema_update_multi")
+            # the kernels wrote through raw pointers: the twin's packed-weight caches are keyed on the version counter, as in Adam.step (harmless after a skipped update)
+            torch.autograd.graph.increment_version(touched)
+
+    def num_updates(self) -> int:
+        """Updates applied so far (a host read of the device count: on request only)."""
+        counts = {int(b[0].item()) for b in self._blocks.values()}
+        if len(counts) > 1:
+            raise NativeError(f"ModelEma: the models' update counts differ ({sorted(counts)})")
+        return counts.pop() if counts else 0
+
+    def _set_count(self, count: int):
+        for b in self._blocks.values():
+            b.copy_(torch.tensor([int(count)] + [0] * 15, dtype=torch.int32))
+
+    def state_dict(self):
+        """Per model an ordinary checkpoint of the twin (reference format), plus the count and the rule."""
+        sd = {n: self.twins[n].state_dict() for n in self.names}
+        sd.update(num_updates=self.num_updates(), decay=self.decay, warmup=self.warmup)
+        return sd
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        for n in self.names:
+            self.twins[n].load_state_dict(sd[n])
+        self.decay, self.warmup = float(sd["decay"]), bool(sd["warmup"])
+        self._set_count(sd["num_updates"])
+
+    @torch.no_grad()
+    def reset(self):
+        """twins := live models, count := 0."""
+        for pairs in self._pairs.values():
+            for e, s in pairs:
+                e.copy_(s)
+        self._set_count(0)
+
+
 def _copy_into(slot: torch.Tensor, g: torch.Tensor) -> None:
     """slot <- g with the library's strided copy (dcv_axpby) on the device; torch's copy on the host (gloo rehearsals)."""
     if slot.is_cuda and g.dtype == torch.float32 and g.dim() in (2, 4, 5):

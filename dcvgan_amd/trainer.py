@@ -70,6 +70,12 @@ def build_optimizers(cfg: StepConfig, models, data_parallel: bool = False, overl
     return opts
 
 
+def build_ema(cfg: StepConfig, models, optimizers, decay: float = 0.999, warmup: bool = True) -> "optim.ModelEma":
+    """The sampling twins of the two generators (optim.ModelEma), wired to the G phase's guard when build_optimizers made one: the three G steps and the EMA
+    update then share one measurement and are all applied or all skipped.  Hand it to StepRunner(..., ema=...)."""
+    return optim.ModelEma(models, names=("ggen", "cgen"), decay=decay, warmup=warmup, guard=getattr(optimizers["ggen"], "guard", None))
+
+
 class StepRunner:
     """`elide_dead_backward=True` builds the D-phase fakes without a tape (they are detached): the
     reference backpropagates `loss_dis` through cgen/ggen too (trainer.py:304-319, fakes not detached)
@@ -78,8 +84,9 @@ class StepRunner:
     "minimal" column).  Default False = the reference's as-written schedule."""
 
     def __init__(self, cfg: StepConfig, models, optimizers, loss, sync_losses: bool = False, elide_dead_backward: bool = False,
-                 side_streams: Optional[bool] = None):
+                 side_streams: Optional[bool] = None, ema: Optional["optim.ModelEma"] = None):
         self.cfg, self.models, self.opt, self.loss = cfg, models, optimizers, loss
+        self.ema = ema      # optim.ModelEma (build_ema): updated once per iteration whose G phase stepped, after its three steps; None leaves the iteration as it is
         self.iteration = 0
         self.sync_losses = sync_losses
         self.elide_dead_backward = elide_dead_backward
@@ -225,6 +232,8 @@ class StepRunner:
             if guard_gen is not None:
                 guard_gen.measure()
             o["ggen"].step(); o["cgen"].step(); o["ggen"].step()  # ggen twice — trainer.py:357-359
+            if self.ema is not None:
+                self.ema.update()      # once per iteration, not per step: both generators get the same averaging horizon
             self._mark("G: Adam")
         else:
             loss_gen.detach_()

@@ -63,7 +63,7 @@ typedef struct dcv_conv_geom {
 } dcv_conv_geom;
 
 const char* dcv_last_error(void);
-/* ABI version.  Still 4: dcv_grad_guard_workspace_bytes, dcv_grad_guard_measure and dcv_adam_step_multi_guarded were added without changing any struct or existing entry.  4 (round 6): dcv_scale_dev, dcv_conv_backward_data_bn(_workspace_bytes), dcv_conv_forward_bn, dcv_conv_backward_weight_bn, dcv_bn_forward_stats_only, dcv_bn_apply exist (no struct changed).  3 (round 5): dcv_conv_backward_weight_acc / dcv_cl_conv_backward_weight_acc, dcv_cl_conv_backward_data_gated, dcv_clf16_*, dcv_normal_fill_many exist (no struct changed).
+/* ABI version.  Still 4: dcv_ema_update_multi was added without changing any struct or existing entry; likewise dcv_grad_guard_workspace_bytes, dcv_grad_guard_measure and dcv_adam_step_multi_guarded were added without changing any struct or existing entry.  4 (round 6): dcv_scale_dev, dcv_conv_backward_data_bn(_workspace_bytes), dcv_conv_forward_bn, dcv_conv_backward_weight_bn, dcv_bn_forward_stats_only, dcv_bn_apply exist (no struct changed).  3 (round 5): dcv_conv_backward_weight_acc / dcv_cl_conv_backward_weight_acc, dcv_cl_conv_backward_data_gated, dcv_clf16_*, dcv_normal_fill_many exist (no struct changed).
  * 2 (round 4): dcv_conv_geom has the 13th field `mfma`, dcv_wpack the 4th field `precision`, dcv_abi_struct_sizes exists.
  * A host compares dcv_version() and dcv_abi_struct_sizes() with its own declarations BEFORE the first call that passes a struct
  * (dcvgan_amd/native.py does, and refuses to load on a mismatch): the library cannot see the size of what a pointer points to. */
@@ -352,6 +352,18 @@ int dcv_grad_guard_measure(int n_tensors, const float* const* g, const int64_t* 
 #define DCV_ADAM_STEP_BLOCK_BYTES 64
 int dcv_adam_step_multi_guarded(int n_tensors, float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* numel,
                                 double lr, double beta1, double beta2, double eps, double weight_decay, int32_t* step_block, const float* state, void* stream);
+
+/* ---- EMA of model weights (the twin a GAN is sampled from): count, warm-up and skip decided on the device ------ *
+ * One update of n_tensors tensors: ema[t] += w (src[t] - ema[t]) as ONE fmaf(w, src - ema, ema) per element, with w = (float)(1 - d),
+ * d = warmup ? min(decay, (1 + t) / (10 + t)) : decay in double, t = the number of updates applied so far.  `ema_block` is DCV_EMA_BLOCK_BYTES of device memory,
+ * zeroed by the caller once: ema_block[0] is that number (a host may read it back); the rest is scratch of the call (skip flag, w).
+ * A one-thread kernel reads guard_state[DCV_GUARD_SKIPPED] (NULL: never skipped); unless set it forms w and increments ema_block[0]; the update kernels read them.
+ * A skipped update touches no ema tensor and no count.  16-byte loads and stores where both bases of a tensor are 16-byte aligned, single elements otherwise.
+ * No atomics (bitwise repeatable).  decay in [0, 1); numel 0 is allowed (nothing is launched for it, its pointers are not looked at).  1 + ceil(n_tensors / 24) launches. */
+#define DCV_EMA_BLOCK_BYTES 64
+/* mode[t]: 0 = average (fp32), 1 = copy dwords (buffers; an int64 tensor is passed as 2 * numel dwords) */
+int dcv_ema_update_multi(int n_tensors, float* const* ema, const float* const* src, const int64_t* numel, const int32_t* mode,
+                         double decay, int warmup, int32_t* ema_block, const float* guard_state /* may be NULL */, void* stream);
 
 /* ---- bf16 channels-last ("CL16") data path -------------------------------------------------- *
  * BASELINE.json configs[2] ("surreal-depth1, bf16 MFMA") and configs[4] ("fp16 MFMA") name 16-bit variants of the same step
