@@ -388,6 +388,12 @@ int dcv_cl_conv_forward(const dcv_conv_geom* g, const void* x, const dcv_dims5* 
 size_t dcv_cl_conv_stats_bytes(const dcv_conv_geom* g, const dcv_dims5* x, const dcv_dims5* y);
 int dcv_cl_conv_forward_stats(const dcv_conv_geom* g, const void* x, const dcv_dims5* xd, const void* packed, void* y, const dcv_dims5* yd,
                               float* stat, size_t stat_bytes, int* nparts, int* pitch, void* ws, size_t ws_bytes, void* stream);
+/* Rounding: every 16-bit value a convolution stores is ONE round-to-nearest-even of its fp32 accumulator (after the fused activation).  accumulate = 1 on the
+ * tiled gather form (cl_gather_kernel with the row-order store, the form every thick layer takes) adds the old dx to that STORED rounding and rounds the sum again,
+ * dx = rne16(rne16(conv^T(dy, w)) + dx_old) — bit for bit what storing the gradient and adding the two 16-bit tensors (dcv_cl_elementwise kind 1) gives, and up to one
+ * 16-bit ulp from rne16(conv^T + dx_old) where both roundings land on ties; the gate of dcv_cl_conv_backward_data_gated multiplies that sum before the last rounding.
+ * The thin-destination form (1x1 GEMM + cl_col2im_kernel) and the gather's direct 8-byte store form (a destination that is no whole 8-channel group) add dx_old in
+ * fp32 and round once.  tests/test_conv_exact_gpu.py holds each form to its definition bit for bit. */
 int dcv_cl_conv_backward_data(const dcv_conv_geom* g, const void* dy, const dcv_dims5* dyd, const void* packed, void* dx, const dcv_dims5* dxd,
                               int accumulate, void* ws, size_t ws_bytes, void* stream);
 /* backward_data + the (Leaky)ReLU derivative of the layer that produced this convolution's input, read off that input `xg` (dx's shape and strides), in one epilogue

@@ -3,6 +3,8 @@ MFMA variants — the reference itself is fp32-only, so this is a throughput mod
 Tensors, weights, BatchNorm statistics and optimiser state stay fp32; only the MFMA fragments are rounded to bf16
 (8 significant bits, RNE), products are exact and accumulated in fp32.  Expected relative L2 error of a convolution:
 ~2^-8 / sqrt(3) * sqrt(2) = 3e-3 (two rounded operands); asserted < 1e-2 — and > 2e-4, which proves the bf16 kernels ran."""
+import zlib
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -45,7 +47,7 @@ def test_conv_bf16_products(bf16, case):
     from dcvgan_amd import native, ops
     dev = bf16
     name, tr, nd, cin, cout, k, s, p, sp, n = case
-    g = torch.Generator().manual_seed(hash(name) % 10000)
+    g = torch.Generator().manual_seed(zlib.crc32(name.encode()) % 10000)
     s_t = (s,) * nd if isinstance(s, int) else s
     p_t = (p,) * nd if isinstance(p, int) else p
     w = (torch.randn(((cin, cout) if tr else (cout, cin)) + (k,) * nd, generator=g) * 0.2).requires_grad_(True)
@@ -161,7 +163,7 @@ def test_conv_f32x6(f32x6, case):
     from dcvgan_amd import native, ops
     dev = f32x6
     name, tr, nd, cin, cout, k, s, p, sp, n = case
-    g = torch.Generator().manual_seed(hash(name) % 10000)
+    g = torch.Generator().manual_seed(zlib.crc32(name.encode()) % 10000)
     s_t = (s,) * nd if isinstance(s, int) else s
     p_t = (p,) * nd if isinstance(p, int) else p
     w = (torch.randn(((cin, cout) if tr else (cout, cin)) + (k,) * nd, generator=g) * 0.2).requires_grad_(True)

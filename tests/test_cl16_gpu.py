@@ -4,6 +4,8 @@
 Operands are rounded to bf16 first and the SAME rounded values go through torch's fp32 CPU ops, so what is measured is the kernels' own arithmetic: fp32
 accumulation of exact bf16 products, then one rounding of the result to bf16 (relative 2^-9 per element: ~2.3e-3 relative L2) for activations and data
 gradients — asserted < 5e-3 — and NO rounding for weight gradients (fp32 out): asserted < 2e-5.  Every case also runs inside NaN guard bands."""
+import zlib
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -79,7 +81,7 @@ def test_conv_cl16(case):
     from dcvgan_amd import native, ops, ops_cl
     native.lib()
     name, tr, nd, cin, cout, k, s, p, sp, n = case
-    g = torch.Generator().manual_seed(hash(name) % 10000)
+    g = torch.Generator().manual_seed(zlib.crc32(name.encode()) % 10000)
     s_t = (s,) * nd if isinstance(s, int) else s
     p_t = (p,) * nd if isinstance(p, int) else p
     w = r16(torch.randn(((cin, cout) if tr else (cout, cin)) + (k,) * nd, generator=g) * 0.1).requires_grad_(True)

@@ -1,6 +1,8 @@
 """GPU: every HIP op against the plain PyTorch fp32 CPU op it replaces (the arithmetic
 the reference delegates to torch.nn).  Tolerance: 1e-3 relative (BASELINE.json
 north_star), in practice ~1e-6."""
+import zlib
+
 import numpy as np
 import pytest
 import torch
@@ -74,7 +76,7 @@ CONVS = [
 def test_conv_fwd_bwd(dev, case, strided):
     from dcvgan_amd import ops
     name, tr, nd, cin, cout, k, s, p, sp, n = case
-    g = torch.Generator().manual_seed(hash(name) % 10000)
+    g = torch.Generator().manual_seed(zlib.crc32(name.encode()) % 10000)
     s_t = (s,) * nd if isinstance(s, int) else s
     p_t = (p,) * nd if isinstance(p, int) else p
     wshape = ((cin, cout) if tr else (cout, cin)) + (k,) * nd
@@ -120,7 +122,7 @@ def test_conv_backward_data_accumulates_into_a_slice(dev, case):
     from dcvgan_amd import native as N, ops
     from dcvgan_amd.native import dims5, ptr, stream_ptr
     name, tr, nd, cin, cout, k, s, p, sp, n = case
-    g = torch.Generator().manual_seed(hash(name) % 1000 + 7)
+    g = torch.Generator().manual_seed(zlib.crc32(name.encode()) % 1000 + 7)
     s_t = (s,) * nd if isinstance(s, int) else s
     p_t = (p,) * nd if isinstance(p, int) else p
     w = torch.randn(((cin, cout) if tr else (cout, cin)) + (k,) * nd, generator=g) * 0.2
