@@ -5,6 +5,7 @@
 // not contiguous fall back to rows of one element.
 #include "dcv_common.h"
 #include <algorithm>
+#include <vector>
 
 namespace dcv {
 
@@ -1075,6 +1076,315 @@ __global__ __launch_bounds__(256) void ema_multi_kernel(const EmaPack k, int nt,
 }
 
 // ------------------------------------------------------------------------- //
+// Spectral normalisation of the discriminators' weights: power iteration, sigma, W_sn = W / sigma, and the gradient's projection
+// ------------------------------------------------------------------------- //
+// A weight is a matrix of M rows (cout) and K columns, contiguous.  Per table of up to ADAM_MT tensors:
+//   sn_cols_kernel   t = W^T u      one block per SN_KC columns of a tensor; leaves t and the block's sum of t^2 (double) in the workspace
+//   sn_rows_kernel   s = W v        one block per SN_MR rows (one wave each); v = t / max(|t|, eps); leaves s and the block's sum of s^2
+//   sn_scale_kernel  u = s / max(|s|, eps); sigma = u^T s; W_sn = W / max(sigma, eps)     adam_multi_kernel's block mapping over the M K elements
+// Every block that needs a norm adds the tensor's block partials itself, all in the same fixed order (so all of them get the same bits), and one thread forms the
+// square root and the reciprocal in double.  Products and a thread's running sums are fp32, everything above a thread is double.  No atomics.
+// The first block of a tensor writes the vector (v, u, sigma) that its kernel has just normalised.
+#define SN_KC 256      // columns per block of sn_cols_kernel (64 groups of 4 columns x 4 row phases)
+#define SN_MR 4        // rows per block of sn_rows_kernel (one per wave)
+struct SnPack {
+    const float* w[ADAM_MT];
+    float* w_sn[ADAM_MT];      // (project: const in effect)
+    float* u[ADAM_MT];
+    float* v[ADAM_MT];
+    float* sigma[ADAM_MT];
+    float* g[ADAM_MT];         // project only
+    int32_t rows[ADAM_MT], cols[ADAM_MT];
+    int32_t first_block[ADAM_MT + 1];
+    int64_t ws_off[ADAM_MT];   // the tensor's part of the workspace, in doubles: [partials of t | partials of s or of <G, W_sn> | t (floats) | s (floats)]
+};
+__host__ __device__ __forceinline__ int sn_kchunks(int K) { return (K + SN_KC - 1) / SN_KC; }
+__host__ __device__ __forceinline__ int sn_mchunks(int M) { return (M + SN_MR - 1) / SN_MR; }
+__host__ __device__ __forceinline__ int64_t sn_eblocks(int M, int K) { return ((int64_t)M * K + 4095) / 4096; }
+// One tensor's workspace part, every array starting on a 16-byte boundary (counts in doubles, each rounded up to even; the part itself starts on an even offset of
+// a 256-byte aligned buffer).  The second partial array serves the update's s (mchunks) and the projection's inner product (eblocks).
+__host__ __device__ __forceinline__ int64_t sn_even(int64_t n) { return (n + 1) / 2 * 2; }
+__host__ __device__ __forceinline__ int64_t sn_second(int M, int K) { return sn_even(sn_mchunks(M) > sn_eblocks(M, K) ? sn_mchunks(M) : sn_eblocks(M, K)); }
+__host__ __device__ __forceinline__ int64_t sn_ws_doubles(int M, int K) {
+    return sn_even(sn_kchunks(K)) + sn_second(M, K) + sn_even(((int64_t)K + 1) / 2) + sn_even(((int64_t)M + 1) / 2);
+}
+struct SnWs {
+    double* part_t; double* part_s; float* t; float* s;
+};
+__device__ __forceinline__ SnWs sn_ws(double* ws, const SnPack& k, int ti) {
+    const int M = k.rows[ti], K = k.cols[ti];
+    SnWs r;
+    r.part_t = ws + k.ws_off[ti];
+    r.part_s = r.part_t + sn_even(sn_kchunks(K));
+    double* t = r.part_s + sn_second(M, K);
+    r.t = reinterpret_cast<float*>(t);
+    r.s = reinterpret_cast<float*>(t + sn_even(((int64_t)K + 1) / 2));
+    return r;
+}
+// sum of n doubles in a fixed order, the same in every block that asks; every thread gets it
+__device__ __forceinline__ double sn_sum_partials(const double* __restrict__ p, int64_t n, double* red) {
+    double acc[1] = {0.0};
+    for (int64_t i = threadIdx.x; i < n; i += 256) acc[0] += p[i];
+    block_sum<1>(acc, red);
+    __syncthreads();      // red is reused by the caller
+    return acc[0];
+}
+// 1 / max(sqrt(ss), eps), formed by one thread in double (correctly rounded sqrt, one division), rounded to fp32 once
+__device__ __forceinline__ float sn_inv_norm(double ss, double eps, float* slot) {
+    if (threadIdx.x == 0) *slot = (float)(1.0 / fmax(sqrt(ss), eps));
+    __syncthreads();
+    return *slot;
+}
+__device__ __forceinline__ int sn_tensor_of_block(const SnPack& k, int nt) {
+    int t = 0;
+    while (t + 1 < nt && (int)blockIdx.x >= k.first_block[t + 1]) ++t;
+    return t;
+}
+
+__global__ void sn_prepare_kernel(int32_t* __restrict__ skip, const float* __restrict__ state) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    *skip = state[DCV_GUARD_SKIPPED] != 0.f;
+}
+
+// t = W^T u.  from_s: u is s / max(|s|, eps) of the previous sn_rows_kernel (this kernel's first block of the tensor then stores it), else the stored u.
+__global__ __launch_bounds__(256) void sn_cols_kernel(const SnPack k, int nt, int from_s, double eps, double* __restrict__ ws, const int32_t* __restrict__ skip) {
+    if (skip != nullptr && *skip) return;
+    __shared__ double red[8];
+    __shared__ float inv_slot;
+    __shared__ float part[4][SN_KC];
+    const int ti = sn_tensor_of_block(k, nt);
+    const int chunk = (int)blockIdx.x - k.first_block[ti];
+    const int M = k.rows[ti], K = k.cols[ti];
+    const float* __restrict__ w = k.w[ti];
+    const SnWs a = sn_ws(ws, k, ti);
+    float inv = 1.f;
+    const float* __restrict__ usrc = k.u[ti];
+    if (from_s) {
+        inv = sn_inv_norm(sn_sum_partials(a.part_s, sn_mchunks(M), red), eps, &inv_slot);
+        usrc = a.s;
+        if (chunk == 0)
+            for (int m = threadIdx.x; m < M; m += 256) k.u[ti][m] = a.s[m] * inv;
+    }
+    const int cg = threadIdx.x & 63, rp = threadIdx.x >> 6;
+    const int col = chunk * SN_KC + cg * 4;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    if (((reinterpret_cast<uintptr_t>(w) & 15) == 0) && (K & 3) == 0) {      // base and row pitch on 16-byte boundaries: one 16-byte load per row
+        if (col < K)
+            for (int m = rp; m < M; m += 4) {
+                const float um = usrc[m] * inv;
+                const float4 x = *reinterpret_cast<const float4*>(w + (int64_t)m * K + col);
+                acc[0] += x.x * um; acc[1] += x.y * um; acc[2] += x.z * um; acc[3] += x.w * um;
+            }
+    } else {
+        for (int m = rp; m < M; m += 4) {
+            const float um = usrc[m] * inv;
+            const float* __restrict__ row = w + (int64_t)m * K;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (col + j < K) acc[j] += row[col + j] * um;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) part[rp][cg * 4 + j] = acc[j];
+    __syncthreads();
+    const int c = chunk * SN_KC + threadIdx.x;
+    float tv = 0.f;
+    if (c < K) {
+        tv = ((part[0][threadIdx.x] + part[1][threadIdx.x]) + part[2][threadIdx.x]) + part[3][threadIdx.x];
+        a.t[c] = tv;
+    }
+    double ss[1] = {(double)tv * (double)tv};
+    block_sum<1>(ss, red);
+    if (threadIdx.x == 0) a.part_t[chunk] = ss[0];
+}
+
+// s = W v.  from_t: v is t / max(|t|, eps) of the previous sn_cols_kernel (this kernel's first block of the tensor then stores it), else the stored v.
+__global__ __launch_bounds__(256) void sn_rows_kernel(const SnPack k, int nt, int from_t, double eps, double* __restrict__ ws, const int32_t* __restrict__ skip) {
+    if (skip != nullptr && *skip) return;
+    __shared__ double red[8];
+    __shared__ float inv_slot;
+    __shared__ float srow[SN_MR];
+    const int ti = sn_tensor_of_block(k, nt);
+    const int chunk = (int)blockIdx.x - k.first_block[ti];
+    const int M = k.rows[ti], K = k.cols[ti];
+    const float* __restrict__ w = k.w[ti];
+    const SnWs a = sn_ws(ws, k, ti);
+    float inv = 1.f;
+    const float* __restrict__ vsrc = k.v[ti];
+    if (from_t) {
+        inv = sn_inv_norm(sn_sum_partials(a.part_t, sn_kchunks(K), red), eps, &inv_slot);
+        vsrc = a.t;
+        if (chunk == 0)
+            for (int c = threadIdx.x; c < K; c += 256) k.v[ti][c] = a.t[c] * inv;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int m = chunk * SN_MR + wave;
+    float acc = 0.f;
+    if (m < M) {
+        const float* __restrict__ row = w + (int64_t)m * K;
+        if (((reinterpret_cast<uintptr_t>(w) & 15) == 0) && (K & 3) == 0 && ((reinterpret_cast<uintptr_t>(vsrc) & 15) == 0)) {
+            for (int c = lane * 4; c < K; c += 256) {
+                const float4 x = *reinterpret_cast<const float4*>(row + c);
+                const float4 y = *reinterpret_cast<const float4*>(vsrc + c);
+                acc += x.x * (y.x * inv); acc += x.y * (y.y * inv); acc += x.z * (y.z * inv); acc += x.w * (y.w * inv);
+            }
+        } else {      // the same elements per lane in the same order, one at a time: the bits do not depend on the alignment
+            for (int c = lane * 4; c < K; c += 256)
+                for (int j = 0; j < 4 && c + j < K; ++j) acc += row[c + j] * (vsrc[c + j] * inv);
+        }
+    }
+    const double tot = wave_sum((double)acc);      // lanes' fp32 sums combined in double, fixed order
+    if (lane == 0) {
+        const float sv = (m < M) ? (float)tot : 0.f;
+        srow[wave] = sv;
+        if (m < M) a.s[m] = sv;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double ss = 0.0;
+#pragma unroll
+        for (int j = 0; j < SN_MR; ++j) ss += (double)srow[j] * (double)srow[j];
+        a.part_s[chunk] = ss;
+    }
+}
+
+// sigma = u^T s with u = s / max(|s|, eps) (from_s) or the stored u; W_sn = W * (float)(1 / max(sigma, eps))
+__global__ __launch_bounds__(256) void sn_scale_kernel(const SnPack k, int nt, int from_s, double eps, double* __restrict__ ws, const int32_t* __restrict__ skip) {
+    if (skip != nullptr && *skip) return;
+    __shared__ double red[8];
+    __shared__ float inv_slot, sig_slot;
+    const int ti = sn_tensor_of_block(k, nt);
+    const int blk = (int)blockIdx.x - k.first_block[ti];
+    const int M = k.rows[ti], K = k.cols[ti];
+    const SnWs a = sn_ws(ws, k, ti);
+    float inv = 1.f;
+    const float* __restrict__ usrc = k.u[ti];
+    if (from_s) {
+        inv = sn_inv_norm(sn_sum_partials(a.part_s, sn_mchunks(M), red), eps, &inv_slot);
+        usrc = a.s;
+    }
+    double dot[1] = {0.0};
+    for (int m = threadIdx.x; m < M; m += 256) dot[0] += (double)(usrc[m] * inv) * (double)a.s[m];
+    block_sum<1>(dot, red);
+    if (threadIdx.x == 0) {
+        const float sg = (float)dot[0];
+        sig_slot = sg;
+        inv_slot = (float)(1.0 / fmax((double)sg, eps));
+    }
+    __syncthreads();
+    const float isg = inv_slot;
+    if (blk == 0) {
+        if (from_s)
+            for (int m = threadIdx.x; m < M; m += 256) k.u[ti][m] = a.s[m] * inv;
+        if (threadIdx.x == 0) k.sigma[ti][0] = sig_slot;
+    }
+    const float* __restrict__ w = k.w[ti];
+    float* __restrict__ o = k.w_sn[ti];
+    const int64_t n = (int64_t)M * K, base = (int64_t)blk * 4096;
+    if (((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(o)) & 15) == 0) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t i = base + (int64_t)(q * 256 + threadIdx.x) * 4;
+            if (i + 4 <= n) {
+                float4 x = *reinterpret_cast<const float4*>(w + i);
+                x.x *= isg; x.y *= isg; x.z *= isg; x.w *= isg;
+                *reinterpret_cast<float4*>(o + i) = x;
+            } else {
+                for (int64_t j = i; j < n; ++j) o[j] = w[j] * isg;      // the tensor's last 1..3 elements
+            }
+        }
+    } else {
+#pragma unroll 4
+        for (int q = 0; q < 16; ++q) {
+            const int64_t i = base + q * 256 + threadIdx.x;
+            if (i >= n) break;
+            o[i] = w[i] * isg;
+        }
+    }
+}
+
+// The projection of a gradient G = dL/dW_sn onto the raw weight: dW = (G - <G, W_sn> u v^T) / max(sigma, eps), in place on G.
+// sn_inner_kernel: per 4096-element block the partial <G, W_sn> (a thread's 16 products in fp32, double above); sn_project_kernel: every block adds its tensor's
+// partials in the same order, one thread rounds the inner product and 1 / sigma to fp32, then g <- fmaf(-(c u_m), v_k, g) * (1 / sigma).
+__global__ __launch_bounds__(256) void sn_inner_kernel(const SnPack k, int nt, double* __restrict__ ws) {
+    __shared__ double red[8];
+    const int ti = sn_tensor_of_block(k, nt);
+    const int blk = (int)blockIdx.x - k.first_block[ti];
+    const float* __restrict__ g = k.g[ti];
+    const float* __restrict__ y = k.w_sn[ti];
+    const int64_t n = (int64_t)k.rows[ti] * k.cols[ti], base = (int64_t)blk * 4096;
+    float acc = 0.f;
+    if (((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(y)) & 15) == 0) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t i = base + (int64_t)(q * 256 + threadIdx.x) * 4;
+            if (i + 4 <= n) {
+                const float4 a = *reinterpret_cast<const float4*>(g + i);
+                const float4 b = *reinterpret_cast<const float4*>(y + i);
+                acc += a.x * b.x; acc += a.y * b.y; acc += a.z * b.z; acc += a.w * b.w;
+            } else {
+                for (int64_t j = i; j < n; ++j) acc += g[j] * y[j];
+            }
+        }
+    } else {      // the same elements per thread in the same order, one at a time: the bits do not depend on the alignment
+        for (int q = 0; q < 4; ++q) {
+            const int64_t i = base + (int64_t)(q * 256 + threadIdx.x) * 4;
+            for (int64_t j = i; j < i + 4 && j < n; ++j) acc += g[j] * y[j];
+        }
+    }
+    double s[1] = {(double)acc};
+    block_sum<1>(s, red);
+    if (threadIdx.x == 0) sn_ws(ws, k, ti).part_s[blk] = s[0];
+}
+__device__ __forceinline__ float sn_project_one(float g, float c, float um, float vk, float isg) { return fmaf(-(c * um), vk, g) * isg; }
+__global__ __launch_bounds__(256) void sn_project_kernel(const SnPack k, int nt, double eps, double* __restrict__ ws) {
+    __shared__ double red[8];
+    __shared__ float c_slot, isg_slot;
+    const int ti = sn_tensor_of_block(k, nt);
+    const int blk = (int)blockIdx.x - k.first_block[ti];
+    const int M = k.rows[ti], K = k.cols[ti];
+    const double inner = sn_sum_partials(sn_ws(ws, k, ti).part_s, sn_eblocks(M, K), red);
+    if (threadIdx.x == 0) {
+        c_slot = (float)inner;
+        isg_slot = (float)(1.0 / fmax((double)k.sigma[ti][0], eps));
+    }
+    __syncthreads();
+    const float c = c_slot, isg = isg_slot;
+    float* __restrict__ g = k.g[ti];
+    const float* __restrict__ u = k.u[ti];
+    const float* __restrict__ v = k.v[ti];
+    const int64_t n = (int64_t)M * K, base = (int64_t)blk * 4096;
+    if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t i = base + (int64_t)(q * 256 + threadIdx.x) * 4;
+            if (i + 4 <= n) {
+                float4 x = *reinterpret_cast<const float4*>(g + i);
+                float e[4] = {x.x, x.y, x.z, x.w};
+                int m = (int)(i / K), c0 = (int)(i - (int64_t)m * K);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    e[j] = sn_project_one(e[j], c, u[m], v[c0], isg);
+                    if (++c0 == K) { c0 = 0; ++m; }
+                }
+                x.x = e[0]; x.y = e[1]; x.z = e[2]; x.w = e[3];
+                *reinterpret_cast<float4*>(g + i) = x;
+            } else {
+                for (int64_t j = i; j < n; ++j) { const int m = (int)(j / K); g[j] = sn_project_one(g[j], c, u[m], v[(int)(j - (int64_t)m * K)], isg); }
+            }
+        }
+    } else {
+#pragma unroll 4
+        for (int q = 0; q < 16; ++q) {
+            const int64_t i = base + q * 256 + threadIdx.x;
+            if (i >= n) break;
+            const int m = (int)(i / K);
+            g[i] = sn_project_one(g[i], c, u[m], v[(int)(i - (int64_t)m * K)], isg);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------- //
 // GRU recurrence (dm <= 32): one 64-lane block per sample, lane u < dm owns unit u
 // ------------------------------------------------------------------------- //
 #define GRU_MAXD 32
@@ -1860,6 +2170,108 @@ int dcv_ema_update_multi(int n_tensors, float* const* ema, const float* const* s
         k.first_block[nt] = blocks;
         if (blocks == 0) continue;
         hipLaunchKernelGGL(ema_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, b);
+        DCV_LAUNCH_CHECK();
+    }
+    return DCV_OK;
+}
+
+// workspace: 256 bytes (the skip flag), then every tensor's part (sn_ws_doubles)
+static bool sn_shapes_ok(int n, const int32_t* rows, const int32_t* cols) {
+    if (n < 0 || (n > 0 && (!rows || !cols))) return false;
+    for (int t = 0; t < n; ++t)
+        if (rows[t] < 1 || cols[t] < 1 || (int64_t)rows[t] * cols[t] > (int64_t)1 << 30) return false;
+    return true;
+}
+static size_t sn_workspace_bytes(int n, const int32_t* rows, const int32_t* cols) {
+    int64_t d = 0;
+    for (int t = 0; t < n; ++t) d += sn_ws_doubles(rows[t], cols[t]);
+    return align_up(256 + (size_t)d * sizeof(double), 256);
+}
+size_t dcv_spectral_workspace_bytes(int n_tensors, const int32_t* rows, const int32_t* cols) {
+    if (!sn_shapes_ok(n_tensors, rows, cols)) { fail(DCV_EINVAL, "spectral_workspace_bytes: bad arguments (rows and cols >= 1, rows * cols <= 2^30)"); return 0; }
+    return sn_workspace_bytes(n_tensors, rows, cols);
+}
+
+// the table of tensors t0 .. t0 + nt - 1; `which` picks the block count per tensor: 0 column chunks, 1 row chunks, 2 blocks of 4096 elements
+static int sn_fill(SnPack& k, int t0, int nt, const int32_t* rows, const int32_t* cols, const int64_t* ws_off, int which) {
+    int64_t blocks = 0;
+    for (int t = 0; t < nt; ++t) {
+        const int M = rows[t0 + t], K = cols[t0 + t];
+        k.rows[t] = M; k.cols[t] = K; k.ws_off[t] = ws_off[t0 + t];
+        k.first_block[t] = (int32_t)blocks;
+        blocks += which == 0 ? sn_kchunks(K) : which == 1 ? sn_mchunks(M) : sn_eblocks(M, K);
+    }
+    k.first_block[nt] = (int32_t)blocks;      // (<= 24 * 2^30 / 4 elements per block ... / 4096: far below 2^31)
+    return (int)blocks;
+}
+
+int dcv_spectral_update_multi(int n_tensors, const float* const* w, float* const* w_sn, float* const* u, float* const* v, float* const* sigma,
+                              const int32_t* rows, const int32_t* cols, int n_iter, double eps, const float* guard_state, void* ws, size_t ws_bytes, void* stream) {
+    if (!sn_shapes_ok(n_tensors, rows, cols) || (n_tensors > 0 && (!w || !w_sn || !u || !v || !sigma)) || n_iter < 0 || !(eps > 0.0) || !ws ||
+        (reinterpret_cast<uintptr_t>(ws) & 15))
+        return fail(DCV_EINVAL, "spectral_update_multi: bad arguments");
+    for (int t = 0; t < n_tensors; ++t)
+        if (!w[t] || !w_sn[t] || !u[t] || !v[t] || !sigma[t] || w[t] == w_sn[t]) return fail(DCV_EINVAL, "spectral_update_multi: null tensor, or w_sn is w");
+    if (sn_workspace_bytes(n_tensors, rows, cols) > ws_bytes) return fail(DCV_EWORKSPACE, "spectral_update_multi: workspace too small");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int32_t* skip = guard_state ? static_cast<int32_t*>(ws) : nullptr;
+    double* wsd = reinterpret_cast<double*>(static_cast<char*>(ws) + 256);
+    if (guard_state) {
+        hipLaunchKernelGGL(sn_prepare_kernel, dim3(1), dim3(1), 0, s, skip, guard_state);
+        DCV_LAUNCH_CHECK();
+    }
+    std::vector<int64_t> off(std::max(n_tensors, 1));
+    int64_t d = 0;
+    for (int t = 0; t < n_tensors; ++t) { off[t] = d; d += sn_ws_doubles(rows[t], cols[t]); }
+    for (int t0 = 0; t0 < n_tensors; t0 += ADAM_MT) {
+        SnPack k;
+        memset(&k, 0, sizeof(k));
+        const int nt = std::min(ADAM_MT, n_tensors - t0);
+        for (int t = 0; t < nt; ++t) { k.w[t] = w[t0 + t]; k.w_sn[t] = w_sn[t0 + t]; k.u[t] = u[t0 + t]; k.v[t] = v[t0 + t]; k.sigma[t] = sigma[t0 + t]; }
+        for (int it = 0; it < n_iter; ++it) {
+            int blocks = sn_fill(k, t0, nt, rows, cols, off.data(), 0);
+            hipLaunchKernelGGL(sn_cols_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, it > 0 ? 1 : 0, eps, wsd, skip);
+            DCV_LAUNCH_CHECK();
+            blocks = sn_fill(k, t0, nt, rows, cols, off.data(), 1);
+            hipLaunchKernelGGL(sn_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, 1, eps, wsd, skip);
+            DCV_LAUNCH_CHECK();
+        }
+        if (n_iter == 0) {      // sigma of the stored u, v
+            const int blocks = sn_fill(k, t0, nt, rows, cols, off.data(), 1);
+            hipLaunchKernelGGL(sn_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, 0, eps, wsd, skip);
+            DCV_LAUNCH_CHECK();
+        }
+        const int blocks = sn_fill(k, t0, nt, rows, cols, off.data(), 2);
+        hipLaunchKernelGGL(sn_scale_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, n_iter > 0 ? 1 : 0, eps, wsd, skip);
+        DCV_LAUNCH_CHECK();
+    }
+    return DCV_OK;
+}
+
+int dcv_spectral_project_multi(int n_tensors, float* const* g, const float* const* w_sn, const float* const* u, const float* const* v, const float* const* sigma,
+                               const int32_t* rows, const int32_t* cols, double eps, void* ws, size_t ws_bytes, void* stream) {
+    if (!sn_shapes_ok(n_tensors, rows, cols) || (n_tensors > 0 && (!g || !w_sn || !u || !v || !sigma)) || !(eps > 0.0) || !ws || (reinterpret_cast<uintptr_t>(ws) & 15))
+        return fail(DCV_EINVAL, "spectral_project_multi: bad arguments");
+    for (int t = 0; t < n_tensors; ++t)
+        if (!g[t] || !w_sn[t] || !u[t] || !v[t] || !sigma[t] || g[t] == w_sn[t]) return fail(DCV_EINVAL, "spectral_project_multi: null tensor, or g is w_sn");
+    if (sn_workspace_bytes(n_tensors, rows, cols) > ws_bytes) return fail(DCV_EWORKSPACE, "spectral_project_multi: workspace too small");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double* wsd = reinterpret_cast<double*>(static_cast<char*>(ws) + 256);
+    std::vector<int64_t> off(std::max(n_tensors, 1));
+    int64_t d = 0;
+    for (int t = 0; t < n_tensors; ++t) { off[t] = d; d += sn_ws_doubles(rows[t], cols[t]); }
+    for (int t0 = 0; t0 < n_tensors; t0 += ADAM_MT) {
+        SnPack k;
+        memset(&k, 0, sizeof(k));
+        const int nt = std::min(ADAM_MT, n_tensors - t0);
+        for (int t = 0; t < nt; ++t) {
+            k.g[t] = g[t0 + t]; k.w_sn[t] = const_cast<float*>(w_sn[t0 + t]); k.u[t] = const_cast<float*>(u[t0 + t]); k.v[t] = const_cast<float*>(v[t0 + t]);
+            k.sigma[t] = const_cast<float*>(sigma[t0 + t]);
+        }
+        const int blocks = sn_fill(k, t0, nt, rows, cols, off.data(), 2);
+        hipLaunchKernelGGL(sn_inner_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, wsd);
+        DCV_LAUNCH_CHECK();
+        hipLaunchKernelGGL(sn_project_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, eps, wsd);
         DCV_LAUNCH_CHECK();
     }
     return DCV_OK;

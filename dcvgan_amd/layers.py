@@ -58,6 +58,13 @@ def geom_of(conv) -> "ops.ConvGeom":
     return ops.conv_geom(conv.weight, conv.stride, conv.padding, isinstance(conv, nn.ConvTranspose2d), getattr(conv, "_dcv_precision", None))
 
 
+def _w_eff(conv, x):
+    """optim.spectral_norm's mark on a convolution (a plain attribute: an unmarked module pays this lookup and nothing else) -> the tensor W / sigma the kernels
+    read in place of conv.weight, or None.  Refuses a stale W / sigma and the 16-bit channels-last path."""
+    sn = conv.__dict__.get("_dcv_spectral")
+    return None if sn is None else sn.effective(conv, ops_cl.is_cl(x))
+
+
 def batch_norm(bn, x, rng, act=(ops.ACT_NONE, 0.0), dropout=None, out=None, partials=None, link=None):
     training = bn.training
     mask = None
@@ -101,6 +108,7 @@ def run(seq: nn.Sequential, x: torch.Tensor, rng, out=None, grad_slot=None, act_
             fused = _act_of(nxt) if nxt is not None else None
             last = i + (2 if fused is not None else 1) >= n
             box = [] if (fused is None and isinstance(nxt, _BNS) and nxt.training and _FUSE_BN_STATS) else None
+            _w_eff(layer, x)      # (raises on a marked convolution: spectral normalisation is fp32-path only)
             x = ops_cl.conv(x, layer.weight, geom_of(layer), *(fused or (ops.ACT_NONE, 0.0)), out=out if last else None, grad_slot=grad_slot if i == 0 else None, bn_stats=box,
                             act_slot=act_slot if (last and fused is not None) else None)
             pending = box[0] if box else None
@@ -111,14 +119,14 @@ def run(seq: nn.Sequential, x: torch.Tensor, rng, out=None, grad_slot=None, act_
             fused = _act_of(nxt) if nxt is not None else None
             if fused is not None:
                 x = ops.conv(x, layer.weight, geom_of(layer), fused[0], fused[1], out=out if i + 2 >= n else None, grad_slot=grad_slot if i == 0 else None,
-                             act_slot=act_slot if i + 2 >= n else None, bn_link=bn_link if i == 0 else None, gate=gate if first_conv else None)
+                             act_slot=act_slot if i + 2 >= n else None, bn_link=bn_link if i == 0 else None, gate=gate if first_conv else None, w_eff=_w_eff(layer, x))
                 first_conv = False
                 _tap(x, fused)
                 i += 2
             else:
                 box = [] if (isinstance(nxt, _BNS) and nxt.training and _FUSE_BN_STATS) else None
                 x = ops.conv(x, layer.weight, geom_of(layer), out=out if i + 1 >= n else None, bn_stats=box, grad_slot=grad_slot if i == 0 else None,
-                             gate=gate if first_conv else None)
+                             gate=gate if first_conv else None, w_eff=_w_eff(layer, x))
                 first_conv = False
                 pending = box[0] if box else None
                 i += 1

@@ -127,6 +127,10 @@ _SIGS = {
     "dcv_adam_step_multi_guarded": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, _P]),
     # EMA of the generators' weights (added symbol only: the ABI version stays 4)
     "dcv_ema_update_multi": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_double, C.c_int, _P, _P, _P]),
+    # spectral normalisation of the discriminators' weights (added symbols only: the ABI version stays 4)
+    "dcv_spectral_workspace_bytes": (C.c_size_t, [C.c_int, _P, _P]),
+    "dcv_spectral_update_multi": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_double, _P, _P, C.c_size_t, _P]),
+    "dcv_spectral_project_multi": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_double, _P, C.c_size_t, _P]),
     # synchronised BatchNorm for data parallel, fp32 path (added symbols only: the ABI version stays 4)
     "dcv_bn_sync_row_doubles": (C.c_size_t, [C.c_int]),
     "dcv_bn_sync_sums": (C.c_int, [_P, _D, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),

@@ -324,8 +324,18 @@ class _Conv(Function):
     _epoch = [object()]
 
     @staticmethod
-    def forward(ctx, x, w, g: ConvGeom, act: int, slope: float, out=None, bn_stats=None, grad_slot=None, act_slot=None, bn_link=None, gate=None):
+    def forward(ctx, x, w, g: ConvGeom, act: int, slope: float, out=None, bn_stats=None, grad_slot=None, act_slot=None, bn_link=None, gate=None, w_eff=None):
         N._require(x, "conv input"); N._require(w, "conv weight")
+        # `w_eff` (spectral normalisation): the tensor whose VALUES the kernels read — forward, data gradient, pack source and pack cache — in place of w's; every
+        # gradient decision below stays keyed on the Parameter w.  None: wv is w.
+        wv = w
+        ctx.w_eff = ctx.w_eff_version = None
+        if w_eff is not None:
+            wv = w_eff.v
+            N._require(wv, "conv effective weight")
+            if wv.shape != w.shape or not wv.is_contiguous() or wv.requires_grad:
+                raise N.NativeError("conv: w_eff must be a contiguous tensor of the weight's shape that does not require a gradient")
+            ctx.w_eff, ctx.w_eff_version = wv, wv._version
         ctx.grad_slot = grad_slot
         ctx.gate = gate if (_GATED_DGRAD and gate is not None and gate[1] is not None) else None
         ctx.bn_link = bn_link if _HEAD_BN_FUSION else None
@@ -343,15 +353,15 @@ class _Conv(Function):
         if need == 0:
             raise N.NativeError("conv forward: " + L.dcv_last_error().decode())
         wsp, wsn = _ws("conv", need, x.device)
-        ctx.pack = pc = _pack_of(w)
-        pk = pc.get(w, 0, g, x, y, xd, yd) if pc is not None else None
+        ctx.pack = pc = _pack_of(wv)
+        pk = pc.get(wv, 0, g, x, y, xd, yd) if pc is not None else None
         pkp = C.byref(pk) if pk is not None else None
         ctx.bn_deferred = False
         lk = ctx.bn_link
         if lk is not None and lk.deferred:
             # x's first channels were never written: the head's kernel reads the BatchNorm input and normalises on load — or, for a geometry it does not take,
             # the output is materialised now and everything proceeds as usual
-            rc = L.dcv_conv_forward_bn(C.byref(g), ptr(x), C.byref(xd), ptr(w), ptr(y), C.byref(yd), act, slope, pkp, wsp, wsn, *lk.view_args(), stream_ptr())
+            rc = L.dcv_conv_forward_bn(C.byref(g), ptr(x), C.byref(xd), ptr(wv), ptr(y), C.byref(yd), act, slope, pkp, wsp, wsn, *lk.view_args(), stream_ptr())
             if rc == N.DCV_EUNSUPPORTED:
                 od, bxd_ = dims5(lk.out), dims5(lk.x)
                 check(L.dcv_bn_apply(ptr(lk.x), C.byref(bxd_), ptr(lk.out), C.byref(od), ptr(lk.gamma), ptr(lk.beta), ptr(lk.stats[0]), ptr(lk.stats[1]), None,
@@ -369,12 +379,12 @@ class _Conv(Function):
             # conv -> BatchNorm pair: the epilogue leaves per-tile {sum, sum^2} of y, the BN op skips its pass over y
             stat = _empty((sbytes // 4,), x.device)     # poison runs turn a (class, tile) row no workgroup wrote into NaN statistics
             nparts, pitch = C.c_int(0), C.c_int(0)
-            check(L.dcv_conv_forward_stats(C.byref(g), ptr(x), C.byref(xd), ptr(w), ptr(y), C.byref(yd), ptr(stat), sbytes,
+            check(L.dcv_conv_forward_stats(C.byref(g), ptr(x), C.byref(xd), ptr(wv), ptr(y), C.byref(yd), ptr(stat), sbytes,
                                            C.byref(nparts), C.byref(pitch), pkp, wsp, wsn, stream_ptr()), "dcv_conv_forward_stats")
             if nparts.value > 0:
                 bn_stats.append((stat, nparts.value, pitch.value))
         else:
-            check(L.dcv_conv_forward(C.byref(g), ptr(x), C.byref(xd), ptr(w), ptr(y), C.byref(yd), act, slope, pkp, wsp, wsn, stream_ptr()), "dcv_conv_forward")
+            check(L.dcv_conv_forward(C.byref(g), ptr(x), C.byref(xd), ptr(wv), ptr(y), C.byref(yd), act, slope, pkp, wsp, wsn, stream_ptr()), "dcv_conv_forward")
         _PackCache.commit(pk)
         ctx.g, ctx.act, ctx.slope = g, act, slope
         ctx.save_for_backward(x, w, y if act != ACT_NONE else None)
@@ -383,6 +393,12 @@ class _Conv(Function):
     @staticmethod
     def backward(ctx, dy):
         x, w, y = ctx.saved_tensors
+        wv = w
+        if ctx.w_eff is not None:
+            wv = ctx.w_eff
+            if wv._version != ctx.w_eff_version:
+                raise N.NativeError("conv backward: the effective weight (w_eff) was rewritten after this forward — SpectralNorm.update() / refresh() belong after the "
+                                    "backward of every forward that used the old values")
         g = ctx.g
         L = lib()
         dy = _dense(dy)
@@ -406,7 +422,7 @@ class _Conv(Function):
             dxd = dims5(dx)
             need = L.dcv_conv_workspace_bytes(C.byref(g), C.byref(dxd), C.byref(dyd), 1)
             wsp, wsn = _ws("conv", need, x.device)
-            pk = ctx.pack.get(w, 1, g, dx, dy, dxd, dyd) if ctx.pack is not None else None
+            pk = ctx.pack.get(wv, 1, g, dx, dy, dxd, dyd) if ctx.pack is not None else None
             pkp = C.byref(pk) if pk is not None else None
             rc = N.DCV_EUNSUPPORTED
             link = ctx.bn_link
@@ -421,7 +437,7 @@ class _Conv(Function):
                 need2 = L.dcv_conv_backward_data_bn_workspace_bytes(C.byref(dxd), cbn)
                 ws2p, ws2n = _ws("headbn", need2, x.device)
                 fused = C.c_int(0)
-                rc = L.dcv_conv_backward_data_bn(C.byref(g), ptr(dy), C.byref(dyd), ptr(w), ptr(dx), C.byref(dxd), pkp, wsp, wsn, cbn, ptr(bx), C.byref(bxd),
+                rc = L.dcv_conv_backward_data_bn(C.byref(g), ptr(dy), C.byref(dyd), ptr(wv), ptr(dx), C.byref(dxd), pkp, wsp, wsn, cbn, ptr(bx), C.byref(bxd),
                                                  ptr(link.gamma), ptr(link.beta), ptr(link.stats[0]), ptr(link.stats[1]), link.act, link.slope,
                                                  ptr(bdx), C.byref(bdxd), ptr(dgb[0]), ptr(dgb[1]), ws2p, ws2n, C.byref(fused), stream_ptr())
                 if rc == N.DCV_EUNSUPPORTED:
@@ -433,7 +449,7 @@ class _Conv(Function):
             if rc == N.DCV_EUNSUPPORTED and into is not None and slot.act is not None and _GATED_DGRAD and tuple(x.stride()) == tuple(into.stride()):
                 # ... and the derivative of the activation that produced x, read off x, in the same epilogue
                 xd_ = dims5(x)
-                rc = L.dcv_conv_backward_data_gated(C.byref(g), ptr(dy), C.byref(dyd), ptr(w), ptr(dx), C.byref(dxd), 1, ptr(x), C.byref(xd_),
+                rc = L.dcv_conv_backward_data_gated(C.byref(g), ptr(dy), C.byref(dyd), ptr(wv), ptr(dx), C.byref(dxd), 1, ptr(x), C.byref(xd_),
                                                     slot.act[0], slot.act[1], pkp, wsp, wsn, stream_ptr())
                 if rc == 0:
                     slot.act_applied = True
@@ -445,14 +461,14 @@ class _Conv(Function):
                 gbuf, gslot = ctx.gate
                 if gslot.act is not None and tuple(gbuf.shape) == tuple(dx.shape) and tuple(gbuf.stride()) == tuple(dx.stride()):
                     gd_ = dims5(gbuf)
-                    rc = L.dcv_conv_backward_data_gated(C.byref(g), ptr(dy), C.byref(dyd), ptr(w), ptr(dx), C.byref(dxd), 0, ptr(gbuf), C.byref(gd_),
+                    rc = L.dcv_conv_backward_data_gated(C.byref(g), ptr(dy), C.byref(dyd), ptr(wv), ptr(dx), C.byref(dxd), 0, ptr(gbuf), C.byref(gd_),
                                                         gslot.act[0], gslot.act[1], pkp, wsp, wsn, stream_ptr())
                     if rc == 0:
                         gslot.act_applied = 2
                     elif rc != N.DCV_EUNSUPPORTED:
                         check(rc, "dcv_conv_backward_data_gated")
             if rc == N.DCV_EUNSUPPORTED:
-                check(L.dcv_conv_backward_data(C.byref(g), ptr(dy), C.byref(dyd), ptr(w), ptr(dx), C.byref(dxd), int(into is not None),
+                check(L.dcv_conv_backward_data(C.byref(g), ptr(dy), C.byref(dyd), ptr(wv), ptr(dx), C.byref(dxd), int(into is not None),
                                                pkp, wsp, wsn, stream_ptr()), "dcv_conv_backward_data")
             _PackCache.commit(pk)
             if into is not None:
@@ -513,7 +529,7 @@ class _Conv(Function):
                 check(L.dcv_conv_backward_weight(C.byref(g), ptr(x), C.byref(xd), ptr(dy), C.byref(dyd), ptr(dw), wsp, wsn, stream_ptr()), "dcv_conv_backward_weight")
                 if _OWN_ACCUMULATION:
                     note_first(w, dw)
-        return dx, dw, None, None, None, None, None, None, None, None, None
+        return dx, dw, None, None, None, None, None, None, None, None, None, None
 
 
 def new_backward_epoch():
@@ -521,13 +537,16 @@ def new_backward_epoch():
     _Conv._epoch[0] = object()
 
 
-def conv(x, w, g: ConvGeom, act: int = ACT_NONE, slope: float = 0.0, out=None, bn_stats=None, grad_slot=None, act_slot=None, bn_link=None, gate=None):
+def conv(x, w, g: ConvGeom, act: int = ACT_NONE, slope: float = 0.0, out=None, bn_stats=None, grad_slot=None, act_slot=None, bn_link=None, gate=None, w_eff=None):
     """y = act(conv(x, w)) for nn.Conv2d / nn.Conv3d / nn.ConvTranspose2d geometries.
     `out`: optional destination view (e.g. a channel slice of a concat buffer) to write into.
     `grad_slot`: ConcatBuffer.slot of the buffer whose second slice IS x (a skip connection), see GradSlot.
     `act_slot`: ConcatBuffer.slot of the buffer this conv + (Leaky)ReLU writes its output into (`out` is its second slice).
-    `bn_link`: the BnLink of the BatchNorm group that produced x's first channels (see BnLink)."""
-    return _Conv.apply(x, w, g, act, float(slope), None if out is None else _Out(out), bn_stats, grad_slot, act_slot, bn_link, gate)
+    `bn_link`: the BnLink of the BatchNorm group that produced x's first channels (see BnLink).
+    `w_eff`: a tensor of w's shape whose values the convolution computes with (optim.SpectralNorm's W / sigma) while the weight gradient — with respect to those
+    values — is still delivered to the Parameter w."""
+    return _Conv.apply(x, w, g, act, float(slope), None if out is None else _Out(out), bn_stats, grad_slot, act_slot, bn_link, gate,
+                       None if w_eff is None else _Opaque(w_eff))
 
 
 # --------------------------------------------------------------------------- #

@@ -737,3 +737,183 @@ def sync_bn_group_of(module_or_models) -> Optional[SyncBnGroup]:
         if h is not None:
             return h
     return None
+
+
+# --------------------------------------------------------------------------- #
+# Spectral normalisation of the discriminators' convolutions (fp32 path)
+# --------------------------------------------------------------------------- #
+class _SpectralMark:
+    """What a marked convolution carries in ``__dict__["_dcv_spectral"]``: W / sigma (plain device memory, not a buffer: it is recomputed, never saved) and the
+    autograd version of the weight it was computed from.  A deep copy of the module gets None in its place: the copy carries the buffers and no mark."""
+    __slots__ = ("w_sn", "version")
+
+    def __init__(self, w_sn):
+        self.w_sn, self.version = w_sn, None
+
+    def effective(self, conv, channels_last: bool) -> torch.Tensor:
+        if channels_last:
+            raise NativeError("spectral normalisation (optim.spectral_norm) is fp32-path only: this convolution received a 16-bit channels-last tensor")
+        if self.version != conv.weight._version:
+            raise NativeError("spectral normalisation: the weight changed since W / sigma was last formed (an optimiser step, load_state_dict, init) — call "
+                              "SpectralNorm.update() after the step, or refresh() after loading")
+        return self.w_sn
+
+    def __deepcopy__(self, memo):
+        return None
+
+
+def is_spectral(conv) -> bool:
+    return conv.__dict__.get("_dcv_spectral") is not None
+
+
+class SpectralNorm:
+    """Spectral normalisation of nn.Conv2d / nn.Conv3d weights on the device: the convolutions compute with W / sigma(W), the Parameter stays W.
+
+        sn = spectral_norm(models, guard=opt_idis.guard)      # marks the convolutions, registers weight_u / weight_v / weight_sigma, 15 power iterations
+        loss.backward(); sn.project()                          # p.grad (the sum over every use of W / sigma): dL/d(W / sigma) -> dL/dW, once per optimiser step
+        guard.measure(); opt.step() ...; sn.update()           # one power iteration and a new W / sigma per weight VERSION, right after the steps
+
+    W is (cout, cin * kd * kh * kw): torch.nn.utils.spectral_norm's dim = 0, its formulas and its eps.  torch updates u, v at every forward; here they — and sigma
+    — stay fixed between two optimiser steps, which is what makes one projection of the summed gradient valid and keeps the packed weights of W / sigma valid over
+    the two or three uses of a discriminator per iteration.  A zero matrix gives W / sigma = 0 (torch: NaN).  With a ``guard`` the update applies — or skips on —
+    the guard's last measurement, like the optimiser steps on it.  Nothing here reads a value on the host, runs a torch kernel or allocates in the steady state; the
+    same bits in give the same bits out, so data-parallel replicas stay identical without a collective.  GPU only, fp32 only."""
+
+    def __init__(self, modules, n_init: int = 15, eps: float = 1e-12, seed: int = 0, guard: Optional[GradGuard] = None):
+        if not float(eps) > 0.0:
+            raise ValueError(f"SpectralNorm: eps must be positive, got {eps!r}")
+        if int(n_init) != n_init or int(n_init) < 0:
+            raise ValueError(f"SpectralNorm: n_init must be a non-negative integer, got {n_init!r}")
+        self.eps, self.guard = float(eps), guard
+        self._dp: List["DataParallelAdam"] = []      # wrappers whose buckets project() reduces first (trainer.build_spectral_norm; a guard's are taken from it)
+        self.convs: List[torch.nn.Module] = []
+        seen = set()
+        for m in modules:
+            for sub in m.modules():
+                if isinstance(sub, (torch.nn.ConvTranspose1d, torch.nn.ConvTranspose2d, torch.nn.ConvTranspose3d)):
+                    raise NativeError("spectral_norm: ConvTranspose layers are not supported (their matrix is the other axis; no discriminator has one)")
+                if isinstance(sub, (torch.nn.Conv2d, torch.nn.Conv3d)) and id(sub) not in seen:
+                    seen.add(id(sub))
+                    self.convs.append(sub)
+        if not self.convs:
+            raise ValueError("spectral_norm: no Conv2d / Conv3d to mark")
+        for c in self.convs:      # every refusal before the first mark
+            if is_spectral(c):
+                raise NativeError("spectral_norm: a convolution is already marked")
+            if c.weight.dtype != torch.float32 or not c.weight.is_contiguous():
+                raise NativeError("spectral_norm: weights must be contiguous float32")
+        gen = torch.Generator().manual_seed(int(seed))      # the same seed on every rank: replicas start from the same u, v
+        for c in self.convs:
+            w = c.weight
+            rows, cols = w.shape[0], w[0].numel()
+            u = torch.nn.functional.normalize(torch.randn(rows, generator=gen, dtype=torch.float64), dim=0, eps=self.eps).float()
+            v = torch.nn.functional.normalize(torch.randn(cols, generator=gen, dtype=torch.float64), dim=0, eps=self.eps).float()
+            c.register_buffer("weight_u", u.to(w.device))      # (host tensor -> device copies, once, before training: no kernel)
+            c.register_buffer("weight_v", v.to(w.device))
+            c.register_buffer("weight_sigma", torch.ones(1).to(w.device))
+            c.__dict__["_dcv_spectral"] = _SpectralMark(torch.zeros(w.shape, dtype=torch.float32).to(w.device))
+        self._tables = None
+        self._ws: Optional[torch.Tensor] = None
+        if self.convs[0].weight.is_cuda:      # host models can be marked (checkpoint layout, tests without a GPU); update() refuses them
+            self.update(n_iter=int(n_init), _guarded=False)
+
+    def remove(self):
+        """Unmark: the convolutions compute with their raw weights again and lose the three buffers."""
+        for c in self.convs:
+            c.__dict__.pop("_dcv_spectral", None)
+            for k in ("weight_u", "weight_v", "weight_sigma"):
+                c._buffers.pop(k, None)
+                c._non_persistent_buffers_set.discard(k)
+        self.convs = []
+
+    def _table(self):
+        ts = [(c.weight, c.__dict__["_dcv_spectral"].w_sn, c.weight_u, c.weight_v, c.weight_sigma) for c in self.convs]
+        key = tuple(t.data_ptr() for row in ts for t in row)
+        if self._tables is not None and self._tables[0] == key:
+            return self._tables
+        for i, row in enumerate(ts):
+            for t in row:
+                _require(t.data, f"SpectralNorm tensor of convolution {i}")
+                if not t.is_contiguous():
+                    raise NativeError("SpectralNorm: tensors must be contiguous")
+            w, w_sn, u, v, sg = row
+            if w_sn.shape != w.shape or u.numel() != w.shape[0] or v.numel() != w[0].numel() or sg.numel() != 1:
+                raise NativeError(f"SpectralNorm: the buffers of convolution {i} do not fit its weight {tuple(w.shape)}")
+        n = len(ts)
+        col = lambda j: (C.c_void_p * n)(*[row[j].data_ptr() for row in ts])
+        rows, cols = (C.c_int32 * n)(*[row[0].shape[0] for row in ts]), (C.c_int32 * n)(*[row[0][0].numel() for row in ts])
+        need = lib().dcv_spectral_workspace_bytes(n, rows, cols)
+        if need == 0:
+            raise NativeError("dcv_spectral_workspace_bytes: " + lib().dcv_last_error().decode(errors="replace"))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=ts[0][0].device)
+        self._tables = (key, n, col(0), col(1), col(2), col(3), col(4), rows, cols, [row[1] for row in ts])
+        return self._tables
+
+    @torch.no_grad()
+    def update(self, n_iter: int = 1, _guarded: bool = True):
+        """`n_iter` power iterations from the stored u, v, then sigma and W / sigma, for every marked convolution; records each weight's version."""
+        _, n, w, w_sn, u, v, sg, rows, cols, touched = self._table()      # every refusal before the first launch
+        state = ptr(self.guard._need_state()) if (self.guard is not None and _guarded) else None
+        check(lib().dcv_spectral_update_multi(n, w, w_sn, u, v, sg, rows, cols, int(n_iter), self.eps, state, ptr(self._ws), self._ws.numel(), stream_ptr()),
+              "dcv_spectral_update_multi")
+        # the kernels wrote through raw pointers: the packed-weight caches of W / sigma are keyed on its version counter (harmless after a skipped update)
+        torch.autograd.graph.increment_version(touched)
+        for c in self.convs:
+            c.__dict__["_dcv_spectral"].version = c.weight._version
+
+    def refresh(self):
+        """sigma and W / sigma of the current weights and the stored u, v (no power iteration, never skipped): after load_state_dict."""
+        self.update(n_iter=0, _guarded=False)
+
+    @torch.no_grad()
+    def project(self):
+        """p.grad <- (G - <G, W / sigma> u v^T) / sigma for every marked weight that has a gradient: G is what the weight-gradient kernels summed over every use of
+        W / sigma since zero_grad.  Once per optimiser step, before the guard measures."""
+        for w in list(self._dp) + (list(self.guard._dp) if self.guard is not None else []):
+            w.reduce_gradients()      # data parallel: never write a slice a collective is still reading, and project the SUM over the ranks (linear)
+        key, n, _, w_sn, u, v, sg, rows, cols, _ = self._table()
+        idx, gs = [], []
+        for i, c in enumerate(self.convs):
+            g = c.weight.grad
+            if g is None:
+                continue
+            _require(g, "SpectralNorm gradient")
+            if not g.is_contiguous() or g.shape != c.weight.shape:
+                raise NativeError("SpectralNorm: gradients must be contiguous and of the weight's shape")
+            idx.append(i); gs.append(g.data_ptr())
+        if not idx:
+            return
+        m = len(idx)
+        pick = lambda arr, ty: (ty * m)(*[arr[i] for i in idx])
+        check(lib().dcv_spectral_project_multi(m, (C.c_void_p * m)(*gs), pick(w_sn, C.c_void_p), pick(u, C.c_void_p), pick(v, C.c_void_p), pick(sg, C.c_void_p),
+                                               pick(rows, C.c_int32), pick(cols, C.c_int32), self.eps, ptr(self._ws), self._ws.numel(), stream_ptr()),
+              "dcv_spectral_project_multi")
+
+    def state_dict(self):
+        """u, v, sigma per marked convolution in marking order (they are also buffers of the modules, so a model checkpoint already carries them) and eps."""
+        return {"eps": self.eps, "u": [c.weight_u.detach().cpu().clone() for c in self.convs], "v": [c.weight_v.detach().cpu().clone() for c in self.convs],
+                "sigma": [c.weight_sigma.detach().cpu().clone() for c in self.convs]}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        """Loads u, v, sigma; W / sigma is stale afterwards — a marked convolution refuses to run until refresh()."""
+        if not (len(sd["u"]) == len(sd["v"]) == len(sd["sigma"]) == len(self.convs)):
+            raise ValueError(f"SpectralNorm.load_state_dict: {len(sd['u'])} layers in the checkpoint, {len(self.convs)} marked")
+        self.eps = float(sd["eps"])
+        for c, u, v, s in zip(self.convs, sd["u"], sd["v"], sd["sigma"]):
+            c.weight_u.copy_(u); c.weight_v.copy_(v); c.weight_sigma.copy_(s)
+            c.__dict__["_dcv_spectral"].version = None
+
+
+def spectral_norm(models_or_modules, names=("idis", "vdis", "gdis"), n_init: int = 15, eps: float = 1e-12, seed: int = 0,
+                  guard: Optional[GradGuard] = None) -> SpectralNorm:
+    """Mark every Conv2d / Conv3d of the models `names` of a dict (or of a module / a sequence of modules) for spectral normalisation and return the handle that
+    updates and projects them (SpectralNorm).  Raises on a ConvTranspose layer.  fp32 path only."""
+    if isinstance(models_or_modules, dict):
+        mods = [models_or_modules[n] for n in names]
+    elif isinstance(models_or_modules, torch.nn.Module):
+        mods = [models_or_modules]
+    else:
+        mods = list(models_or_modules)
+    return SpectralNorm(mods, n_init=n_init, eps=eps, seed=seed, guard=guard)

@@ -76,6 +76,16 @@ def build_ema(cfg: StepConfig, models, optimizers, decay: float = 0.999, warmup:
     return optim.ModelEma(models, names=("ggen", "cgen"), decay=decay, warmup=warmup, guard=getattr(optimizers["ggen"], "guard", None))
 
 
+def build_spectral_norm(cfg: StepConfig, models, optimizers, names=("idis", "vdis", "gdis"), n_init: int = 15, eps: float = 1e-12,
+                        seed: int = 0) -> "optim.SpectralNorm":
+    """Spectral normalisation of the discriminators' convolutions (optim.spectral_norm), wired to the D phase's guard when build_optimizers made one — the three D
+    steps and the power iteration then share one measurement and are all applied or all skipped — and to the data-parallel wrappers, whose bucket the projection
+    reduces first.  Hand it to StepRunner(..., spectral=...).  fp32 path only."""
+    sn = optim.spectral_norm(models, names=names, n_init=n_init, eps=eps, seed=seed, guard=getattr(optimizers[names[0]], "guard", None))
+    sn._dp = [optimizers[n] for n in names if hasattr(optimizers[n], "reduce_gradients")]
+    return sn
+
+
 class StepRunner:
     """`elide_dead_backward=True` builds the D-phase fakes without a tape (they are detached): the
     reference backpropagates `loss_dis` through cgen/ggen too (trainer.py:304-319, fakes not detached)
@@ -84,8 +94,11 @@ class StepRunner:
     "minimal" column).  Default False = the reference's as-written schedule."""
 
     def __init__(self, cfg: StepConfig, models, optimizers, loss, sync_losses: bool = False, elide_dead_backward: bool = False,
-                 side_streams: Optional[bool] = None, ema: Optional["optim.ModelEma"] = None):
+                 side_streams: Optional[bool] = None, ema: Optional["optim.ModelEma"] = None, spectral: Optional["optim.SpectralNorm"] = None):
         self.cfg, self.models, self.opt, self.loss = cfg, models, optimizers, loss
+        # optim.SpectralNorm (build_spectral_norm): in the D phase the summed gradients are projected before the guard measures, and W / sigma is renewed right after
+        # the three steps, on the optimiser's stream (the lanes see it ordered as they see the new weights); None leaves the iteration as it is
+        self.spectral = spectral
         self.ema = ema      # optim.ModelEma (build_ema): updated once per iteration whose G phase stepped, after its three steps; None leaves the iteration as it is
         self.iteration = 0
         self.sync_losses = sync_losses
@@ -204,9 +217,13 @@ class StepRunner:
         if self.iteration % c.num_gen_update == 0:
             loss_dis.backward(guard_dis.root(loss_dis) if guard_dis is not None else self._root(loss_dis))
             self._mark("D: backward (D lanes, then the generators' dead backward)")
+            if self.spectral is not None:
+                self.spectral.project()      # dL/d(W / sigma), summed over the real and the fake batch -> dL/dW (the G phase's gradients into D are never stepped)
             if guard_dis is not None:
                 guard_dis.measure()
             o["idis"].step(); o["vdis"].step(); o["gdis"].step()
+            if self.spectral is not None:
+                self.spectral.update()       # one power iteration per weight version
             self._mark("D: Adam")
         else:
             loss_dis.detach_()

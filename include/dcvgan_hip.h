@@ -365,6 +365,28 @@ int dcv_adam_step_multi_guarded(int n_tensors, float* const* p, const float* con
 int dcv_ema_update_multi(int n_tensors, float* const* ema, const float* const* src, const int64_t* numel, const int32_t* mode,
                          double decay, int warmup, int32_t* ema_block, const float* guard_state /* may be NULL */, void* stream);
 
+/* ---- spectral normalisation of convolution weights (the discriminators' Lipschitz control), fp32 ------ *
+ * A weight is a contiguous matrix W of rows[t] rows (cout) and cols[t] columns (cin * kd * kh * kw).  One update with n_iter power iterations:
+ *   repeat n_iter:  t = W^T u ; v = t / max(|t|, eps) ; s = W v ; u = s / max(|s|, eps)
+ *   sigma = u^T (W v)   (n_iter = 0: of the stored u, v) ;  w_sn = W / max(sigma, eps)        (a zero matrix gives w_sn = 0, not NaN)
+ * Products and a thread's running sums are fp32; block partials are double and are added in a fixed order; the norms, 1 / norm and 1 / sigma are formed by one thread
+ * in double (sqrt and one division) and rounded to fp32 once.  No atomics: the same inputs give the same bits.  16-byte loads where a tensor's base (and, for the
+ * matrix passes, its row pitch) allow, single elements otherwise; pointers need 4-byte alignment only.  `w` is never written.
+ * LAUNCHES, a function of n_tensors, n_iter and the guard only: ceil(n_tensors / 24) * (n_iter > 0 ? 2 * n_iter + 1 : 2) + (guard_state ? 1 : 0) for an update,
+ * 2 * ceil(n_tensors / 24) for a projection.
+ * With guard_state a one-thread kernel reads guard_state[DCV_GUARD_SKIPPED] first; a skipped update writes no u, v, sigma or w_sn.
+ * `ws`: dcv_spectral_workspace_bytes(n, rows, cols) bytes of device memory on a 16-byte boundary, scratch of one call (update or projection).
+ * rows, cols >= 1 and rows * cols <= 2^30. */
+size_t dcv_spectral_workspace_bytes(int n_tensors, const int32_t* rows, const int32_t* cols);
+int dcv_spectral_update_multi(int n_tensors, const float* const* w, float* const* w_sn, float* const* u, float* const* v, float* const* sigma,
+                              const int32_t* rows, const int32_t* cols, int n_iter, double eps, const float* guard_state /* may be NULL */,
+                              void* ws, size_t ws_bytes, void* stream);
+/* The gradient with respect to W of a loss whose gradient with respect to w_sn is g, with u and v held constant, in place on g:
+ *   g <- (g - <g, w_sn> u v^T) / max(sigma, eps)        (eps: the update's, so that both divide by the same number)
+ * It is linear in g: apply it once to the SUM of the gradients of all uses of one (w_sn, u, v, sigma).  w_sn, u, v and sigma are not written. */
+int dcv_spectral_project_multi(int n_tensors, float* const* g, const float* const* w_sn, const float* const* u, const float* const* v, const float* const* sigma,
+                               const int32_t* rows, const int32_t* cols, double eps, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- bf16 channels-last ("CL16") data path -------------------------------------------------- *
  * BASELINE.json configs[2] ("surreal-depth1, bf16 MFMA") and configs[4] ("fp16 MFMA") name 16-bit variants of the same step
  * (config/surreal-depth1.yml:5,47-76, config/isogd-flow.yml; the reference itself is fp32-only).  This is that path as a DATA path:
