@@ -94,6 +94,19 @@ __device__ __forceinline__ float cl_hi(uint32_t w) { return __builtin_bit_cast(f
 __device__ __forceinline__ float cl_round(float v) { return (float)(cl_h)v; }      // the value as it will be stored
 }  // namespace dcv
 namespace dcv {
+// Philox4x32-10 (Salmon et al. 2011): counter c, key (k0, k1); every random draw of the library (elementwise.hip, augment.hip)
+__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+        const uint32_t n0 = hi1 ^ c[1] ^ k0, n1 = lo1, n2 = hi0 ^ c[3] ^ k1, n3 = lo0;
+        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+}  // namespace dcv
+namespace dcv {
 // n / d for the FastDiv above (d == 1 handled by mul == 0 convention)
 __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv f) {
     if (f.div == 1) return n;

@@ -213,16 +213,7 @@ struct Axpby {
 // ------------------------------------------------------------------------- //
 // Philox4x32-10 + Box-Muller
 // ------------------------------------------------------------------------- //
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n1 = lo1, n2 = hi0 ^ c[3] ^ k1, n3 = lo0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
+// (philox4x32_10 itself is in dcv_common.h: augment.hip draws with the same function)
 // 4 N(0,1) samples for 128-bit counter (idx, stream offset)
 __device__ __forceinline__ void normal4(uint64_t seed, uint64_t offset, uint64_t idx, float (&o)[4]) {
     uint32_t c[4] = {(uint32_t)idx, (uint32_t)(idx >> 32), (uint32_t)offset, (uint32_t)(offset >> 32)};

@@ -47,6 +47,11 @@ class ConvGeom(C.Structure):
         return tuple(getattr(self, f) for f, _ in self._fields_)
 
 
+class AugLimits(C.Structure):
+    """dcv_aug_limits: the ranges dcv_aug_draw draws a clip's row from, and the mask of enabled ops (flip 1, translate 2, cutout 4, colour 8)."""
+    _fields_ = [("mx", C.c_int32), ("my", C.c_int32), ("size", C.c_int32), ("mask", C.c_int32), ("contrast", C.c_float), ("brightness", C.c_float)]
+
+
 _P = C.c_void_p
 _D = C.POINTER(Dims5)
 _G = C.POINTER(ConvGeom)
@@ -131,6 +136,13 @@ _SIGS = {
     "dcv_spectral_workspace_bytes": (C.c_size_t, [C.c_int, _P, _P]),
     "dcv_spectral_update_multi": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_double, _P, _P, C.c_size_t, _P]),
     "dcv_spectral_project_multi": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_double, _P, C.c_size_t, _P]),
+    # adaptive clip augmentation in front of the discriminators (added symbols only: the ABI version stays 4)
+    "dcv_aug_apply": (C.c_int, [_P, _D, _P, C.c_int, _P, _D, C.c_int, C.c_int, _P]),
+    "dcv_aug_apply_backward": (C.c_int, [_P, _D, _P, C.c_int, _P, _D, C.c_int, C.c_int, _P]),
+    "dcv_aug_fan_backward": (C.c_int, [_P, _D, _P, _D, _P, _D, _P, _D, C.c_int, _P, C.c_int, _P, _D, C.c_int, C.c_int, _P]),
+    "dcv_aug_draw": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_uint64, C.c_uint64, _P]),
+    "dcv_aug_observe": (C.c_int, [_P, C.c_int64, _P, _P]),
+    "dcv_aug_adjust": (C.c_int, [_P, C.c_double, C.c_float, C.c_float, _P]),
     # synchronised BatchNorm for data parallel, fp32 path (added symbols only: the ABI version stays 4)
     "dcv_bn_sync_row_doubles": (C.c_size_t, [C.c_int]),
     "dcv_bn_sync_sums": (C.c_int, [_P, _D, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),

@@ -86,6 +86,17 @@ def build_spectral_norm(cfg: StepConfig, models, optimizers, names=("idis", "vdi
     return sn
 
 
+def build_augment(cfg: StepConfig, models, optimizers, **kw) -> "augment.ClipAugment":
+    """Adaptive clip augmentation in front of the three discriminators (augment.ClipAugment) on the models' device; keyword arguments are the
+    constructor's (p, adaptive, target, interval, p_max, adjust_clips, ops, seed, ...).  Hand it to StepRunner(..., augment=...).  fp32 path only.  Under data
+    parallelism every rank makes this call (it creates a process group); the per-rank batch is cfg.batchsize, so `batch` defaults to batchsize x world."""
+    from . import augment
+    import torch.distributed as dist
+    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    kw.setdefault("batch", cfg.batchsize * world)
+    return augment.ClipAugment(cfg, next(models["idis"].parameters()).device, **kw)
+
+
 class StepRunner:
     """`elide_dead_backward=True` builds the D-phase fakes without a tape (they are detached): the
     reference backpropagates `loss_dis` through cgen/ggen too (trainer.py:304-319, fakes not detached)
@@ -94,8 +105,12 @@ class StepRunner:
     "minimal" column).  Default False = the reference's as-written schedule."""
 
     def __init__(self, cfg: StepConfig, models, optimizers, loss, sync_losses: bool = False, elide_dead_backward: bool = False,
-                 side_streams: Optional[bool] = None, ema: Optional["optim.ModelEma"] = None, spectral: Optional["optim.SpectralNorm"] = None):
+                 side_streams: Optional[bool] = None, ema: Optional["optim.ModelEma"] = None, spectral: Optional["optim.SpectralNorm"] = None,
+                 augment: Optional["augment.ClipAugment"] = None):
         self.cfg, self.models, self.opt, self.loss = cfg, models, optimizers, loss
+        # augment.ClipAugment (build_augment): the real pair and each phase's fakes pass through it on their way to the discriminators (cgen still reads the
+        # un-augmented geometry clip); None leaves the iteration as it is
+        self.augment = augment
         # optim.SpectralNorm (build_spectral_norm): in the D phase the summed gradients are projected before the guard measures, and W / sigma is renewed right after
         # the three steps, on the optimiser's stream (the lanes see it ordered as they see the new weights); None leaves the iteration as it is
         self.spectral = spectral
@@ -161,12 +176,26 @@ class StepRunner:
     # is a torch add per extra consumer plus the zero-fill + copy of each slice's backward (18 + ~25 torch launches per iteration in round 5's traces).
     def _colour(self, cgen, xg_fake, t_rand):
         """-> ((frame, for vdis, for gdis) of the geometry clip, the same of the colour clip cgen makes of it)"""
+        if self.augment is not None:
+            return self._colour_augmented(cgen, xg_fake, t_rand)
         if not (xg_fake.is_cuda and xg_fake.requires_grad):
             xc = cgen.forward_videos(xg_fake)
             return (xg_fake[:, :, t_rand], xg_fake, xg_fake), (xc[:, :, t_rand], xc, xc)
         g_i, g_c, g_v, g_g = ops.fan_out(xg_fake, t_rand, 3)
         c_i, c_v, c_g = ops.fan_out(cgen.forward_videos(g_c), t_rand, 2)
         return (g_i, g_v, g_g), (c_i, c_v, c_g)
+
+    def _colour_augmented(self, cgen, xg_fake, t_rand):
+        """_colour with the augmentation between the generators and the discriminators: cgen reads the clip as ggen made it and the augmented pair (one draw) is what
+        fans out to the three discriminators.  The colour clip's fan-in stays ops.fan_out; the geometry clip's four readers meet in augment._AugFan."""
+        if not (xg_fake.is_cuda and xg_fake.requires_grad):
+            yg, yc = self.augment(xg_fake, cgen.forward_videos(xg_fake))
+            return (yg[:, :, t_rand], yg, yg), (yc[:, :, t_rand], yc, yc)
+        aug = self.augment
+        table = aug.draw(xg_fake.shape[0], xg_fake.shape[3], xg_fake.shape[4])
+        g_c, g_i, g_v, g_g = aug.fan_geometry(xg_fake, t_rand, table)      # the geometry clip's ONE gradient: one launch, in ops.fan_out's order of additions
+        yc = aug.colour(cgen.forward_videos(g_c), table)
+        return (g_i, g_v, g_g), ops.fan_out(yc, t_rand, 2)
 
     def _fakes_through(self, dis, idis, xg, xc, t_rand):
         which = {id(d): k for k, d in enumerate(dis)}
@@ -202,6 +231,8 @@ class StepRunner:
             d.zero_grad()
         dis = (idis, vdis, gdis)
         self._mark("start")
+        if self.augment is not None:
+            xg_real, xc_real = self.augment(xg_real, xc_real)      # once per iteration, before the D lanes start
         y_real = self._on_lanes(dis, lambda d: d(xg_real[:, :, t_rand], xc_real[:, :, t_rand]) if d is idis else d(xg_real, xc_real), join=False)
         with torch.set_grad_enabled(not self.elide_dead_backward):
             xg_fake = ggen.sample_videos(c.batchsize)     # on the main stream, beside the discriminators' real-batch passes
@@ -209,6 +240,9 @@ class StepRunner:
         self._mark("D: generators forward (beside D on the real batch)")
         y_fake = self._fakes_through(dis, idis, xg_fake, xc_fake, t_rand)
         self._adopt(y_real)
+        if self.augment is not None:
+            for y in y_real:
+                self.augment.observe(y)      # r = E[sign(D(real))]: integer sums on the device (adaptive mode only)
         self._mark("D: discriminators forward on the fakes")
         loss_idis = self.loss.compute_dis_loss(y_real[0], y_fake[0])
         loss_vdis = self.loss.compute_dis_loss(y_real[1], y_fake[1])
@@ -233,6 +267,8 @@ class StepRunner:
             out = {"loss_idis": loss_idis.detach(), "loss_vdis": loss_vdis.detach(), "loss_gdis": loss_gdis.detach()}
         if guard_dis is not None:
             self._guard_report(out, guard_dis, "dis")
+        if self.augment is not None:
+            self.augment.end_of_iteration(self.iteration)      # every `interval` iterations: p follows r (one thread; after an all-reduce of the sums under data parallelism)
         del y_real, y_fake, xg_fake, xc_fake, loss_dis
         # ---- generator phase (trainer.py:338-363) ----
         ggen.train(); cgen.train()

@@ -387,6 +387,69 @@ int dcv_spectral_update_multi(int n_tensors, const float* const* w, float* const
 int dcv_spectral_project_multi(int n_tensors, float* const* g, const float* const* w_sn, const float* const* u, const float* const* v, const float* const* sigma,
                                const int32_t* rows, const int32_t* cols, double eps, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- adaptive clip augmentation in front of the discriminators (DiffAugment's transforms, ADA's probability), fp32 ------ *
+ * The reference shows the discriminators the clips as they are (trainer.py:299-309 the real pair and the D phase's fakes, trainer.py:344-349 the G phase's fakes);
+ * these entries transform a clip pair between those lines and the discriminators' forward, differentiably (added symbols only: the ABI version stays 4).
+ * One row of `table` = int32[table_rows][8] per clip serves all frames and both streams of a pair:                                                          */
+#define DCV_AUG_T_FLIP 0       /* 0 or 1: mirror left-right                                                                    */
+#define DCV_AUG_T_DX 1         /* shift right by dx pixels, zero padding                                                       */
+#define DCV_AUG_T_DY 2         /* shift down by dy pixels                                                                      */
+#define DCV_AUG_T_CUT_Y0 3     /* the cutout box [cut_y0, cut_y0 + cut_size) x [cut_x0, cut_x0 + cut_size); may hang over a border */
+#define DCV_AUG_T_CUT_X0 4
+#define DCV_AUG_T_CUT_SIZE 5   /* 0: no cutout                                                                                 */
+#define DCV_AUG_T_GAIN 6       /* fp32 bits                                                                                    */
+#define DCV_AUG_T_BIAS 7       /* fp32 bits.  The identity row is {0, 0, 0, 0, 0, 0, bits(1.0f), bits(0.0f)}                   */
+/* y[b, c, t, h, w] = 0 inside the cutout box; else with hs = h - dy, ws = w - dx: 0 if (hs, ws) is outside the plane (padding is zero AFTER the colour step); else
+ *   v = x[b, c, t, hs, flip ? W - 1 - ws : ws],  y = sgn * v * gain + bias  as two separately rounded fp32 operations (never one fma).
+ * `colour` = 0 (the geometry stream): gain 1, bias 0 and NO arithmetic: the bits are moved (-0.0 and NaN payloads survive).  sgn = -1 where flip is set and
+ * c == flip_negate_channel (-1: no such channel; 0 for an optical-flow clip, whose horizontal component changes sign under a mirror, util.py:160), exact.
+ * x: any strided view; y: contiguous (N, C, D, H, W).  16-byte stores where y's base allows (W % 4 == 0), 16-byte loads where dx % 4 == 0, there is no flip and
+ * x's base and pitches allow, dword loads otherwise; W % 4 != 0 or a w stride other than 1 takes one element per lane.  One launch.
+ * (The adjoint's output dx may be any strided view: a gradient is best written in the layout of the tensor it belongs to.)
+ * dcv_aug_apply_backward is the adjoint, also a gather (no atomics): for source pixel (hs, wsrc), ws = flip ? W - 1 - wsrc : wsrc, (h, w) = (hs + dy, ws + dx);
+ *   dx_out = (sgn * gain) * dy_in[h, w] (one rounding; gain 1 on the geometry stream) if (h, w) is inside the plane and outside the box, else 0.  bias has no gradient.
+ * DCV_EINVAL before any launch: shapes that differ, table_rows != N, an output that is not contiguous; DCV_EUNSUPPORTED: H or W above 4096. */
+int dcv_aug_apply(const float* x, const dcv_dims5* xd, const int32_t* table, int table_rows, float* y, const dcv_dims5* yd, int colour, int flip_negate_channel,
+                  void* stream);
+int dcv_aug_apply_backward(const float* dy, const dcv_dims5* dyd, const int32_t* table, int table_rows, float* dx, const dcv_dims5* dxd, int colour,
+                           int flip_negate_channel, void* stream);
+/* The adjoint for a clip that several consumers read (the fakes' geometry clip: the colour generator reads it as it is, two discriminators read the augmented clip
+ * and the image discriminator reads frame `frame` of it, trainer.py:303-309,344-349), as ONE gather that also forms the sum, in the operands' order:
+ *   dx = ((base + A^T dy0) + A^T dy1) + A^T embed(dyf)      with A^T = dcv_aug_apply_backward and embed() placing the (N, C, 1, H, W) cotangent at frame `frame`.
+ * base (already in the clip's own space), dy1 and dyf may be NULL (with their dims), not all of dy0, dy1, dyf.  With the identity row every A^T moves bits, so the sum
+ * is the one the un-augmented fan-in forms, addition for addition.  dx: any strided view (e.g. the clip's own layout), as for dcv_aug_apply_backward. */
+int dcv_aug_fan_backward(const float* base, const dcv_dims5* based, const float* dy0, const dcv_dims5* dy0d, const float* dy1, const dcv_dims5* dy1d,
+                         const float* dyf, const dcv_dims5* dyfd, int frame, const int32_t* table, int table_rows, float* dx, const dcv_dims5* dxd, int colour,
+                         int flip_negate_channel, void* stream);
+/* The state block: DCV_AUG_STATE_WORDS 32-bit words in device memory, owned by the caller, who initialises it once (p, everything else 0). */
+#define DCV_AUG_P 0            /* fp32 bits: the probability of each enabled transform                                          */
+#define DCV_AUG_SUM_SIGN 1     /* int32: sum of sign(D(real)) since the last adjustment                                        */
+#define DCV_AUG_COUNT 2        /* int32: logits observed since the last adjustment                                             */
+#define DCV_AUG_ADJUSTS 3      /* int32: adjustments made                                                                      */
+#define DCV_AUG_STATE_WORDS 8  /* words 4-7 reserved, zero                                                                     */
+#define DCV_AUG_FLIP 1
+#define DCV_AUG_TRANSLATE 2
+#define DCV_AUG_CUTOUT 4
+#define DCV_AUG_COLOUR 8
+typedef struct dcv_aug_limits {      /* a host struct, passed by value to the kernel */
+    int32_t mx, my;                  /* |dx| <= mx, |dy| <= my                                           */
+    int32_t size;                    /* side of the cutout box                                           */
+    int32_t mask;                    /* DCV_AUG_FLIP | _TRANSLATE | _CUTOUT | _COLOUR: the enabled ops   */
+    float contrast, brightness;      /* gain in 1 + 2 contrast (u - 0.5), bias in brightness (u - 0.5)   */
+} dcv_aug_limits;
+/* One thread per clip draws its row: Philox4x32-10 with key = seed, counter = {idx lo, idx hi, offset lo, offset hi}, block j of clip b at idx = 4 b + j, words
+ * w0..w3 of a block; u(r) = ((float)r + 0.5f) * 2^-32 in (0, 1].  p = state[DCV_AUG_P], read on the device.  A gate is on <=> its op is enabled and u <= p.
+ *   block 0: w0 flip gate; flip = gate && (w1 >> 31); w2 translate gate          block 1: dx = (int)(w0 % (2 mx + 1)) - mx; dy likewise from w1, my; w2 cutout gate
+ *   block 2: cut_y0 = (int)(w0 % H) - size / 2; cut_x0 = (int)(w1 % W) - size / 2; w2 colour gate
+ *   block 3: gain = 1 + (2 contrast) * (u(w0) - 0.5), bias = brightness * (u(w1) - 0.5), every operation rounded to fp32 on its own.
+ * A gate that is off writes its op's identity words: p = 0 gives identity rows, p = 1 turns every enabled gate on. */
+int dcv_aug_draw(int32_t* table, int B, int H, int W, const int32_t* state, const dcv_aug_limits* limits, uint64_t seed, uint64_t offset, void* stream);
+/* state[SUM_SIGN] += sum sign(logits[i]) (sign(0) = 0, a NaN counts 0), state[COUNT] += n.  One workgroup, integer sums: exact and repeatable.  1 <= n <= 2^24. */
+int dcv_aug_observe(const float* logits, int64_t n, int32_t* state, void* stream);
+/* ADA's rule (Karras et al. 2020) with r = E[sign(D(real))], one thread: if COUNT > 0: r = SUM_SIGN / COUNT in double, p = min(max(p + sgn(r - target) * step, 0), p_max)
+ * in fp32 (sgn(0) = 0).  Then SUM_SIGN = COUNT = 0 and ADJUSTS += 1.  The host calls it every `interval` iterations; nothing is read back. */
+int dcv_aug_adjust(int32_t* state, double target, float step, float p_max, void* stream);
+
 /* ---- bf16 channels-last ("CL16") data path -------------------------------------------------- *
  * BASELINE.json configs[2] ("surreal-depth1, bf16 MFMA") and configs[4] ("fp16 MFMA") name 16-bit variants of the same step
  * (config/surreal-depth1.yml:5,47-76, config/isogd-flow.yml; the reference itself is fp32-only).  This is that path as a DATA path:
