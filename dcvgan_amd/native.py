@@ -143,6 +143,9 @@ _SIGS = {
     "dcv_aug_draw": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_uint64, C.c_uint64, _P]),
     "dcv_aug_observe": (C.c_int, [_P, C.c_int64, _P, _P]),
     "dcv_aug_adjust": (C.c_int, [_P, C.c_double, C.c_float, C.c_float, _P]),
+    # LeCam regularisation of the discriminators (added symbols only: the ABI version stays 4)
+    "dcv_lecam_sums": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P]),
+    "dcv_lecam_apply": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, C.c_double, C.c_int, C.c_double, C.c_int, _P, _P, _P, _P, _P]),
     # synchronised BatchNorm for data parallel, fp32 path (added symbols only: the ABI version stays 4)
     "dcv_bn_sync_row_doubles": (C.c_size_t, [C.c_int]),
     "dcv_bn_sync_sums": (C.c_int, [_P, _D, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),

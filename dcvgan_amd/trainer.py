@@ -97,6 +97,15 @@ def build_augment(cfg: StepConfig, models, optimizers, **kw) -> "augment.ClipAug
     return augment.ClipAugment(cfg, next(models["idis"].parameters()).device, **kw)
 
 
+def build_lecam(cfg: StepConfig, models, optimizers, **kw) -> "lecam.LeCam":
+    """LeCam regularisation of the three discriminators (lecam.LeCam) on the models' device; keyword arguments are the constructor's (weight — required —
+    decay, start, one_sided).  Hand it to StepRunner(..., lecam=...).  fp32 path only.  Under data parallelism every rank makes this call (it creates a process
+    group)."""
+    from . import lecam
+    kw.setdefault("device", next(models["idis"].parameters()).device)
+    return lecam.LeCam(3, **kw)
+
+
 class StepRunner:
     """`elide_dead_backward=True` builds the D-phase fakes without a tape (they are detached): the
     reference backpropagates `loss_dis` through cgen/ggen too (trainer.py:304-319, fakes not detached)
@@ -106,8 +115,12 @@ class StepRunner:
 
     def __init__(self, cfg: StepConfig, models, optimizers, loss, sync_losses: bool = False, elide_dead_backward: bool = False,
                  side_streams: Optional[bool] = None, ema: Optional["optim.ModelEma"] = None, spectral: Optional["optim.SpectralNorm"] = None,
-                 augment: Optional["augment.ClipAugment"] = None):
+                 augment: Optional["augment.ClipAugment"] = None, lecam: Optional["lecam.LeCam"] = None):
         self.cfg, self.models, self.opt, self.loss = cfg, models, optimizers, loss
+        # lecam.LeCam (build_lecam): the D phase forms its three losses through it — loss_idis / loss_vdis / loss_gdis of step()'s result then INCLUDE their regulariser
+        # term, which the result also carries alone as lecam_idis / lecam_vdis / lecam_gdis — and the anchors move every iteration, also one whose D update is gated
+        # off or skipped by the guard (they are statistics of the outputs, not of the weights); the G phase is untouched; None leaves the iteration as it is
+        self.lecam = lecam
         # augment.ClipAugment (build_augment): the real pair and each phase's fakes pass through it on their way to the discriminators (cgen still reads the
         # un-augmented geometry clip); None leaves the iteration as it is
         self.augment = augment
@@ -244,9 +257,12 @@ class StepRunner:
             for y in y_real:
                 self.augment.observe(y)      # r = E[sign(D(real))]: integer sums on the device (adaptive mode only)
         self._mark("D: discriminators forward on the fakes")
-        loss_idis = self.loss.compute_dis_loss(y_real[0], y_fake[0])
-        loss_vdis = self.loss.compute_dis_loss(y_real[1], y_fake[1])
-        loss_gdis = self.loss.compute_dis_loss(y_real[2], y_fake[2])
+        if self.lecam is not None:
+            loss_idis, loss_vdis, loss_gdis = self.lecam.compute_dis_losses(self.loss, y_real, y_fake)      # the GAN terms + the regulariser: 2 more launches
+        else:
+            loss_idis = self.loss.compute_dis_loss(y_real[0], y_fake[0])
+            loss_vdis = self.loss.compute_dis_loss(y_real[1], y_fake[1])
+            loss_gdis = self.loss.compute_dis_loss(y_real[2], y_fake[2])
         loss_dis = ops.sum_scalars(loss_idis, loss_vdis, loss_gdis) if loss_idis.is_cuda else loss_idis + loss_vdis + loss_gdis      # trainer.py:315
         if self.iteration % c.num_gen_update == 0:
             loss_dis.backward(guard_dis.root(loss_dis) if guard_dis is not None else self._root(loss_dis))
@@ -265,6 +281,9 @@ class StepRunner:
             out = {"loss_idis": loss_idis.cpu().item(), "loss_vdis": loss_vdis.cpu().item(), "loss_gdis": loss_gdis.cpu().item()}
         else:
             out = {"loss_idis": loss_idis.detach(), "loss_vdis": loss_vdis.detach(), "loss_gdis": loss_gdis.detach()}
+        if self.lecam is not None:
+            reg = self.lecam.reg.cpu().tolist() if self.sync_losses else self.lecam.reg      # (this iteration's own tensor: the next one writes another)
+            out["lecam_idis"], out["lecam_vdis"], out["lecam_gdis"] = reg[0], reg[1], reg[2]
         if guard_dis is not None:
             self._guard_report(out, guard_dis, "dis")
         if self.augment is not None:

@@ -450,6 +450,36 @@ int dcv_aug_observe(const float* logits, int64_t n, int32_t* state, void* stream
  * in fp32 (sgn(0) = 0).  Then SUM_SIGN = COUNT = 0 and ADJUSTS += 1.  The host calls it every `interval` iterations; nothing is read back. */
 int dcv_aug_adjust(int32_t* state, double target, float step, float p_max, void* stream);
 
+/* ---- LeCam regularisation of the discriminators (Tseng et al. 2021), anchors kept on the device, fp32 ------ *
+ * The reference's discriminator losses are loss.py:91-99,163-164 alone; these entries add weight * (mean(relu(D(real) - aF)^2) + mean(relu(aR - D(fake))^2)) to the
+ * value and the stored gradient dcv_gan_loss left, with the anchors aR / aF = an EMA of each discriminator's mean logit on the real / fake batch
+ * (added symbols only: the ABI version stays 4).  Tables (y_real[], y_fake[], n_real[], n_fake[], loss[], dy_real[], dy_fake[]) are HOST arrays of n_dis entries.
+ * The state: n_dis blocks of DCV_LECAM_STATE_WORDS 32-bit words in device memory, owned by the caller, who zeroes it once.                                 */
+#define DCV_LECAM_ANCHOR_REAL 0   /* fp32 bits: EMA of mean D(real)                                                               */
+#define DCV_LECAM_ANCHOR_FAKE 1   /* fp32 bits: EMA of mean D(fake)                                                               */
+#define DCV_LECAM_UPDATES 2       /* int32: anchor updates applied so far                                                         */
+#define DCV_LECAM_ACTIVE 3        /* int32: 1 if the last apply added the regulariser                                             */
+#define DCV_LECAM_STATE_WORDS 8   /* words 4-7 reserved, zero                                                                     */
+/* sums[k] = {sum y_real[k], (double)n_real[k], sum y_fake[k], (double)n_fake[k]} (sums: n_dis x 4 doubles in device memory).  THE SUM ORDER, here and for S_d, S_e
+ * below: 256 lanes; lane l adds elements l, l + 256, ... in increasing index, each converted to double first, into a double that starts at +0.0; then for
+ * s = 128, 64, .., 1 every lane l < s does p[l] += p[l + s]; the result is p[0].  One launch (one workgroup per discriminator), no atomics: the same input gives the
+ * same bits.  Sums are additive over ranks: a data-parallel caller all-reduces `sums` (SUM) between the two entries. */
+int dcv_lecam_sums(int n_dis, const float* const* y_real, const float* const* y_fake, const int64_t* n_real, const int64_t* n_fake, double* sums, void* stream);
+/* For each discriminator k, with aR, aF, U = the state's anchors and UPDATES as they are BEFORE this call (the anchors are constants: no gradient flows through them):
+ *   1. active = (U >= max(start, 1)); state[ACTIVE] = active.
+ *   2. d_i = y_real[i] - aF, e_i = aR - y_fake[i], one fp32 subtraction each; one_sided: d_i = (d_i < 0 ? 0 : d_i), e_i likewise (a NaN stays a NaN).
+ *      R = S_d / n_real + S_e / n_fake in double, S_d = sum (double)d_i * (double)d_i and S_e likewise, in the order above; r = (float)(weight * R), rounded once.
+ *      active:     *loss[k] += r (one fp32 add); dy_real[k][i] += c_r * d_i; dy_fake[k][i] -= c_f * e_i with c_r = (float)(2 * weight / n_real), c_f likewise; product
+ *                  and sum are rounded on their own (never one fma); reg[k] = r.
+ *      not active: no byte of loss[k], dy_real[k], dy_fake[k] is written; reg[k] = 0.
+ *   3. m_r = sums[k][0] / sums[k][1], m_f = sums[k][2] / sums[k][3] in double.  Either non-finite: the anchors and UPDATES stay as they are.  Else U == 0:
+ *      aR = (float)m_r, aF = (float)m_f; otherwise aR = (float)((double)aR * decay + m_r * (1 - decay)), rounded once, aF likewise.  Then UPDATES += 1.
+ * loss[k]: one 0-d device float; dy_*[k]: n_*[k] floats, read and modified.  One launch.  DCV_EINVAL before any launch unless 1 <= n_dis <= 8, 1 <= n <= 2^24 per
+ * tensor, decay in [0, 1], weight finite and >= 0, no pointer NULL. */
+int dcv_lecam_apply(int n_dis, const float* const* y_real, const float* const* y_fake, const int64_t* n_real, const int64_t* n_fake, const double* sums,
+                    int32_t* state, double decay, int start, double weight, int one_sided, float* const* loss, float* const* dy_real, float* const* dy_fake,
+                    float* reg, void* stream);
+
 /* ---- bf16 channels-last ("CL16") data path -------------------------------------------------- *
  * BASELINE.json configs[2] ("surreal-depth1, bf16 MFMA") and configs[4] ("fp16 MFMA") name 16-bit variants of the same step
  * (config/surreal-depth1.yml:5,47-76, config/isogd-flow.yml; the reference itself is fp32-only).  This is that path as a DATA path:
