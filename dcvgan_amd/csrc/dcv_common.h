@@ -107,6 +107,29 @@ __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uin
 }
 }  // namespace dcv
 namespace dcv {
+// The input pipeline's per-element arithmetic (dataset.py:125-181), shared by the batch decoders (elementwise.hip) and the clip store's gather (clipstore.hip): one
+// definition, so a gathered batch holds the bytes the decoders write.  numpy's fp32 operation order, every operation rounded on its own.
+__device__ __forceinline__ float decode_value(float v, float div, float sub) {      // dataset.py:131, 168, 174
+#pragma clang fp contract(off)
+    return v / div - sub;
+}
+__device__ __forceinline__ float onehot_value(int label, int c) { return c == label ? 1.f : 0.f; }      // dataset.py:180
+// SURREAL depth (dataset.py:137-156): foreground = depth < 1e10; its min and max start at +-3.4e38
+__device__ __forceinline__ void surreal_fold(float v, float& lo, float& hi) {
+    if (v < 1e10f) { lo = fminf(lo, v); hi = fmaxf(hi, v); }
+}
+__device__ __forceinline__ float surreal_value(float v, float mi, float ma) {
+#pragma clang fp contract(off)   // numpy rounds h*1.8 before subtracting; no fma
+    float o = 1.0f;                                        // background
+    if (v < 1e10f) {
+        float h = v;
+        if (ma - mi > 0.f) h = (v - mi) / (ma - mi);
+        o = h * 1.8f - 1.0f;                               // [-1.0, 0.8]
+    }
+    return o;
+}
+}  // namespace dcv
+namespace dcv {
 // n / d for the FastDiv above (d == 1 handled by mul == 0 convention)
 __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv f) {
     if (f.div == 1) return n;

@@ -1582,7 +1582,7 @@ __global__ __launch_bounds__(256) void decode_video_kernel(const TIN* __restrict
     const int c = (int)(r % Cc);
     const int64_t b = r / Cc;
     const float v = (float)in[((b * BT_per_B + t) * HW + hw) * Cc + c];
-    out[i] = v / div - sub;
+    out[i] = decode_value(v, div, sub);
 }
 
 // SURREAL depth (dataset.py:137-156): foreground = depth < 1e10; min-max of the foreground per clip
@@ -1591,8 +1591,7 @@ __global__ __launch_bounds__(256) void surreal_minmax_kernel(const float* __rest
     const float* p = d + (int64_t)blockIdx.x * per_clip;
     float lo = 3.4e38f, hi = -3.4e38f;
     for (int64_t i = threadIdx.x; i < per_clip; i += 256) {
-        const float v = p[i];
-        if (v < 1e10f) { lo = fminf(lo, v); hi = fmaxf(hi, v); }
+        surreal_fold(p[i], lo, hi);
     }
     for (int o = 32; o > 0; o >>= 1) { lo = fminf(lo, __shfl_xor(lo, o, 64)); hi = fmaxf(hi, __shfl_xor(hi, o, 64)); }
     if ((threadIdx.x & 63) == 0) { smin[threadIdx.x >> 6] = lo; smax[threadIdx.x >> 6] = hi; }
@@ -1607,14 +1606,7 @@ __global__ __launch_bounds__(256) void surreal_norm_kernel(const float* __restri
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const int64_t b = i / per_clip;
-    const float v = d[i], mi = mm[2 * b], ma = mm[2 * b + 1];
-    float o = 1.0f;                                        // background
-    if (v < 1e10f) {
-        float h = v;
-        if (ma - mi > 0.f) h = (v - mi) / (ma - mi);
-        o = h * 1.8f - 1.0f;                               // [-1.0, 0.8]
-    }
-    out[i] = o;
+    out[i] = surreal_value(d[i], mm[2 * b], mm[2 * b + 1]);
 }
 
 
@@ -1693,7 +1685,7 @@ __global__ __launch_bounds__(256) void segm_decode_kernel(const uint8_t* __restr
     if (p >= P) return;
     const int64_t b = p / per_clip, r = p % per_clip;
     const int l = labels[p];
-    for (int c = 0; c < C; ++c) out[(b * C + c) * per_clip + r] = c == l ? 1.f : 0.f;
+    for (int c = 0; c < C; ++c) out[(b * C + c) * per_clip + r] = onehot_value(l, c);
 }
 
 }  // namespace dcv

@@ -146,6 +146,10 @@ _SIGS = {
     # LeCam regularisation of the discriminators (added symbols only: the ABI version stays 4)
     "dcv_lecam_sums": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P]),
     "dcv_lecam_apply": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, C.c_double, C.c_int, C.c_double, C.c_int, _P, _P, _P, _P, _P]),
+    # the device-resident dataset (added symbols only: the ABI version stays 4)
+    "dcv_clipstore_draw": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_uint64, C.c_uint64, C.c_int64, _P]),
+    "dcv_clipstore_gather": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P]),
+    "dcv_clipstore_surreal": (C.c_int, [_P, C.c_int, C.c_int64, _P]),
     # synchronised BatchNorm for data parallel, fp32 path (added symbols only: the ABI version stays 4)
     "dcv_bn_sync_row_doubles": (C.c_size_t, [C.c_int]),
     "dcv_bn_sync_sums": (C.c_int, [_P, _D, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),

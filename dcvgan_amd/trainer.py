@@ -106,6 +106,17 @@ def build_lecam(cfg: StepConfig, models, optimizers, **kw) -> "lecam.LeCam":
     return lecam.LeCam(3, **kw)
 
 
+def build_clip_sampler(cfg: StepConfig, store, **kw) -> "clipstore.ClipSampler":
+    """The real batches of the run, made on the device from a clipstore.ClipStore instead of a DataLoader (train.py:101-109, trainer.py:271): per-rank
+    batches of cfg.batchsize; keyword arguments are the sampler's (seed, rank, world — by default torch.initial_seed() and torch.distributed's rank and world).  Feed
+    ``runner.step(batch["color"], batch[cfg.geometric_info], t_rand)``.  No collective call: every rank computes its own slice of the epoch."""
+    from . import clipstore
+    if store.geometric_info != cfg.geometric_info or store.video_length != cfg.video_length:
+        raise ValueError(f"build_clip_sampler: the store holds {store.geometric_info} clips of {store.video_length} frames, the config asks for "
+                         f"{cfg.geometric_info} clips of {cfg.video_length}")
+    return clipstore.ClipSampler(store, kw.pop("batchsize", cfg.batchsize), **kw)
+
+
 class StepRunner:
     """`elide_dead_backward=True` builds the D-phase fakes without a tape (they are detached): the
     reference backpropagates `loss_dis` through cgen/ggen too (trainer.py:304-319, fakes not detached)

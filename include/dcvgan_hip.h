@@ -480,6 +480,33 @@ int dcv_lecam_apply(int n_dis, const float* const* y_real, const float* const* y
                     int32_t* state, double decay, int start, double weight, int one_sided, float* const* loss, float* const* dy_real, float* const* dy_fake,
                     float* reg, void* stream);
 
+/* ---- the device-resident dataset: clips sampled and decoded on the device (added symbols only: the ABI version stays 4) ------ *
+ * A stream's store is ONE packed buffer: the frames of all N videos back to back in disk order, video i at frames starts[i] .. starts[i+1] - 1 (`starts`: N + 1
+ * int64 in device memory, a prefix sum of the frame counts of list.txt, dataset.py:86-97).  A batch is a (B, 2) int32 device table of rows (clip, t0): the clip is
+ * frames t0 .. t0 + T - 1 of video `clip`.
+ *
+ * dcv_clipstore_draw replaces the DataLoader's shuffle (train.py:101-109: shuffle=True, drop_last=True; trainer.py:271) and the window draw of
+ * dataset.py:116-123.  Row b is epoch position p = first_position + b (0 <= first_position, first_position + B <= N):
+ *   clip = perm(p): a balanced Feistel network of 8 rounds on w = 2 h bits, w the smallest even width with 2^w >= N (at least 2), applied again while the value
+ *          is >= N (cycle walking).  Round r: (L, R) <- (R, L ^ F_r(R)), starting from L = x >> h, R = x & (2^h - 1) and ending at x = L << h | R;
+ *          F_r(R) = word 0 of Philox4x32-10(counter {R, r, epoch lo, epoch hi}, key {seed lo, seed hi}) & (2^h - 1).
+ *   n = starts[clip + 1] - starts[clip];  t0 = 0 if n <= T, else mulhi32(u, n - T) in [0, n - T - 1] (np.random.randint(n - T), dataset.py:122: the last window
+ *          is never drawn), u = word 0 of Philox4x32-10(counter {p, 0xFFFFFFFF, epoch lo, epoch hi}, same key).
+ * One launch, one thread per row, no state: any position of any epoch is computed on its own.  1 <= N < 2^31. */
+int dcv_clipstore_draw(int32_t* table, int B, const int64_t* starts, int64_t N, int T, uint64_t seed, uint64_t epoch, int64_t first_position, void* stream);
+#define DCV_CLIP_U8 0       /* frames uint8 (F, H, W, C), 1 <= C <= 4: out = (float)x / div - sub   (colour, grey depth: div 127.5, sub 1; dataset.py:127-131, 158-166) */
+#define DCV_CLIP_F32 1      /* frames fp32 (F, H, W, C), 1 <= C <= 4: out = x / div - sub           (optical flow: div image_size, sub 0; dataset.py:168-174)        */
+#define DCV_CLIP_LABELS 2   /* frames uint8 (F, H, W): out = one-hot with C parts, C <= 256; div and sub unused (dataset.py:176-181)                                  */
+/* out (B, C, T, H, W) fp32 contiguous = the table's windows of `frames`, normalised with the expressions of dcv_decode_video / dcv_decode_segmentation (one
+ * definition, dcv_common.h): the bytes dataprep.decode_* writes for the same frames.  One launch.  All frame addressing is 64-bit; 16-byte loads where the window's
+ * ADDRESS allows, 4-byte or single-byte loads otherwise.  A row that does not name T frames of one video (never drawn; the Python layer refuses it) is written as
+ * NaN (one-hot: zeros) and nothing is read for it.  1 <= B <= 65535. */
+int dcv_clipstore_gather(const void* frames, int mode, const int32_t* table, const int64_t* starts, int64_t N, int B, int T, int H, int W, int C, float div, float sub,
+                         float* out, void* stream);
+/* SURREAL depth (dataset.py:134-156), in place on `clips` = B gathered raw windows of per_clip fp32 metres each (DCV_CLIP_F32, C 1, div 1, sub 0): the foreground
+ * (< 1e10) min-max of the WINDOW goes to [-1, 0.8], background 1.0 — dcv_surreal_depth's arithmetic.  One launch, one workgroup per clip. */
+int dcv_clipstore_surreal(float* clips, int B, int64_t per_clip, void* stream);
+
 /* ---- bf16 channels-last ("CL16") data path -------------------------------------------------- *
  * BASELINE.json configs[2] ("surreal-depth1, bf16 MFMA") and configs[4] ("fp16 MFMA") name 16-bit variants of the same step
  * (config/surreal-depth1.yml:5,47-76, config/isogd-flow.yml; the reference itself is fp32-only).  This is that path as a DATA path:
