@@ -6,28 +6,8 @@
 
 namespace dcv {
 
-static const int CLIP_FEISTEL_ROUNDS = 8;
-
 // ---- the draw ------------------------------------------------------------------------------------------------------------------------------------------------
-// perm(seed, epoch, .): a keyed bijection on [0, N).  A balanced Feistel network on w = 2 h bits (the smallest even width with 2^w >= N, at least 2) is a bijection
-// on [0, 2^w) whatever its round function is; walking its cycle until the value is below N restricts it to [0, N) (Black & Rogaway 2002).  2^w < 4 N, so the walk
-// takes fewer than four network passes on average.  Round r maps (L, R) to (R, L ^ F_r(R)), F_r(R) = the low h bits of word 0 of Philox4x32-10 with counter
-// {R, r, epoch lo, epoch hi} and key (seed lo, seed hi).
-__device__ __forceinline__ uint32_t clip_perm(uint32_t x, uint32_t N, int h, uint32_t k0, uint32_t k1, uint32_t e0, uint32_t e1) {
-    const uint32_t mask = (1u << h) - 1u;
-    do {
-        uint32_t L = x >> h, R = x & mask;
-        for (int r = 0; r < CLIP_FEISTEL_ROUNDS; ++r) {
-            uint32_t c[4] = {R, (uint32_t)r, e0, e1};
-            philox4x32_10(c, k0, k1);
-            const uint32_t t = L ^ (c[0] & mask);
-            L = R; R = t;
-        }
-        x = (L << h) | R;
-    } while (x >= N);
-    return x;
-}
-
+// clip = clip_perm(position) under (seed, epoch): the keyed bijection on [0, N) of dcv_common.h (the kernel distance draws its subsets with it too).
 // One thread per row.  The window start of a video of n > T frames is mulhi32(u, n - T) in [0, n - T - 1] (np.random.randint(n - T) of dataset.py:122: the last
 // window is never drawn), u = word 0 of Philox with counter {position, 0xFFFFFFFF, epoch lo, epoch hi}: no Feistel round has that counter (r < 2^32 - 1).
 __global__ __launch_bounds__(64) void clip_draw_kernel(int32_t* __restrict__ table, int B, const int64_t* __restrict__ starts, uint32_t N, int T, int h, uint32_t k0,
@@ -199,10 +179,7 @@ int dcv_clipstore_draw(int32_t* table, int B, const int64_t* starts, int64_t N, 
     if (first_position < 0 || first_position + B > N)
         return fail(DCV_EINVAL, "clipstore_draw: positions %lld .. %lld are not inside the epoch's [0, %lld)", (long long)first_position, (long long)first_position + B - 1,
                     (long long)N);
-    int bits = 0;
-    while ((1ll << bits) < N) ++bits;
-    const int w = bits + (bits & 1) < 2 ? 2 : bits + (bits & 1);
-    hipLaunchKernelGGL(clip_draw_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream), table, B, starts, (uint32_t)N, T, w / 2,
+    hipLaunchKernelGGL(clip_draw_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream), table, B, starts, (uint32_t)N, T, clip_perm_half_bits(N),
                        (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)epoch, (uint32_t)(epoch >> 32), (uint32_t)first_position);
     DCV_LAUNCH_CHECK();
     return DCV_OK;

@@ -107,6 +107,35 @@ __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uin
 }
 }  // namespace dcv
 namespace dcv {
+// The keyed bijection of the library's shuffles (clipstore.hip: the epoch's order; evalstats.hip: the kernel distance's subsets).
+static const int CLIP_FEISTEL_ROUNDS = 8;
+// perm(seed, epoch, .): a keyed bijection on [0, N).  A balanced Feistel network on w = 2 h bits (the smallest even width with 2^w >= N, at least 2) is a bijection
+// on [0, 2^w) whatever its round function is; walking its cycle until the value is below N restricts it to [0, N) (Black & Rogaway 2002).  2^w < 4 N, so the walk
+// takes fewer than four network passes on average.  Round r maps (L, R) to (R, L ^ F_r(R)), F_r(R) = the low h bits of word 0 of Philox4x32-10 with counter
+// {R, r, epoch lo, epoch hi} and key (seed lo, seed hi).
+__device__ __forceinline__ uint32_t clip_perm(uint32_t x, uint32_t N, int h, uint32_t k0, uint32_t k1, uint32_t e0, uint32_t e1) {
+    const uint32_t mask = (1u << h) - 1u;
+    do {
+        uint32_t L = x >> h, R = x & mask;
+        for (int r = 0; r < CLIP_FEISTEL_ROUNDS; ++r) {
+            uint32_t c[4] = {R, (uint32_t)r, e0, e1};
+            philox4x32_10(c, k0, k1);
+            const uint32_t t = L ^ (c[0] & mask);
+            L = R; R = t;
+        }
+        x = (L << h) | R;
+    } while (x >= N);
+    return x;
+}
+// h of clip_perm for [0, N): half the smallest even width that covers it, at least 1
+inline int clip_perm_half_bits(int64_t N) {
+    int bits = 0;
+    while ((1ll << bits) < N) ++bits;
+    const int w = bits + (bits & 1) < 2 ? 2 : bits + (bits & 1);
+    return w / 2;
+}
+}  // namespace dcv
+namespace dcv {
 // The input pipeline's per-element arithmetic (dataset.py:125-181), shared by the batch decoders (elementwise.hip) and the clip store's gather (clipstore.hip): one
 // definition, so a gathered batch holds the bytes the decoders write.  numpy's fp32 operation order, every operation rounded on its own.
 __device__ __forceinline__ float decode_value(float v, float div, float sub) {      // dataset.py:131, 168, 174

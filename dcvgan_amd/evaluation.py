@@ -1,0 +1,515 @@
+"""On-device evaluation: Inception score, Fréchet distance and kernel distance.
+
+The reference's ``Trainer.evaluate`` (trainer.py:171-224) generates ``eval_num_samples`` clips, moves the generators to the CPU, writes every clip
+as an mp4 and lets an external package read the files back for IS / FID / PRD.  Here the clips and their features stay in device memory.  The feature network is the
+caller's, handed over as a callable; everything after it is this module's:
+
+* ``FeatureMoments``: streaming mean and covariance of the features (``dcv_eval_moments_update``: fp32 features, fp64 sums on the fp64 matrix pipe),
+* ``InceptionStats``: the sums the Inception score is finalised from (``dcv_eval_inception_update``: an fp64 softmax per row),
+* ``kernel_distance``: KID with the cubic polynomial kernel over drawn subsets (``dcv_eval_kid_draw`` + ``dcv_eval_kid_sums``; the m x m kernel matrices are never
+  written),
+* ``frechet_distance``: the O(D^3) eigenvalue step on the host in numpy — it runs once per evaluation and produces a number for the host's logger anyway,
+* ``Evaluator``: generator -> extractor -> statistics without a clip or a feature crossing PCIe.
+
+Every accumulation has one fixed order and no floating-point atomic: the same sequence of calls gives the same bits.  ``draw_host`` is an integer-exact numpy mirror
+of the subset draw, as ``clipstore.permute_host`` is of the epoch shuffle: the specification the kernel is tested against.  PRD (its k-means) is not attempted.
+"""
+from __future__ import annotations
+
+from typing import Callable, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import clipstore
+from . import native as N
+from .native import NativeError, check, lib, ptr, stream_ptr
+
+MAX_DIM = 4096                       # features per row (D) and classes per row (K): the kernels' limit
+MAX_SUBSETS, MAX_SUBSET_SIZE = 4096, 65536
+KID_SALT = 0x9FB21C651E98DF25        # DCV_EVAL_KID_SALT: the draw's Philox key is the seed plus this constant
+_M64 = 0xFFFFFFFFFFFFFFFF
+METRICS = ("is", "fid", "kid")
+
+_STATS = {"launches": 0}
+
+
+def launches() -> int:
+    """Kernel launches this module has issued so far, in this process (dcv_eval_inception_update and dcv_eval_kid_sums are two each, every other entry one)."""
+    return _STATS["launches"]
+
+
+def _call(name: str, n_launches: int, *args):
+    check(getattr(lib(), name)(*args), name)
+    _STATS["launches"] += n_launches
+
+
+def _device(device) -> torch.device:
+    from . import util
+    return torch.device(device if device is not None else util.current_device())
+
+
+def _rows(t, width: Optional[int], what: str) -> Tuple[int, int, int]:
+    """(n, width, row stride in elements) of a (n, width) fp32 device tensor whose rows are dense; a row-strided view is taken as it is, anything else is refused."""
+    if not isinstance(t, torch.Tensor):
+        raise NativeError(f"{what}: expected a tensor, got {type(t).__name__}")
+    N._require(t, what)
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1 or (width is not None and t.shape[1] != width):
+        raise NativeError(f"{what}: expected a (n, {width if width is not None else 'D'}) tensor with n >= 1, got {tuple(t.shape)}")
+    n, w = int(t.shape[0]), int(t.shape[1])
+    if w > MAX_DIM or n >= 2 ** 31:
+        raise NativeError(f"{what}: at most {MAX_DIM} values per row and fewer than 2^31 rows, got {tuple(t.shape)}")
+    stride = int(t.stride(0)) if n > 1 else w
+    if (w > 1 and t.stride(1) != 1) or stride < w:
+        raise NativeError(f"{what}: rows must be dense and at least a row apart (a row-strided view is fine), got strides {tuple(t.stride())} for shape {tuple(t.shape)}")
+    return n, w, stride
+
+
+_ZERO_ROW = 1024      # fp32 words of the zero row a state is cleared from; a state buffer is a whole number of such rows (512 doubles)
+_ZEROS = {}
+
+
+def _state_buffer(n_doubles: int, device) -> torch.Tensor:
+    """One flat fp64 buffer for an additive state and, in its last used slot, the row count during a collective: zeros, padded to whole zero rows.  A host tensor
+    copied over once (no kernel)."""
+    padded = -(-int(n_doubles) // (_ZERO_ROW // 2)) * (_ZERO_ROW // 2)
+    return torch.zeros((padded,), dtype=torch.float64).to(device)
+
+
+def _clear(buf: torch.Tensor) -> None:
+    """buf <- 0 on the device by the library's strided copy (dcv_axpby, one launch) of a zero row broadcast over the buffer's rows — a copy, not a scaling, so a NaN
+    left by an earlier stream does not survive; on the host torch's fill."""
+    if not buf.is_cuda:
+        buf.zero_()
+        return
+    from . import ops
+    key = str(buf.device)
+    if key not in _ZEROS:
+        _ZEROS[key] = torch.zeros(_ZERO_ROW, dtype=torch.float32).to(buf.device)
+    rows = buf.numel() * 2 // _ZERO_ROW
+    ops._axpby(_ZEROS[key].view(1, 1, 1, 1, _ZERO_ROW).expand(1, rows, 1, 1, _ZERO_ROW), 1.0, None, 0.0, buf.view(torch.float32).view(1, rows, 1, 1, _ZERO_ROW))
+    _STATS["launches"] += 1
+
+
+def _dist_world(group=None) -> int:
+    import torch.distributed as dist
+    return dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
+
+
+def _all_reduce_state(buf: torch.Tensor, used: int, n: int, group=None) -> int:
+    """ONE collective (SUM) over the state and its row count: the count rides in slot `used` of the state's own buffer as a double (exact below 2^53), so the
+    collective runs on the tensor's device — a backend registered for device tensors alone, as nccl is, serves it — and cannot leave the sums reduced and the count
+    not.  -> the summed count; the slot is zero again afterwards."""
+    import torch.distributed as dist
+    slot = buf[used:used + 1]
+    slot.copy_(torch.tensor([float(n)], dtype=torch.float64))      # host -> device copy, no kernel
+    dist.all_reduce(buf[:used + 1], op=dist.ReduceOp.SUM, group=group)
+    total = int(round(float(slot.cpu().item())))
+    slot.copy_(torch.zeros(1, dtype=torch.float64))
+    return total
+
+
+# --------------------------------------------------------------------------- #
+# feature moments and the Fréchet distance
+# --------------------------------------------------------------------------- #
+class FeatureMoments:
+    """``FeatureMoments(dim, device=None)``: the additive state ``(n, sum, gram)`` of a stream of ``dim``-dimensional features — ``sum`` (dim,) and ``gram`` (dim, dim)
+    fp64 in device memory, the row count on the host, where it is known.  ``update(feats)`` is one launch and no host read; ``mean()`` / ``cov()`` read the state
+    back (host fp64).  On ``device="cpu"`` the object only holds statistics (``load``, ``load_state_dict``): updating it is refused."""
+
+    def __init__(self, dim: int, device=None):
+        if not 1 <= int(dim) <= MAX_DIM:
+            raise ValueError(f"FeatureMoments: 1 <= dim <= {MAX_DIM}, got {dim!r}")
+        self.dim, self.device, self.n = int(dim), _device(device), 0
+        D = self.dim
+        self._buf = _state_buffer(D * D + D + 1, self.device)      # gram, sum, and the slot the row count rides in during all_reduce
+        self.gram, self.sum = self._buf[:D * D].view(D, D), self._buf[D * D:D * D + D]
+
+    def reset(self) -> "FeatureMoments":
+        """Back to no rows: the device state is cleared in place (one launch), nothing is allocated or copied from the host."""
+        _clear(self._buf)
+        self.n = 0
+        return self
+
+    def update(self, feats: torch.Tensor) -> "FeatureMoments":
+        """sum += sum_i x_i, gram += X^T X for a (n, dim) fp32 device tensor (a row-strided view is passed as it is)."""
+        n, _, stride = _rows(feats, self.dim, "FeatureMoments.update")
+        if not self.sum.is_cuda:
+            raise NativeError(f"FeatureMoments: the state is on {self.sum.device} — the moments are accumulated on the GPU only (there is no CPU fallback)")
+        if self.n + n >= 2 ** 53:
+            raise NativeError("FeatureMoments: row count out of range")
+        _call("dcv_eval_moments_update", 1, ptr(feats), n, self.dim, stride, ptr(self.sum), ptr(self.gram), stream_ptr())
+        self.n += n
+        return self
+
+    # ---- host reads ----------------------------------------------------------------------------------------------------------------------------------------
+    def _host(self):
+        return self.sum.cpu().numpy().astype(np.float64), self.gram.cpu().numpy().astype(np.float64)
+
+    def mean(self) -> np.ndarray:
+        if self.n < 1:
+            raise ValueError("FeatureMoments.mean: no rows yet")
+        return self._host()[0] / float(self.n)
+
+    def cov(self) -> np.ndarray:
+        """The unbiased covariance (gram - s s^T / n) / (n - 1), as numpy.cov(rowvar=False) has it."""
+        if self.n < 2:
+            raise ValueError(f"FeatureMoments.cov: at least two rows are needed, got {self.n}")
+        s, g = self._host()
+        return (g - np.outer(s, s) / float(self.n)) / float(self.n - 1)
+
+    def state_dict(self):
+        s, g = self._host()
+        return dict(dim=self.dim, n=int(self.n), sum=s, gram=g)
+
+    def load_state_dict(self, sd) -> "FeatureMoments":
+        s, g = np.asarray(sd["sum"], dtype=np.float64), np.asarray(sd["gram"], dtype=np.float64)
+        if int(sd["dim"]) != self.dim or s.shape != (self.dim,) or g.shape != (self.dim, self.dim) or int(sd["n"]) < 0:
+            raise ValueError(f"FeatureMoments: built for dim {self.dim}, the state has dim {sd['dim']}, sum {s.shape}, gram {g.shape}, n {sd['n']}")
+        self.sum.copy_(torch.from_numpy(np.ascontiguousarray(s)))
+        self.gram.copy_(torch.from_numpy(np.ascontiguousarray(g)))
+        self.n = int(sd["n"])
+        return self
+
+    def save(self, path) -> None:
+        """An .npz with ``mu``, ``sigma``, ``n``: the usual shape of precomputed real statistics."""
+        np.savez(path, mu=self.mean(), sigma=self.cov(), n=np.int64(self.n))
+
+    @classmethod
+    def load(cls, path, device=None) -> "FeatureMoments":
+        """The moments of a saved ``mu`` / ``sigma`` / ``n``: sum = n mu, gram = (n - 1) sigma + n mu mu^T."""
+        with np.load(path) as z:
+            mu, sigma, n = np.asarray(z["mu"], dtype=np.float64), np.asarray(z["sigma"], dtype=np.float64), int(z["n"])
+        if mu.ndim != 1 or sigma.shape != (mu.size, mu.size) or n < 2:
+            raise ValueError(f"FeatureMoments.load: mu {mu.shape}, sigma {sigma.shape}, n {n}")
+        fm = cls(mu.size, device)
+        return fm.load_state_dict(dict(dim=mu.size, n=n, sum=n * mu, gram=(n - 1) * sigma + n * np.outer(mu, mu)))
+
+    def all_reduce(self, group=None) -> "FeatureMoments":
+        """The state is additive: SUM over ``sum``, ``gram`` and ``n`` of every rank, in one collective on the state's device tensor (a collective call; nothing to
+        do in a single process)."""
+        if _dist_world(group) > 1:
+            self.n = _all_reduce_state(self._buf, self.dim * self.dim + self.dim, self.n, group)
+        return self
+
+
+def frechet_distance(a: FeatureMoments, b: FeatureMoments) -> float:
+    """|mu_a - mu_b|^2 + tr S_a + tr S_b - 2 tr (S_a^1/2 S_b S_a^1/2)^1/2 (Heusel et al. 2017) in host fp64, from symmetric eigendecompositions alone.
+
+    With S_a = V diag(w) V^T (``eigh``, w clipped at 0) and R = S_a^1/2 = V diag(sqrt w) V^T, the trace term is sum_i sqrt(max(lambda_i, 0)) over
+    lambda = eigvalsh(R S_b R).  R S_b R = V M V^T with M = diag(sqrt w) (V^T S_b V) diag(sqrt w), so lambda is taken from M, restricted to the directions in which
+    S_a is numerically non-zero (w_i > dim * eps * max w; the others are the clipped ones and rounding noise around them): the same non-zero eigenvalues.  The
+    restriction matters for a rank-deficient S_a (fewer rows than features): a symmetric eigensolver returns the zero eigenvalues of the full matrix as
+    +-eps |M|, whose square roots, 1e-8 |S| each, are the error the sqrtm formulation shows there.  For the same reason a lambda_i below len(lambda) * eps * max lambda
+    (S_b deficient inside the range of S_a) is the solver's noise around zero and counts as zero."""
+    if not isinstance(a, FeatureMoments) or not isinstance(b, FeatureMoments):
+        raise TypeError("frechet_distance: two FeatureMoments")
+    if a.dim != b.dim:
+        raise ValueError(f"frechet_distance: feature dimensions {a.dim} and {b.dim}")
+    mu_a, mu_b, sa, sb = a.mean(), b.mean(), a.cov(), b.cov()
+    w, v = np.linalg.eigh((sa + sa.T) * 0.5)
+    keep = w > a.dim * np.finfo(np.float64).eps * max(float(w.max()), 0.0)
+    r, v = np.sqrt(w[keep]), v[:, keep]
+    m = (v.T @ ((sb + sb.T) * 0.5) @ v) * r[:, None] * r[None, :]
+    lam = np.linalg.eigvalsh((m + m.T) * 0.5) if m.size else np.zeros(0)
+    if lam.size:
+        lam = np.where(lam > lam.size * np.finfo(np.float64).eps * max(float(lam.max()), 0.0), lam, 0.0)
+    d = mu_a - mu_b
+    return float(d @ d + np.trace(sa) + np.trace(sb) - 2.0 * np.sum(np.sqrt(lam)))
+
+
+# --------------------------------------------------------------------------- #
+# the Inception score
+# --------------------------------------------------------------------------- #
+def inception_score_from_state(state, n: int) -> float:
+    """exp(state[K] / n - sum_k pbar_k log pbar_k), pbar = state[:K] / n (Salimans et al. 2016: exp of the mean KL(p(y|x) || p(y))); a class with pbar = 0 adds
+    nothing."""
+    state = np.asarray(state, dtype=np.float64).reshape(-1)
+    if int(n) < 1 or state.size < 2:
+        raise ValueError(f"inception score: at least one row and one class, got n {n}, state of {state.size}")
+    pbar = state[:-1] / float(n)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        marginal = np.where(pbar == 0.0, 0.0, pbar * np.log(pbar))
+    return float(np.exp(state[-1] / float(n) - marginal.sum()))
+
+
+class InceptionStats:
+    """``InceptionStats(num_classes, device=None)``: ``state[k] = sum_i p_ik``, ``state[K] = sum_i sum_k p_ik log p_ik`` as K + 1 doubles in device memory;
+    ``update(logits)`` is two launches and no host read, ``score()`` finalises on the host."""
+
+    def __init__(self, num_classes: int, device=None):
+        if not 1 <= int(num_classes) <= MAX_DIM:
+            raise ValueError(f"InceptionStats: 1 <= num_classes <= {MAX_DIM}, got {num_classes!r}")
+        self.num_classes, self.device, self.n = int(num_classes), _device(device), 0
+        self._buf = _state_buffer(self.num_classes + 2, self.device)      # the K + 1 sums, and the slot the row count rides in during all_reduce
+        self.state = self._buf[:self.num_classes + 1]
+
+    def reset(self) -> "InceptionStats":
+        """Back to no rows: the device state is cleared in place (one launch)."""
+        _clear(self._buf)
+        self.n = 0
+        return self
+
+    def update(self, logits: torch.Tensor) -> "InceptionStats":
+        n, K, stride = _rows(logits, self.num_classes, "InceptionStats.update")
+        if not self.state.is_cuda:
+            raise NativeError(f"InceptionStats: the state is on {self.state.device} — the sums are accumulated on the GPU only (there is no CPU fallback)")
+        need = int(lib().dcv_eval_inception_workspace_bytes(n, K))
+        ws = N.scratch.get("eval_inception", need, logits.device)
+        _call("dcv_eval_inception_update", 2, ptr(logits), n, K, stride, ptr(self.state), ptr(ws), ws.numel(), stream_ptr())
+        self.n += n
+        return self
+
+    def state_host(self) -> np.ndarray:
+        return self.state.cpu().numpy().astype(np.float64)
+
+    def score(self) -> float:
+        return inception_score_from_state(self.state_host(), self.n)
+
+    def state_dict(self):
+        return dict(num_classes=self.num_classes, n=int(self.n), state=self.state_host())
+
+    def load_state_dict(self, sd) -> "InceptionStats":
+        s = np.asarray(sd["state"], dtype=np.float64)
+        if int(sd["num_classes"]) != self.num_classes or s.shape != (self.num_classes + 1,):
+            raise ValueError(f"InceptionStats: built for {self.num_classes} classes, the state has {sd['num_classes']} and shape {s.shape}")
+        self.state.copy_(torch.from_numpy(np.ascontiguousarray(s)))
+        self.n = int(sd["n"])
+        return self
+
+    def all_reduce(self, group=None) -> "InceptionStats":
+        if _dist_world(group) > 1:
+            self.n = _all_reduce_state(self._buf, self.num_classes + 1, self.n, group)
+        return self
+
+
+# --------------------------------------------------------------------------- #
+# the kernel distance
+# --------------------------------------------------------------------------- #
+def draw_host(seed: int, subsets: int, m: int, na: int, nb: int) -> np.ndarray:
+    """The (subsets, 2, m) int32 table dcv_eval_kid_draw writes — integers only, the specification of the kernel.  table[s][side][i] = perm(i): the clip store's
+    keyed bijection (8 Feistel rounds over Philox4x32-10, cycle-walked) on [0, na) for side 0 and [0, nb) for side 1, with key = seed + KID_SALT and the Philox
+    counter {R, r, s, side} in round r."""
+    subsets, m, na, nb = int(subsets), int(m), int(na), int(nb)
+    if not (1 <= subsets <= MAX_SUBSETS and 2 <= m <= MAX_SUBSET_SIZE and m <= na < 2 ** 31 and m <= nb < 2 ** 31):
+        raise ValueError(f"draw_host: 1 <= subsets <= {MAX_SUBSETS}, 2 <= m <= {MAX_SUBSET_SIZE}, m <= na, nb < 2^31; got {subsets}, {m}, {na}, {nb}")
+    key = (int(seed) + KID_SALT) & _M64
+    k0, k1 = key & 0xFFFFFFFF, key >> 32
+    out = np.empty((subsets, 2, m), dtype=np.int32)
+    s_col = np.repeat(np.arange(subsets, dtype=np.uint64), m)
+    for side, n_rows in ((0, na), (1, nb)):
+        h = clipstore.half_bits(n_rows)
+        mask = np.uint64((1 << h) - 1)
+        x = np.tile(np.arange(m, dtype=np.uint64), subsets)
+        todo = np.ones(x.shape, dtype=bool)
+        while todo.any():      # cycle walking: only the values still outside [0, n_rows) go round again
+            v = x[todo]
+            L, R = v >> np.uint64(h), v & mask
+            for r in range(clipstore.FEISTEL_ROUNDS):
+                f = clipstore.philox4x32_10(R, r, s_col[todo], side, k0, k1)[0] & mask
+                L, R = R, L ^ f
+            v = (L << np.uint64(h)) | R
+            x[todo] = v
+            todo[todo] = v >= np.uint64(n_rows)
+        out[:, side, :] = x.reshape(subsets, m).astype(np.int32)
+    return out
+
+
+def mmd2_from_sums(out, m: int) -> np.ndarray:
+    """MMD^2_s = out0 / (m (m - 1)) + out1 / (m (m - 1)) - 2 out2 / m^2 per subset: the unbiased estimator of Binkowski et al. 2018."""
+    o = np.asarray(out, dtype=np.float64).reshape(-1, 3)
+    m = float(m)
+    return o[:, 0] / (m * (m - 1.0)) + o[:, 1] / (m * (m - 1.0)) - 2.0 * o[:, 2] / (m * m)
+
+
+def kid_sums(fa: torch.Tensor, fb: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+    """The (subsets, 3) fp64 device tensor dcv_eval_kid_sums writes for a contiguous (subsets, 2, m) int32 device table: per subset the sums of
+    k(x, y) = (x.y / D + 1)^3 over i != j of the a rows, of the b rows, and over all (i, j) across.  Two launches, no host read.  The table's entries are the
+    caller's to keep inside [0, na) x [0, nb) (kernel_distance checks an injected one; a row named outside counts as NaN, nothing is read for it)."""
+    na, D, sa = _rows(fa, None, "kernel distance: features a")
+    nb, _, sb = _rows(fb, D, "kernel distance: features b")
+    if not isinstance(table, torch.Tensor) or not table.is_cuda or table.dtype != torch.int32 or table.dim() != 3 or table.shape[1] != 2 or not table.is_contiguous() \
+            or not 1 <= table.shape[0] <= MAX_SUBSETS or not 2 <= table.shape[2] <= MAX_SUBSET_SIZE:
+        got = f"{table.dtype}{tuple(table.shape)} on {table.device}" if isinstance(table, torch.Tensor) else type(table).__name__
+        raise NativeError(f"kernel distance: expected a contiguous (subsets <= {MAX_SUBSETS}, 2, 2 <= m <= {MAX_SUBSET_SIZE}) int32 device table, got {got}")
+    subsets, m = int(table.shape[0]), int(table.shape[2])
+    need = int(lib().dcv_eval_kid_workspace_bytes(subsets, m))
+    ws = N.scratch.get("eval_kid", need, fa.device)
+    out = torch.empty((subsets, 3), dtype=torch.float64, device=fa.device)
+    _call("dcv_eval_kid_sums", 2, ptr(fa), sa, na, ptr(fb), sb, nb, D, ptr(table), subsets, m, ptr(ws), ws.numel(), ptr(out), stream_ptr())
+    return out
+
+
+def kid_draw(na: int, nb: int, subsets: int, m: int, seed: int, device) -> torch.Tensor:
+    """The (subsets, 2, m) int32 device table of draw_host: one launch."""
+    table = torch.empty((int(subsets), 2, int(m)), dtype=torch.int32, device=device)
+    _call("dcv_eval_kid_draw", 1, ptr(table), int(subsets), int(m), int(na), int(nb), int(seed) & _M64, stream_ptr())
+    return table
+
+
+def kernel_distance(fa: torch.Tensor, fb: torch.Tensor, num_subsets: int = 100, subset_size: int = 1000, seed: int = 0,
+                    table: Optional[torch.Tensor] = None) -> Tuple[float, float]:
+    """(mean, std) over the subsets of MMD^2 between the rows of ``fa`` (na, D) and ``fb`` (nb, D), fp32 device tensors, with the kernel (x.y / D + 1)^3 and
+    m = min(subset_size, na, nb) rows of each per subset.  The defaults are those of Karras et al. 2020 (100 subsets of 1000); std is the population standard
+    deviation of the per-subset estimates.  ``table``: an explicit (subsets, 2, m) int32 device table instead of the draw (read back and checked here)."""
+    na, D, _ = _rows(fa, None, "kernel distance: features a")
+    nb, _, _ = _rows(fb, D, "kernel distance: features b")
+    if table is None:
+        m = min(int(subset_size), na, nb)
+        if not 1 <= int(num_subsets) <= MAX_SUBSETS or not 2 <= m <= MAX_SUBSET_SIZE:
+            raise NativeError(f"kernel distance: 1 <= num_subsets <= {MAX_SUBSETS} and 2 <= min(subset_size, na, nb) <= {MAX_SUBSET_SIZE}; got {num_subsets} subsets, "
+                              f"subset_size {subset_size}, na {na}, nb {nb}")
+        table = kid_draw(na, nb, int(num_subsets), m, seed, fa.device)
+    else:
+        if not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or table.dim() != 3 or table.shape[1] != 2:
+            raise NativeError("kernel distance: the table must be a (subsets, 2, m) int32 device tensor")
+        rows = table.cpu().numpy()
+        if rows.size and (rows.min() < 0 or rows[:, 0].max() >= na or rows[:, 1].max() >= nb):
+            raise ValueError(f"kernel distance: the table names rows outside [0, {na}) x [0, {nb})")
+    out = kid_sums(fa, fb, table)
+    mmd2 = mmd2_from_sums(out.cpu().numpy(), int(table.shape[2]))
+    return float(mmd2.mean()), float(mmd2.std())
+
+
+# --------------------------------------------------------------------------- #
+# generator -> extractor -> statistics
+# --------------------------------------------------------------------------- #
+class Evaluator:
+    """``Evaluator(extractor, metrics=("is", "fid", "kid"), max_features=50000)``: the replacement of ``Trainer.evaluate`` (trainer.py:171-224).
+
+    ``extractor(xc)`` takes a (B, 3, T, H, W) fp32 device clip in [-1, 1] and returns ``(features (B, D), logits (B, K) or None)`` on the device — the caller's
+    network (the reference's is a Kinetics ResNeXt-101).  ``observe_real(xc)`` feeds real batches (a ``clipstore.ClipSampler``'s ``batch["color"]`` for instance);
+    the real statistics are computed once, ``real.save(path)`` keeps them and ``real_moments=FeatureMoments.load(path)`` brings them back (enough for "fid"; "kid"
+    needs real features).  ``evaluate(ggen, cgen, num_samples, batchsize)`` samples as ``sampling.generate_samples`` does and returns Python floats.
+
+    Features for the kernel distance go to device buffers of at most ``max_features`` rows per side, allocated once (on the first batch, when D is known) and
+    filled by the library's strided copy; rows past the buffer still enter the moments."""
+
+    def __init__(self, extractor: Callable, metrics: Sequence[str] = METRICS, max_features: int = 50000, kid_subsets: int = 100, kid_subset_size: int = 1000,
+                 seed: int = 0, real_moments: Optional[FeatureMoments] = None):
+        metrics = tuple(metrics)
+        unknown = [m for m in metrics if m not in METRICS]
+        if unknown or not metrics:
+            raise ValueError(f"Evaluator: metrics are chosen from {METRICS}, got {metrics}")
+        if not callable(extractor):
+            raise TypeError("Evaluator: the extractor must be callable")
+        if int(max_features) < 2:
+            raise ValueError(f"Evaluator: max_features >= 2, got {max_features}")
+        self.extractor, self.metrics, self.max_features = extractor, metrics, int(max_features)
+        self.kid_subsets, self.kid_subset_size, self.seed = int(kid_subsets), int(kid_subset_size), int(seed)
+        self.real: Optional[FeatureMoments] = real_moments
+        self.real_feats: Optional[torch.Tensor] = None      # (max_features, D) fp32, the first n_real_feats rows filled
+        self.n_real_feats = 0
+        self.fake: Optional[FeatureMoments] = None           # of the last evaluate()
+        self.inception: Optional[InceptionStats] = None
+        self.fake_feats: Optional[torch.Tensor] = None
+        self.n_fake_feats = 0
+        self.ggen = self.cgen = None      # the generators evaluate() samples when it is given none (trainer.build_evaluator binds them)
+
+    @staticmethod
+    def _clip(xc, what: str):
+        if not isinstance(xc, torch.Tensor):
+            raise NativeError(f"{what}: expected a tensor, got {type(xc).__name__}")
+        N._require(xc, what)
+        if xc.dim() != 5:
+            raise NativeError(f"{what}: expected a (B, C, T, H, W) clip, got {tuple(xc.shape)}")
+
+    def _extract(self, xc, what: str):
+        out = self.extractor(xc)
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise NativeError(f"{what}: the extractor must return (features, logits or None)")
+        feats, logits = out
+        _rows(feats, None, f"{what}: features")
+        if feats.shape[0] != xc.shape[0]:
+            raise NativeError(f"{what}: {xc.shape[0]} clips in, {feats.shape[0]} feature rows out")
+        if logits is not None:
+            _rows(logits, None, f"{what}: logits")
+            if logits.shape[0] != xc.shape[0]:
+                raise NativeError(f"{what}: {xc.shape[0]} clips in, {logits.shape[0]} logit rows out")
+        return feats, logits
+
+    def _store(self, buf: Optional[torch.Tensor], filled: int, feats: torch.Tensor):
+        """Append feats' rows to the side's buffer with dcv_axpby (one launch), as far as it has room."""
+        from . import ops
+        if buf is None:
+            buf = torch.empty((self.max_features, feats.shape[1]), dtype=torch.float32, device=feats.device)
+        if buf.shape[1] != feats.shape[1]:
+            raise NativeError(f"Evaluator: the extractor's features have {feats.shape[1]} values, the stored ones {buf.shape[1]}")
+        k = min(int(feats.shape[0]), self.max_features - filled)
+        if k > 0:
+            ops._axpby(feats[:k], 1.0, None, 0.0, buf[filled:filled + k])
+            _STATS["launches"] += 1
+        return buf, filled + max(k, 0)
+
+    def observe_real(self, xc: torch.Tensor) -> None:
+        """One real batch: its features enter the real moments and, for the kernel distance, the real feature buffer.  The logits are not used."""
+        self._clip(xc, "Evaluator.observe_real")
+        with torch.no_grad():
+            feats, _ = self._extract(xc, "Evaluator.observe_real")
+            if "fid" in self.metrics:      # the Gram is accumulated only where the Fréchet distance is asked for
+                if self.real is None:
+                    self.real = FeatureMoments(feats.shape[1], feats.device)
+                self.real.update(feats)
+            if "kid" in self.metrics:
+                self.real_feats, self.n_real_feats = self._store(self.real_feats, self.n_real_feats, feats)
+
+    def _refuse_missing(self):
+        if "fid" in self.metrics and (self.real is None or self.real.n < 2):
+            raise NativeError('Evaluator: "fid" needs the real statistics (observe_real() on at least two clips, or real_moments=FeatureMoments.load(...))')
+        if "kid" in self.metrics and self.n_real_feats < 2:
+            raise NativeError('Evaluator: "kid" needs real features (observe_real() on at least two clips)')
+
+    def evaluate(self, ggen=None, cgen=None, num_samples: int = 0, batchsize: int = 20) -> dict:
+        """Generate ``num_samples`` clips in batches of ``batchsize`` (eval mode, no_grad, the last batch truncated), run the extractor on each batch and accumulate;
+        then finalise.  -> ``{"is": .., "fid": .., "kid": .., "kid_std": ..}`` (the requested ones) as Python floats.  A metric whose inputs are missing is refused
+        by name before this module launches anything.  ``ggen`` / ``cgen`` default to the generators trainer.build_evaluator bound."""
+        ggen, cgen = ggen if ggen is not None else self.ggen, cgen if cgen is not None else self.cgen
+        if ggen is None or cgen is None:
+            raise ValueError("Evaluator.evaluate: no generators (pass ggen and cgen, or build the evaluator with trainer.build_evaluator)")
+        num_samples, batchsize = int(num_samples), int(batchsize)
+        if num_samples < 2 or batchsize < 1:
+            raise ValueError(f"Evaluator.evaluate: num_samples >= 2 and batchsize >= 1, got {num_samples}, {batchsize}")
+        self._refuse_missing()
+        ggen.eval()
+        cgen.eval()
+        self.n_fake_feats = 0
+        first = True
+        for start in range(0, num_samples, batchsize):
+            k = min(batchsize, num_samples - start)
+            with torch.no_grad():
+                xg = ggen.sample_videos(batchsize)
+                xc = cgen.forward_videos(xg)
+                self._clip(xc, "Evaluator.evaluate: the colour generator's output")
+                feats, logits = self._extract(xc, "Evaluator.evaluate")
+                if "is" in self.metrics and logits is None:
+                    raise NativeError('Evaluator: "is" needs logits, and the extractor returned None for them')
+                if first:      # the states of the last evaluate() are cleared in place and used again; one is made only for a metric that was asked for
+                    first = False
+                    if "fid" in self.metrics:
+                        if self.real.dim != feats.shape[1]:
+                            raise NativeError(f"Evaluator: the real statistics have {self.real.dim} features, the extractor returns {feats.shape[1]}")
+                        if self.fake is not None and self.fake.dim == feats.shape[1] and self.fake.device == feats.device:
+                            self.fake.reset()
+                        else:
+                            self.fake = FeatureMoments(feats.shape[1], feats.device)
+                    if "is" in self.metrics:
+                        if self.inception is not None and self.inception.num_classes == logits.shape[1] and self.inception.device == logits.device:
+                            self.inception.reset()
+                        else:
+                            self.inception = InceptionStats(logits.shape[1], logits.device)
+                feats = feats[:k]
+                if "fid" in self.metrics:
+                    self.fake.update(feats)
+                if "is" in self.metrics:
+                    self.inception.update(logits[:k])
+                if "kid" in self.metrics:
+                    self.fake_feats, self.n_fake_feats = self._store(self.fake_feats, self.n_fake_feats, feats)
+        out = {}
+        if "is" in self.metrics:
+            out["is"] = self.inception.score()
+        if "fid" in self.metrics:
+            out["fid"] = frechet_distance(self.real, self.fake)
+        if "kid" in self.metrics:
+            out["kid"], out["kid_std"] = kernel_distance(self.real_feats[:self.n_real_feats], self.fake_feats[:self.n_fake_feats], self.kid_subsets,
+                                                         self.kid_subset_size, self.seed)
+        return out

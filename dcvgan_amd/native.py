@@ -150,6 +150,13 @@ _SIGS = {
     "dcv_clipstore_draw": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_uint64, C.c_uint64, C.c_int64, _P]),
     "dcv_clipstore_gather": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P]),
     "dcv_clipstore_surreal": (C.c_int, [_P, C.c_int, C.c_int64, _P]),
+    # on-device evaluation statistics: Inception score, Fréchet and kernel distance (added symbols only: the ABI version stays 4)
+    "dcv_eval_moments_update": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int64, _P, _P, _P]),
+    "dcv_eval_inception_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "dcv_eval_inception_update": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int64, _P, _P, C.c_size_t, _P]),
+    "dcv_eval_kid_draw": (C.c_int, [_P, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_uint64, _P]),
+    "dcv_eval_kid_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "dcv_eval_kid_sums": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int, _P, C.c_int, C.c_int, _P, C.c_size_t, _P, _P]),
     # synchronised BatchNorm for data parallel, fp32 path (added symbols only: the ABI version stays 4)
     "dcv_bn_sync_row_doubles": (C.c_size_t, [C.c_int]),
     "dcv_bn_sync_sums": (C.c_int, [_P, _D, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),

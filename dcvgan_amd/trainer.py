@@ -117,6 +117,17 @@ def build_clip_sampler(cfg: StepConfig, store, **kw) -> "clipstore.ClipSampler":
     return clipstore.ClipSampler(store, kw.pop("batchsize", cfg.batchsize), **kw)
 
 
+def build_evaluator(cfg: StepConfig, models, extractor, ema=None, **kw) -> "evaluation.Evaluator":
+    """On-device evaluation in place of Trainer.evaluate (trainer.py:171-224): an evaluation.Evaluator bound to the two generators — with `ema`
+    (optim.ModelEma, build_ema) to their EMA twins, the weights a GAN is evaluated from — so that ``ev.evaluate(num_samples=..., batchsize=...)`` needs no models.
+    `extractor(xc) -> (features, logits or None)` is the caller's feature network; keyword arguments are the Evaluator's (metrics, max_features, kid_subsets,
+    kid_subset_size, seed, real_moments).  Feed the real statistics once with ``ev.observe_real(batch["color"])``."""
+    from . import evaluation
+    ev = evaluation.Evaluator(extractor, **kw)
+    ev.ggen, ev.cgen = (ema.module("ggen"), ema.module("cgen")) if ema is not None else (models["ggen"], models["cgen"])
+    return ev
+
+
 class StepRunner:
     """`elide_dead_backward=True` builds the D-phase fakes without a tape (they are detached): the
     reference backpropagates `loss_dis` through cgen/ggen too (trainer.py:304-319, fakes not detached)

@@ -507,6 +507,47 @@ int dcv_clipstore_gather(const void* frames, int mode, const int32_t* table, con
  * (< 1e10) min-max of the WINDOW goes to [-1, 0.8], background 1.0 — dcv_surreal_depth's arithmetic.  One launch, one workgroup per clip. */
 int dcv_clipstore_surreal(float* clips, int B, int64_t per_clip, void* stream);
 
+/* ---- on-device evaluation statistics: Inception score, Frechet and kernel distance (added symbols only: the ABI version stays 4) ------ *
+ * The reference's Trainer.evaluate (trainer.py:171-224) moves the generators to the CPU, writes every generated clip as an mp4 and lets an external package read
+ * them back for IS / FID / PRD.  These entries are the dense arithmetic AFTER the feature network (which stays the caller's): they accumulate, in fp64 and in device
+ * memory, what the three metrics are finalised from.  No floating-point atomic: every output element has one owning workgroup and every sum one order, so the same
+ * sequence of calls gives the same bits.  Every refusal (DCV_EINVAL, DCV_EWORKSPACE) is returned before the first launch.
+ *
+ * Feature moments, the statistics of the Frechet distance (Heusel et al. 2017: mu = sum / n, Sigma = (gram - sum sum^T / n) / (n - 1)):
+ *   sum[c] += sum_i x[i][c];   gram[c][d] += sum_i x[i][c] * x[i][d]        x: n rows of D fp32 values, row_stride >= D elements apart
+ * Operands are converted to fp64 on load (a product of two fp32 values is exact in fp64) and go through v_mfma_f64_16x16x4_f64 with the stored values of the gram
+ * tile as the accumulator input, rows in ascending order, four per instruction: the only rounding is the fp64 accumulation.  A 64 x 64 tile of gram has one owning
+ * workgroup (the upper tiles are computed, the lower ones stored as their mirror image; inside a diagonal tile both halves are computed from the same products in
+ * the same order): after every call gram is the full matrix, symmetric bit for bit.  sum: one lane per column, rows ascending.  A non-finite feature propagates.
+ * The caller zeroes sum (D doubles) and gram (D x D doubles) once and keeps the row count.  One launch.  1 <= D <= 4096, 1 <= n < 2^31. */
+int dcv_eval_moments_update(const float* x, int64_t n, int D, int64_t row_stride, double* sum, double* gram, void* stream);
+/* The Inception score's sums (Salimans et al. 2016: IS = exp(E_x KL(p(y|x) || p(y))) = exp(sum_i sum_k p_ik log p_ik / n - sum_k pbar_k log pbar_k), pbar = sum_i p_i / n):
+ *   state[k] += sum_i p_ik (k < K);   state[K] += sum_i sum_k p_ik log p_ik        logits: n rows of K fp32 values, row_stride >= K elements apart
+ * Per row, in fp64, every operation rounded on its own: m = max_k z_k; e_k = exp(z_k - m); S = sum_k e_k; p_k = e_k / S; log p_k = (z_k - m) - log S; a class with
+ * p_k == 0 adds nothing to the last sum.  Workgroup g of G = min(n, 256) takes rows g, g + G, ...; its 256 lanes hold classes l, l + 256, ... (S: lane order, then the
+ * tree of dcv_lecam_sums) and leave K + 1 partial sums in row g of the workspace; a second launch adds the G rows in ascending g and then the state.  Two launches.
+ * state: K + 1 doubles, zeroed once by the caller.  1 <= K <= 4096, 1 <= n < 2^31; workspace of at least dcv_eval_inception_workspace_bytes(n, K) (0: out of range). */
+size_t dcv_eval_inception_workspace_bytes(int64_t n, int K);
+int dcv_eval_inception_update(const float* logits, int64_t n, int K, int64_t row_stride, double* state, void* workspace, size_t workspace_bytes, void* stream);
+/* The kernel distance (Binkowski et al. 2018; the subset protocol and the defaults of Karras et al. 2020, "Training generative adversarial networks with limited
+ * data": 100 subsets of 1000, k(x, y) = (x.y / D + 1)^3).
+ * dcv_eval_kid_draw writes the int32 table (subsets, 2, m): row (s, 0) = the first m images of a keyed permutation of [0, na), row (s, 1) of [0, nb):
+ *   table[s][side][i] = perm(i), the bijection of dcv_clipstore_draw on [0, na or nb) with key {lo, hi} of seed + DCV_EVAL_KID_SALT and the Philox counter
+ *   {R, r, s, side} in round r.  One launch, no state.  m <= na, nb < 2^31. */
+#define DCV_EVAL_KID_SALT 0x9FB21C651E98DF25ull
+int dcv_eval_kid_draw(int32_t* table, int subsets, int m, int64_t na, int64_t nb, uint64_t seed, void* stream);
+/* For subset s, with a_i = fa[table[s][0][i]] and b_j = fb[table[s][1][j]] (rows of D fp32 values, stride_a / stride_b >= D elements apart):
+ *   out[3 s + 0] = sum_{i != j} k(a_i, a_j);   out[3 s + 1] = sum_{i != j} k(b_i, b_j);   out[3 s + 2] = sum_{i, j} k(a_i, b_j)        in fp64
+ * MMD^2_s = out0 / (m (m - 1)) + out1 / (m (m - 1)) - 2 out2 / m^2 is the host's.  The dot products run through v_mfma_f64_16x16x4_f64 with the contraction over D
+ * (operands converted on load: exact products); the m x m kernel matrix is never written: per 64 x 64 tile the epilogue forms t = dot / D + 1, (t * t) * t — each
+ * operation rounded on its own —, leaves out the diagonal of the two symmetric blocks, and reduces the tile to one partial in the workspace (only the upper tiles of
+ * a symmetric block are computed; an off-diagonal one counts twice, exactly); a second launch sums a subset's partials in a fixed order.  Two launches.
+ * A table entry outside [0, na) / [0, nb) is not followed: its row counts as NaN.  2 <= m <= 65536, 1 <= subsets <= 4096, 1 <= D <= 4096; workspace of at least
+ * dcv_eval_kid_workspace_bytes(subsets, m) (0: out of range). */
+size_t dcv_eval_kid_workspace_bytes(int subsets, int m);
+int dcv_eval_kid_sums(const float* fa, int64_t stride_a, int64_t na, const float* fb, int64_t stride_b, int64_t nb, int D, const int32_t* table, int subsets, int m,
+                      void* workspace, size_t workspace_bytes, double* out, void* stream);
+
 /* ---- bf16 channels-last ("CL16") data path -------------------------------------------------- *
  * BASELINE.json configs[2] ("surreal-depth1, bf16 MFMA") and configs[4] ("fp16 MFMA") name 16-bit variants of the same step
  * (config/surreal-depth1.yml:5,47-76, config/isogd-flow.yml; the reference itself is fp32-only).  This is that path as a DATA path:

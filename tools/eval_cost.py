@@ -1,0 +1,118 @@
+"""What on-device evaluation costs, on one MI355X, with the protocol of tools/layer_table.py: HIP events around REPS timed calls after WARM untimed ones.
+(a) dcv_eval_moments_update at (n, D) = (100, 2048) — one batch of an evaluation — and at (10000, 2048), where the fp64 matrix pipe's rate shows.
+(b) dcv_eval_kid_sums at the defaults: 100 subsets of 1000, D = 2048 (and the draw alone).
+(c) dcv_eval_inception_update at (100, 400).
+(d) One Evaluator.evaluate of 1000 samples of isogd-depth in batches of 50 with all three metrics, against the same sampling loop alone; the extractor is a stand-in
+    that returns free views of the clip (2048 features, 400 logits), so the difference is this module's launches and its host finalisation.
+FLOP counts are the nominal ones of the full matrices (2 n D^2 for the Gram, 3 * subsets * 2 m^2 D for the kernel distance); the kernels execute the upper tiles of
+the symmetric blocks only.  The measuring leg is a fresh child process under its own time limit; a failure ends the script there.
+Usage: python tools/eval_cost.py [out.txt]      (default out: profiles/eval_cost.txt; the record also goes to stdout)"""
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WARM, REPS = 10, 20
+LIMIT_S = 540
+
+
+def measure(out):
+    import datetime
+    import time
+    import torch
+    from dcvgan_amd import evaluation as E, native, trainer
+    from dcvgan_amd.configs import CONFIGS
+    native.lib()
+    dev = torch.device("cuda:0")
+    lines = ["evaluation cost: one MI355X (%s), %s; HIP events, %d timed calls after %d untimed; library %s" %
+             (torch.cuda.get_device_name(0), datetime.date.today().isoformat(), REPS, WARM, native.csrc_digest()[:12])]
+
+    def timed(fn, reps=REPS, warm=WARM):
+        for _ in range(warm):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps      # ms per call
+
+    g = torch.Generator().manual_seed(1)
+    D = 2048
+    # ---- (a) the moments ----
+    for n, reps, warm in ((100, REPS, WARM), (10000, 5, 2)):
+        x = torch.randn(n, D, generator=g).to(dev)
+        fm = E.FeatureMoments(D, dev)
+        ms = timed(lambda: fm.update(x), reps, warm)
+        gflop = 2.0 * n * D * D / 1e9
+        lines.append("(a) dcv_eval_moments_update (%d, %d): %.3f ms per call, %.2f GFLOP nominal -> %.2f TFLOP/s fp64 (%d timed after %d)" %
+                     (n, D, ms, gflop, gflop / ms, reps, warm))
+    # ---- (b) the kernel distance ----
+    fa, fb = torch.randn(10000, D, generator=g).to(dev), (torch.randn(10000, D, generator=g) + 0.1).to(dev)
+    table = E.kid_draw(10000, 10000, 100, 1000, 0, dev)
+    ms = timed(lambda: E.kid_sums(fa, fb, table), 5, 2)
+    tflop = 3 * 100 * 2.0 * 1000 * 1000 * D / 1e12
+    lines.append("(b) dcv_eval_kid_sums, 100 subsets of 1000, D = %d, rows gathered from 2 x 10000: %.2f ms per call, %.2f TFLOP nominal -> %.2f TFLOP/s fp64 "
+                 "(5 timed after 2)" % (D, ms, tflop, tflop / ms * 1e3))
+    lines.append("    dcv_eval_kid_draw alone (100 x 2 x 1000 rows): %.1f us" % (timed(lambda: E.kid_draw(10000, 10000, 100, 1000, 0, dev)) * 1e3))
+    h0 = time.perf_counter()
+    kid = E.kernel_distance(fa, fb)
+    lines.append("    kernel_distance end to end (draw, sums, host read): %.1f ms; KID %.3e +- %.1e" % ((time.perf_counter() - h0) * 1e3, kid[0], kid[1]))
+    # ---- (c) the Inception sums ----
+    z = (torch.randn(100, 400, generator=g) * 3).to(dev)
+    st = E.InceptionStats(400, dev)
+    lines.append("(c) dcv_eval_inception_update (100, 400), 2 launches: %.1f us per call" % (timed(lambda: st.update(z)) * 1e3))
+    # ---- (d) one evaluation ----
+    cfg = CONFIGS["isogd-depth"]
+    torch.manual_seed(1)
+    models = trainer.build_models(cfg, dev)
+
+    def extractor(xc):
+        flat = xc.permute(0, 2, 1, 3, 4).reshape(xc.shape[0], -1)
+        return flat[:, :D], flat[:, D:D + 400]
+
+    ev = trainer.build_evaluator(cfg, models, extractor)
+    T, S = cfg.video_length, cfg.image_size
+    for _ in range(20):
+        ev.observe_real((torch.rand(50, 3, T, S, S, generator=g) * 2 - 1).to(dev))
+
+    def sample_only():
+        with torch.no_grad():
+            for _ in range(20):
+                extractor(models["cgen"].forward_videos(models["ggen"].sample_videos(50)))
+        torch.cuda.synchronize()
+
+    ev.evaluate(num_samples=100, batchsize=50)      # warm-up
+    sample_only()
+    rows = []
+    for _ in range(2):
+        h0 = time.perf_counter(); l0 = E.launches()
+        res = ev.evaluate(num_samples=1000, batchsize=50)
+        t_eval = time.perf_counter() - h0
+        n_launch = E.launches() - l0
+        h0 = time.perf_counter()
+        sample_only()
+        rows.append((t_eval, time.perf_counter() - h0))
+    h0 = time.perf_counter()
+    E.frechet_distance(ev.real, ev.fake)
+    t_fid = time.perf_counter() - h0
+    lines.append("(d) Evaluator.evaluate, 1000 samples of isogd-depth in batches of 50, is + fid + kid (D = %d, K = 400, 1000 real clips observed before): "
+                 "%.2f s / %.2f s wall clock in two runs, the same sampling loop alone %.2f s / %.2f s; %d launches of this module; of the rest the host's "
+                 "frechet_distance (two symmetric eigenproblems of %d x %d) takes %.2f s" % (D, rows[0][0], rows[1][0], rows[0][1], rows[1][1], n_launch, D, D, t_fid))
+    lines.append("    result: " + ", ".join("%s %.6g" % kv for kv in sorted(res.items())))
+    print("\n".join(lines))
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    open(out, "w").write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--leg":
+        sys.path.insert(0, ROOT)
+        measure(sys.argv[2])
+    else:
+        out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "eval_cost.txt")
+        rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", out], cwd=ROOT, timeout=LIMIT_S).returncode      # a fresh child under its own time limit
+        if rc != 0:
+            sys.exit("eval_cost: the measuring leg ended with status %d; nothing else is started" % rc)
