@@ -159,6 +159,29 @@ __device__ __forceinline__ float surreal_value(float v, float mi, float ma) {
 }
 }  // namespace dcv
 namespace dcv {
+// The fp64 matrix pipe and the 256-lane tree of the evaluation kernels (evalstats.hip: moments and kernel distance; evalknn.hip: the k-nearest-neighbour metrics).
+typedef double ev_d4 __attribute__((ext_vector_type(4)));
+typedef float ev_f4 __attribute__((ext_vector_type(4)));
+
+// v_mfma_f64_16x16x4_f64: D = A (16 x 4) * B (4 x 16) + C.  Lane l holds A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15], one double each, and
+// C/D[row (l >> 4) + 4 r][col l & 15] in element r of its four: NOT the row map of the other MFMA forms (4 (l >> 4) + r).
+__device__ __forceinline__ ev_d4 ev_mfma(double a, double b, ev_d4 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+
+// The order above the lanes, as lecam.hip has it: p[l] += p[l + s] for s = 128 .. 1; every lane returns p[0].
+__device__ __forceinline__ double ev_tree_sum(double v, double* p) {
+    const int l = threadIdx.x;
+    __syncthreads();      // the previous tree's p[0] has been read by every lane
+    p[l] = v;
+    __syncthreads();
+#pragma unroll
+    for (int s = 128; s >= 1; s >>= 1) {
+        if (l < s) p[l] += p[l + s];
+        __syncthreads();
+    }
+    return p[0];
+}
+}  // namespace dcv
+namespace dcv {
 // n / d for the FastDiv above (d == 1 handled by mul == 0 convention)
 __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv f) {
     if (f.div == 1) return n;

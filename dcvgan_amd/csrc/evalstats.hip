@@ -9,32 +9,13 @@
 
 namespace dcv {
 
-typedef double ev_d4 __attribute__((ext_vector_type(4)));
-typedef float ev_f4 __attribute__((ext_vector_type(4)));
-
 static const int EV_MAX_D = 4096;            // features per row, classes per row
 static const int EV_TILE = 64;               // a workgroup's output tile: 4 waves x (2 x 2) MFMA tiles of 16 x 16
 static const int EV_INCEPTION_GROUPS = 256;  // workgroups (= partial rows in the workspace) of the Inception sums at most
 static const int EV_MAX_SUBSETS = 4096;
 static const int EV_MAX_SUBSET_SIZE = 65536;
 
-// v_mfma_f64_16x16x4_f64: D = A (16 x 4) * B (4 x 16) + C.  Lane l holds A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15], one double each, and
-// C/D[row (l >> 4) + 4 r][col l & 15] in element r of its four: NOT the row map of the other MFMA forms (4 (l >> 4) + r).
-__device__ __forceinline__ ev_d4 ev_mfma(double a, double b, ev_d4 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-
-// The order above the lanes, as lecam.hip has it: p[l] += p[l + s] for s = 128 .. 1; every lane returns p[0].
-__device__ __forceinline__ double ev_tree_sum(double v, double* p) {
-    const int l = threadIdx.x;
-    __syncthreads();      // the previous tree's p[0] has been read by every lane
-    p[l] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = 128; s >= 1; s >>= 1) {
-        if (l < s) p[l] += p[l + s];
-        __syncthreads();
-    }
-    return p[0];
-}
+// ev_d4, ev_f4, ev_mfma (v_mfma_f64_16x16x4_f64 and its lane maps) and ev_tree_sum (the order above the lanes) live in dcv_common.h: evalknn.hip shares them.
 __device__ __forceinline__ float ev_tree_max(float v, float* p) {      // fmaxf drops a NaN; the NaN itself reaches the sums through exp()
     const int l = threadIdx.x;
     __syncthreads();

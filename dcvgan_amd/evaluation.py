@@ -8,6 +8,8 @@ caller's, handed over as a callable; everything after it is this module's:
 * ``InceptionStats``: the sums the Inception score is finalised from (``dcv_eval_inception_update``: an fp64 softmax per row),
 * ``kernel_distance``: KID with the cubic polynomial kernel over drawn subsets (``dcv_eval_kid_draw`` + ``dcv_eval_kid_sums``; the m x m kernel matrices are never
   written),
+* ``manifold_metrics``: improved precision / recall and density / coverage (``dcv_eval_row_norms``, ``dcv_eval_knn_radii``, ``dcv_eval_manifold_counts``,
+  ``dcv_eval_manifold_reduce``; the n x n distance matrices are never written), with ``manifold_host`` as its numpy mirror,
 * ``frechet_distance``: the O(D^3) eigenvalue step on the host in numpy — it runs once per evaluation and produces a number for the host's logger anyway,
 * ``Evaluator``: generator -> extractor -> statistics without a clip or a feature crossing PCIe.
 
@@ -29,13 +31,16 @@ MAX_DIM = 4096                       # features per row (D) and classes per row 
 MAX_SUBSETS, MAX_SUBSET_SIZE = 4096, 65536
 KID_SALT = 0x9FB21C651E98DF25        # DCV_EVAL_KID_SALT: the draw's Philox key is the seed plus this constant
 _M64 = 0xFFFFFFFFFFFFFFFF
-METRICS = ("is", "fid", "kid")
+METRICS = ("is", "fid", "kid", "pr", "dc")
+DEFAULT_METRICS = ("is", "fid", "kid")
+MAX_K, MAX_COL_SPLITS = 16, 64        # neighbours and column shares of the k-nearest-neighbour metrics: the kernels' limits
 
 _STATS = {"launches": 0}
 
 
 def launches() -> int:
-    """Kernel launches this module has issued so far, in this process (dcv_eval_inception_update and dcv_eval_kid_sums are two each, every other entry one)."""
+    """Kernel launches this module has issued so far, in this process (dcv_eval_inception_update, dcv_eval_kid_sums, dcv_eval_knn_radii and
+    dcv_eval_manifold_counts are two each, every other entry one)."""
     return _STATS["launches"]
 
 
@@ -372,21 +377,214 @@ def kernel_distance(fa: torch.Tensor, fb: torch.Tensor, num_subsets: int = 100, 
 
 
 # --------------------------------------------------------------------------- #
+# precision / recall and density / coverage
+# --------------------------------------------------------------------------- #
+def _k(k, what: str) -> int:
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_K:
+        raise ValueError(f"{what}: 1 <= k <= {MAX_K}, got {k!r}")
+    return int(k)
+
+
+def _splits(col_splits, what: str) -> int:
+    if isinstance(col_splits, bool) or not isinstance(col_splits, (int, np.integer)) or not 0 <= int(col_splits) <= MAX_COL_SPLITS:
+        raise ValueError(f"{what}: 0 <= col_splits <= {MAX_COL_SPLITS} (0: the library chooses), got {col_splits!r}")
+    return int(col_splits)
+
+
+def _vector(t, n: int, dtype, what: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or t.dim() != 1 or t.shape[0] != n or not t.is_contiguous():
+        got = f"{t.dtype}{tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise NativeError(f"{what}: expected a contiguous ({n},) {dtype} device tensor, got {got}")
+    return t
+
+
+def row_norms(feats: torch.Tensor) -> torch.Tensor:
+    """The (n,) fp64 device tensor of ``|x_i|^2 = sum_d x[i][d]^2`` (features ascending) for a (n, D) fp32 device tensor.  One launch."""
+    n, D, stride = _rows(feats, None, "row_norms")
+    out = torch.empty((n,), dtype=torch.float64, device=feats.device)
+    _call("dcv_eval_row_norms", 1, ptr(feats), n, D, stride, ptr(out), stream_ptr())
+    return out
+
+
+def knn_radii(feats: torch.Tensor, k: int, col_splits: int = 0, norms: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The (n,) fp64 device tensor ``rad2[i]`` = the k-th smallest ``d2(x_i, x_j)`` over ``j != i`` (self excluded by index, a NaN distance never selected; +inf where
+    fewer than k distances survive).  ``norms``: ``row_norms(feats)`` if the caller has them already.  Two launches (three without ``norms``), no host read; the result
+    is the same bits for every ``col_splits``."""
+    n, D, stride = _rows(feats, None, "knn_radii")
+    k, col_splits = _k(k, "knn_radii"), _splits(col_splits, "knn_radii")
+    if n < k + 1:
+        raise NativeError(f"knn_radii: the {k}-th neighbour needs at least {k + 1} rows, got {n}")
+    norms = row_norms(feats) if norms is None else _vector(norms, n, torch.float64, "knn_radii: norms")
+    need = int(lib().dcv_eval_knn_workspace_bytes(n, k, col_splits))
+    ws = N.scratch.get("eval_knn", need, feats.device)
+    out = torch.empty((n,), dtype=torch.float64, device=feats.device)
+    _call("dcv_eval_knn_radii", 2, ptr(feats), n, D, stride, ptr(norms), k, col_splits, ptr(ws), ws.numel(), ptr(out), stream_ptr())
+    return out
+
+
+def manifold_counts(queries: torch.Tensor, support: torch.Tensor, rad2: Optional[torch.Tensor], col_splits: int = 0, norms_q: Optional[torch.Tensor] = None,
+                    norms_s: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(count, dmin2)`` per query row: ``count[q] = #{i : d2(q, s_i) <= rad2[i]}`` (int32) and ``dmin2[q] = min_i d2(q, s_i)`` (fp64, +inf if every distance is
+    NaN), for (nq, D) and (ns, D) fp32 device tensors and the supports' (ns,) fp64 ``rad2`` (None: the counts are zero, only the minima are formed).  Two launches
+    (one more per side without its norms), no host read; the same bits for every ``col_splits``."""
+    nq, D, sq = _rows(queries, None, "manifold_counts: queries")
+    ns, _, ss = _rows(support, D, "manifold_counts: support")
+    col_splits = _splits(col_splits, "manifold_counts")
+    if nq * ns >= 2 ** 53:
+        raise NativeError(f"manifold_counts: nq * ns must stay below 2^53, got {nq} x {ns}")
+    if rad2 is not None:
+        _vector(rad2, ns, torch.float64, "manifold_counts: rad2")
+    norms_q = row_norms(queries) if norms_q is None else _vector(norms_q, nq, torch.float64, "manifold_counts: norms_q")
+    norms_s = row_norms(support) if norms_s is None else _vector(norms_s, ns, torch.float64, "manifold_counts: norms_s")
+    need = int(lib().dcv_eval_manifold_workspace_bytes(nq, ns, col_splits))
+    ws = N.scratch.get("eval_manifold", need, queries.device)
+    count = torch.empty((nq,), dtype=torch.int32, device=queries.device)
+    dmin2 = torch.empty((nq,), dtype=torch.float64, device=queries.device)
+    _call("dcv_eval_manifold_counts", 2, ptr(queries), sq, nq, ptr(norms_q), ptr(support), ss, ns, ptr(norms_s), ptr(rad2), D, col_splits, ptr(ws), ws.numel(),
+          ptr(count), ptr(dmin2), stream_ptr())
+    return count, dmin2
+
+
+def _metric_names(metrics, what: str) -> Tuple[str, ...]:
+    metrics = tuple(metrics)
+    if not metrics or any(m not in ("pr", "dc") for m in metrics):
+        raise ValueError(f'{what}: metrics are chosen from ("pr", "dc"), got {metrics}')
+    return metrics
+
+
+def manifold_launches(k_pr: int = 3, k_dc: int = 5, metrics: Sequence[str] = ("pr", "dc")) -> int:
+    """The launches of one ``manifold_metrics`` call: 2 for the norms, 2 per radius vector, 3 per counts call with its reduction — 17 at the defaults, 12 for "pr"
+    alone or for both pairs with one k, 10 for "dc" alone."""
+    pr, dc = "pr" in metrics, "dc" in metrics
+    radii = (2 if pr else 0) + (1 if dc and not (pr and k_pr == k_dc) else 0)            # rA and rB at k_pr; rA at k_dc unless it is the same vector
+    counts = 2 + (1 if pr and dc and k_pr != k_dc else 0)                                  # B against A, A against B; B against A again with the other radii
+    return 2 + 2 * radii + 3 * counts
+
+
+def manifold_metrics(real_feats: torch.Tensor, fake_feats: torch.Tensor, k_pr: int = 3, k_dc: int = 5, metrics: Sequence[str] = ("pr", "dc")) -> dict:
+    """Improved precision and recall (Kynkäänniemi et al. 2019; "pr", k = 3) and density and coverage (Naeem et al. 2020; "dc", k = 5) between the rows of
+    ``real_feats`` (na, D) and ``fake_feats`` (nb, D), fp32 device tensors -> ``{"precision", "recall", "density", "coverage"}`` (the requested pairs) as Python
+    floats.  With rA, rB the squared k-th-neighbour radii of each side::
+
+        precision = #{j : exists i, d2(b_j, a_i) <= rA[i]} / nb        recall   = #{i : exists j, d2(a_i, b_j) <= rB[j]} / na
+        density   = sum_j #{i : d2(b_j, a_i) <= rA[i]} / (k nb)        coverage = #{i : min_j d2(a_i, b_j) <= rA[i]} / na
+
+    Every comparison is ``<=`` (Kynkäänniemi's convention).  The ``prdc`` package uses ``<`` for density and coverage; the two differ on exact ties only.  If a row
+    norm of either side is not finite, all requested metrics are NaN.  The norms are computed once per side, each radius vector once per distinct k, and the reduced
+    integers come back in one small device-to-host read at the end (``manifold_launches`` launches)."""
+    metrics = _metric_names(metrics, "manifold_metrics")
+    na, D, _ = _rows(real_feats, None, "manifold_metrics: real features")
+    nb, _, _ = _rows(fake_feats, D, "manifold_metrics: fake features")
+    pr, dc = "pr" in metrics, "dc" in metrics
+    k_pr, k_dc = _k(k_pr, "manifold_metrics: k_pr"), _k(k_dc, "manifold_metrics: k_dc")
+    need = max(k_pr if pr else 0, k_dc if dc else 0) + 1
+    if na < need or (pr and nb < k_pr + 1):
+        raise NativeError(f"manifold_metrics: the k-th neighbour needs k + 1 rows (k_pr {k_pr}, k_dc {k_dc}), got {na} real and {nb} fake")
+    if na * nb >= 2 ** 53:
+        raise NativeError(f"manifold_metrics: na * nb must stay below 2^53, got {na} x {nb}")
+    norm_a, norm_b = row_norms(real_feats), row_norms(fake_feats)
+    out = torch.empty((3, 4), dtype=torch.float64, device=real_feats.device)      # one row per reduction
+
+    def reduce(row, count, dmin2, own_rad2, norms, n):
+        _call("dcv_eval_manifold_reduce", 1, ptr(count), ptr(dmin2), ptr(own_rad2), ptr(norms), n, ptr(out[row]), stream_ptr())
+
+    radii_a = {}
+    for k in ([k_pr] if pr else []) + ([k_dc] if dc else []):
+        if k not in radii_a:
+            radii_a[k] = knn_radii(real_feats, k, norms=norm_a)
+    k_first = k_pr if pr else k_dc
+    c, m = manifold_counts(fake_feats, real_feats, radii_a[k_first], norms_q=norm_b, norms_s=norm_a)      # precision, and density when it shares the radii
+    reduce(0, c, m, None, norm_b, nb)
+    rad_b = knn_radii(fake_feats, k_pr, norms=norm_b) if pr else None
+    c, m = manifold_counts(real_feats, fake_feats, rad_b, norms_q=norm_a, norms_s=norm_b)                  # recall, and coverage's minima
+    reduce(1, c, m, radii_a[k_dc] if dc else None, norm_a, na)
+    if pr and dc and k_dc != k_pr:
+        c, m = manifold_counts(fake_feats, real_feats, radii_a[k_dc], norms_q=norm_b, norms_s=norm_a)     # density
+        reduce(2, c, m, None, norm_b, nb)
+    o = out.cpu().numpy()
+    dens = o[2] if (pr and dc and k_dc != k_pr) else o[0]
+    bad = o[0, 3] + o[1, 3] > 0
+    res = {}
+    if pr:
+        res["precision"], res["recall"] = float(o[0, 0] / nb), float(o[1, 0] / na)
+    if dc:
+        res["density"], res["coverage"] = float(dens[1] / (float(k_dc) * nb)), float(o[1, 2] / na)
+    return {key: float("nan") for key in res} if bad else res
+
+
+def _norms_host(x: np.ndarray) -> np.ndarray:
+    s = np.zeros(x.shape[0], dtype=np.float64)
+    for d in range(x.shape[1]):      # features ascending, as dcv_eval_row_norms adds them
+        s = s + x[:, d] * x[:, d]
+    return s
+
+
+def d2_host(x, y) -> np.ndarray:
+    """``d2(x_i, y_j) = max(0, (|x_i|^2 + |y_j|^2) - 2 x_i.y_j)`` in numpy fp64 for fp32 rows (a NaN stays a NaN)."""
+    x, y = np.asarray(x, dtype=np.float32).astype(np.float64), np.asarray(y, dtype=np.float32).astype(np.float64)
+    with np.errstate(all="ignore"):
+        t = (_norms_host(x)[:, None] + _norms_host(y)[None, :]) - 2.0 * (x @ y.T)
+        return np.where(t < 0.0, 0.0, t)
+
+
+def knn_radii_host(x, k: int) -> np.ndarray:
+    """``rad2_k(X)``: per row the k-th smallest ``d2`` to the OTHER rows — self excluded by index, a NaN never selected, +inf where fewer than k survive."""
+    k = _k(k, "knn_radii_host")
+    d = d2_host(x, x)
+    if d.shape[0] < k + 1:
+        raise ValueError(f"knn_radii_host: the {k}-th neighbour needs at least {k + 1} rows, got {d.shape[0]}")
+    np.fill_diagonal(d, np.inf)
+    d[np.isnan(d)] = np.inf
+    return np.sort(d, axis=1)[:, k - 1]
+
+
+def counts_host(queries, support, rad2) -> Tuple[np.ndarray, np.ndarray]:
+    """``(count, dmin2)`` of dcv_eval_manifold_counts: a NaN distance is in no ball and is no minimum; ``rad2`` None: zero counts."""
+    d = d2_host(queries, support)
+    with np.errstate(invalid="ignore"):
+        count = np.zeros(d.shape[0], dtype=np.int32) if rad2 is None else (d <= np.asarray(rad2, dtype=np.float64)[None, :]).sum(axis=1).astype(np.int32)
+    return count, np.where(np.isnan(d), np.inf, d).min(axis=1)
+
+
+def manifold_host(a, b, k: int) -> dict:
+    """The numpy fp64 mirror of the four metrics with one k — the specification the kernels are tested against, as ``draw_host`` is for the KID draw.  ->
+    ``precision``, ``recall``, ``density``, ``coverage`` (floats; NaN, all four, if a row norm of either side is not finite) and what they are counted from:
+    ``rad2_a``, ``rad2_b``, ``count_ba`` / ``dmin2_ba`` (fakes against reals and rA), ``count_ab`` / ``dmin2_ab`` (reals against fakes and rB)."""
+    a, b = np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)
+    if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1] or not 1 <= a.shape[1] <= MAX_DIM:
+        raise ValueError(f"manifold_host: two (n, D) arrays with 1 <= D <= {MAX_DIM}, got {a.shape} and {b.shape}")
+    ra, rb = knn_radii_host(a, k), knn_radii_host(b, k)
+    c_ba, m_ba = counts_host(b, a, ra)
+    c_ab, m_ab = counts_host(a, b, rb)
+    na, nb = a.shape[0], b.shape[0]
+    res = dict(precision=float((c_ba > 0).sum() / nb), recall=float((c_ab > 0).sum() / na), density=float(c_ba.astype(np.int64).sum() / (float(k) * nb)),
+               coverage=float((m_ab <= ra).sum() / na))
+    with np.errstate(all="ignore"):
+        finite = np.isfinite(_norms_host(a.astype(np.float64))).all() and np.isfinite(_norms_host(b.astype(np.float64))).all()
+    if not finite:
+        res = {key: float("nan") for key in res}
+    res.update(rad2_a=ra, rad2_b=rb, count_ba=c_ba, dmin2_ba=m_ba, count_ab=c_ab, dmin2_ab=m_ab)
+    return res
+
+
+# --------------------------------------------------------------------------- #
 # generator -> extractor -> statistics
 # --------------------------------------------------------------------------- #
 class Evaluator:
-    """``Evaluator(extractor, metrics=("is", "fid", "kid"), max_features=50000)``: the replacement of ``Trainer.evaluate`` (trainer.py:171-224).
+    """``Evaluator(extractor, metrics=("is", "fid", "kid"), max_features=50000)``: the replacement of ``Trainer.evaluate`` (trainer.py:171-224).  ``metrics`` are chosen
+    from ``("is", "fid", "kid", "pr", "dc")``: "pr" adds improved precision and recall (``pr_k`` = 3 neighbours), "dc" density and coverage (``dc_k`` = 5), both
+    over the stored features of the two sides (``manifold_metrics``).
 
     ``extractor(xc)`` takes a (B, 3, T, H, W) fp32 device clip in [-1, 1] and returns ``(features (B, D), logits (B, K) or None)`` on the device — the caller's
     network (the reference's is a Kinetics ResNeXt-101).  ``observe_real(xc)`` feeds real batches (a ``clipstore.ClipSampler``'s ``batch["color"]`` for instance);
-    the real statistics are computed once, ``real.save(path)`` keeps them and ``real_moments=FeatureMoments.load(path)`` brings them back (enough for "fid"; "kid"
-    needs real features).  ``evaluate(ggen, cgen, num_samples, batchsize)`` samples as ``sampling.generate_samples`` does and returns Python floats.
+    the real statistics are computed once, ``real.save(path)`` keeps them and ``real_moments=FeatureMoments.load(path)`` brings them back (enough for "fid"; "kid",
+    "pr" and "dc" need real features).  ``evaluate(ggen, cgen, num_samples, batchsize)`` samples as ``sampling.generate_samples`` does and returns Python floats.
 
-    Features for the kernel distance go to device buffers of at most ``max_features`` rows per side, allocated once (on the first batch, when D is known) and
+    Features for the kernel distance and the manifold metrics go to device buffers of at most ``max_features`` rows per side, allocated once (on the first batch, when D is known) and
     filled by the library's strided copy; rows past the buffer still enter the moments."""
 
-    def __init__(self, extractor: Callable, metrics: Sequence[str] = METRICS, max_features: int = 50000, kid_subsets: int = 100, kid_subset_size: int = 1000,
-                 seed: int = 0, real_moments: Optional[FeatureMoments] = None):
+    def __init__(self, extractor: Callable, metrics: Sequence[str] = DEFAULT_METRICS, max_features: int = 50000, kid_subsets: int = 100, kid_subset_size: int = 1000,
+                 seed: int = 0, real_moments: Optional[FeatureMoments] = None, pr_k: int = 3, dc_k: int = 5):
         metrics = tuple(metrics)
         unknown = [m for m in metrics if m not in METRICS]
         if unknown or not metrics:
@@ -397,6 +595,8 @@ class Evaluator:
             raise ValueError(f"Evaluator: max_features >= 2, got {max_features}")
         self.extractor, self.metrics, self.max_features = extractor, metrics, int(max_features)
         self.kid_subsets, self.kid_subset_size, self.seed = int(kid_subsets), int(kid_subset_size), int(seed)
+        self.pr_k, self.dc_k = _k(pr_k, "Evaluator: pr_k"), _k(dc_k, "Evaluator: dc_k")
+        self._stores = any(m in metrics for m in ("kid", "pr", "dc"))      # the metrics computed from the stored features of both sides
         self.real: Optional[FeatureMoments] = real_moments
         self.real_feats: Optional[torch.Tensor] = None      # (max_features, D) fp32, the first n_real_feats rows filled
         self.n_real_feats = 0
@@ -442,7 +642,8 @@ class Evaluator:
         return buf, filled + max(k, 0)
 
     def observe_real(self, xc: torch.Tensor) -> None:
-        """One real batch: its features enter the real moments and, for the kernel distance, the real feature buffer.  The logits are not used."""
+        """One real batch: its features enter the real moments and, for the kernel distance and the manifold metrics, the real feature buffer.  The logits are not
+        used."""
         self._clip(xc, "Evaluator.observe_real")
         with torch.no_grad():
             feats, _ = self._extract(xc, "Evaluator.observe_real")
@@ -450,18 +651,25 @@ class Evaluator:
                 if self.real is None:
                     self.real = FeatureMoments(feats.shape[1], feats.device)
                 self.real.update(feats)
-            if "kid" in self.metrics:
+            if self._stores:
                 self.real_feats, self.n_real_feats = self._store(self.real_feats, self.n_real_feats, feats)
 
-    def _refuse_missing(self):
+    def _refuse_missing(self, num_samples: int):
         if "fid" in self.metrics and (self.real is None or self.real.n < 2):
             raise NativeError('Evaluator: "fid" needs the real statistics (observe_real() on at least two clips, or real_moments=FeatureMoments.load(...))')
         if "kid" in self.metrics and self.n_real_feats < 2:
             raise NativeError('Evaluator: "kid" needs real features (observe_real() on at least two clips)')
+        for name, k in (("pr", self.pr_k), ("dc", self.dc_k)):      # the k-th neighbour of a row is among the OTHER rows of its side
+            if name in self.metrics and self.n_real_feats < k + 1:
+                raise NativeError(f'Evaluator: "{name}" with k = {k} needs at least {k + 1} real features (observe_real() saw {self.n_real_feats})')
+            if name in self.metrics and min(num_samples, self.max_features) < k + 1:
+                raise NativeError(f'Evaluator: "{name}" with k = {k} needs at least {k + 1} generated samples within max_features, got num_samples {num_samples}, '
+                                  f'max_features {self.max_features}')
 
     def evaluate(self, ggen=None, cgen=None, num_samples: int = 0, batchsize: int = 20) -> dict:
         """Generate ``num_samples`` clips in batches of ``batchsize`` (eval mode, no_grad, the last batch truncated), run the extractor on each batch and accumulate;
-        then finalise.  -> ``{"is": .., "fid": .., "kid": .., "kid_std": ..}`` (the requested ones) as Python floats.  A metric whose inputs are missing is refused
+        then finalise.  -> ``{"is": .., "fid": .., "kid": .., "kid_std": .., "precision": .., "recall": .., "density": .., "coverage": ..}`` (the requested ones) as
+        Python floats.  A metric whose inputs are missing is refused
         by name before this module launches anything.  ``ggen`` / ``cgen`` default to the generators trainer.build_evaluator bound."""
         ggen, cgen = ggen if ggen is not None else self.ggen, cgen if cgen is not None else self.cgen
         if ggen is None or cgen is None:
@@ -469,7 +677,7 @@ class Evaluator:
         num_samples, batchsize = int(num_samples), int(batchsize)
         if num_samples < 2 or batchsize < 1:
             raise ValueError(f"Evaluator.evaluate: num_samples >= 2 and batchsize >= 1, got {num_samples}, {batchsize}")
-        self._refuse_missing()
+        self._refuse_missing(num_samples)
         ggen.eval()
         cgen.eval()
         self.n_fake_feats = 0
@@ -502,7 +710,7 @@ class Evaluator:
                     self.fake.update(feats)
                 if "is" in self.metrics:
                     self.inception.update(logits[:k])
-                if "kid" in self.metrics:
+                if self._stores:
                     self.fake_feats, self.n_fake_feats = self._store(self.fake_feats, self.n_fake_feats, feats)
         out = {}
         if "is" in self.metrics:
@@ -512,4 +720,7 @@ class Evaluator:
         if "kid" in self.metrics:
             out["kid"], out["kid_std"] = kernel_distance(self.real_feats[:self.n_real_feats], self.fake_feats[:self.n_fake_feats], self.kid_subsets,
                                                          self.kid_subset_size, self.seed)
+        wanted = tuple(m for m in ("pr", "dc") if m in self.metrics)
+        if wanted:
+            out.update(manifold_metrics(self.real_feats[:self.n_real_feats], self.fake_feats[:self.n_fake_feats], self.pr_k, self.dc_k, wanted))
         return out

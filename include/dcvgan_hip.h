@@ -548,6 +548,41 @@ size_t dcv_eval_kid_workspace_bytes(int subsets, int m);
 int dcv_eval_kid_sums(const float* fa, int64_t stride_a, int64_t na, const float* fb, int64_t stride_b, int64_t nb, int D, const int32_t* table, int subsets, int m,
                       void* workspace, size_t workspace_bytes, double* out, void* stream);
 
+/* ---- on-device evaluation: improved precision / recall and density / coverage (added symbols only: the ABI version stays 4) ---------- *
+ * The k-nearest-neighbour manifold metrics (Kynkaanniemi et al. 2019; Naeem et al. 2020) over A = na real and B = nb fake rows of D fp32 features, row strides >= D:
+ *   d2(x, y) = max(0, (|x|^2 + |y|^2) - 2 x.y)                      fp64, every operation rounded on its own; a NaN stays a NaN and compares false everywhere
+ *   rad2_k(X)[i] = the k-th smallest d2(x_i, x_j) over j != i         self excluded by index: a duplicate row is a neighbour at distance 0
+ *   precision = #{j : exists i, d2(b_j, a_i) <= rA[i]} / nb           recall = #{i : exists j, d2(a_i, b_j) <= rB[j]} / na
+ *   density = sum_j #{i : d2(b_j, a_i) <= rA[i]} / (k nb)             coverage = #{i : min_j d2(a_i, b_j) <= rA[i]} / na
+ * Every comparison is <=.  The dot products run through v_mfma_f64_16x16x4_f64 with the contraction over D, as in dcv_eval_kid_sums (64 x 64 tile per workgroup,
+ * one 16-byte read per lane feeding four MFMAs where D, the strides and the bases allow it, four guarded 4-byte reads otherwise); the n x n distance matrix is never
+ * written.  A workgroup owns 64 rows and a share of the column tiles (s, s + S, ...); what the shares leave is combined by operations that do not depend on the
+ * order (the k smallest of a multiset, integer sums, minima), so every result is the same bits for every S.  No atomic.  col_splits = 0: the library chooses
+ * S = max(1, min(64, column tiles, 512 / row tiles)) (tiles of 64); 1 .. 64 forces S.  1 <= D <= 4096, 1 <= k <= 16, fewer than 2^31 rows; every refusal
+ * (DCV_EINVAL, DCV_EWORKSPACE) is returned before the first launch.
+ *
+ * norms[i] = sum_d x[i][d]^2 in fp64, features ascending.  One launch.  1 <= n < 2^31. */
+int dcv_eval_row_norms(const float* x, int64_t n, int D, int64_t row_stride, double* norms, void* stream);
+/* rad2[i] = rad2_k(X)[i] for the n rows of x with their norms (+inf where fewer than k distances are not NaN).  The first launch keeps, per row and share, the k
+ * smallest d2 in the workspace (per tile the distances pass through one LDS tile and four lanes per row scan them into ascending lists in registers); the second
+ * merges a row's S lists.  Two launches.  k + 1 <= n < 2^31; workspace of at least dcv_eval_knn_workspace_bytes(n, k, col_splits) = S * n * k * 8 (0: out of range). */
+size_t dcv_eval_knn_workspace_bytes(int64_t n_rows, int k, int col_splits);
+int dcv_eval_knn_radii(const float* x, int64_t n, int D, int64_t row_stride, const double* norms, int k, int col_splits, void* workspace, size_t workspace_bytes,
+                       double* rad2, void* stream);
+/* Per query row q of `queries` against the ns rows of `support` with the supports' rad2:
+ *   count[q] = #{i : d2(q, s_i) <= rad2[i]}  (int32);   dmin2[q] = min_i d2(q, s_i)  (fp64; +inf if every distance is NaN)
+ * rad2 may be null: count is then 0 and only dmin2 is formed (coverage alone).  The first launch leaves a count and a minimum per query and share in the workspace,
+ * the second adds the counts and folds the minima.  Two launches.  1 <= nq, ns < 2^31, nq * ns < 2^53; workspace of at least
+ * dcv_eval_manifold_workspace_bytes(nq, ns, col_splits) = S * nq * 12 (0: out of range). */
+size_t dcv_eval_manifold_workspace_bytes(int64_t n_queries, int64_t n_support, int col_splits);
+int dcv_eval_manifold_counts(const float* queries, int64_t stride_q, int64_t nq, const double* norms_q, const float* support, int64_t stride_s, int64_t ns,
+                             const double* norms_s, const double* rad2, int D, int col_splits, void* workspace, size_t workspace_bytes, int32_t* count, double* dmin2,
+                             void* stream);
+/* The integers a metric is a ratio of, over the n query rows of one dcv_eval_manifold_counts call, as doubles (64-bit integer sums, exact below 2^53):
+ *   out[0] = #{count > 0};  out[1] = sum count;  out[2] = #{dmin2 <= own_rad2} (0 when own_rad2 is null);  out[3] = #{norms not finite}
+ * own_rad2: the QUERIES' own radii (coverage compares a real row's nearest fake with the real row's radius); norms: the queries' norms.  One launch, one workgroup. */
+int dcv_eval_manifold_reduce(const int32_t* count, const double* dmin2, const double* own_rad2, const double* norms, int64_t n, double* out, void* stream);
+
 /* ---- bf16 channels-last ("CL16") data path -------------------------------------------------- *
  * BASELINE.json configs[2] ("surreal-depth1, bf16 MFMA") and configs[4] ("fp16 MFMA") name 16-bit variants of the same step
  * (config/surreal-depth1.yml:5,47-76, config/isogd-flow.yml; the reference itself is fp32-only).  This is that path as a DATA path:

@@ -4,6 +4,8 @@
 (c) dcv_eval_inception_update at (100, 400).
 (d) One Evaluator.evaluate of 1000 samples of isogd-depth in batches of 50 with all three metrics, against the same sampling loop alone; the extractor is a stand-in
     that returns free views of the clip (2048 features, 400 logits), so the difference is this module's launches and its host finalisation.
+(e) The k-nearest-neighbour metrics at 10000 x 10000, D = 2048: dcv_eval_knn_radii and dcv_eval_manifold_counts with k = 3 and 5 (2 n^2 D FLOP each,
+    all of it executed: no symmetry is used), the norms, and manifold_metrics end to end; dcv_eval_kid_sums of (b), timed in the same process, is the yardstick.
 FLOP counts are the nominal ones of the full matrices (2 n D^2 for the Gram, 3 * subsets * 2 m^2 D for the kernel distance); the kernels execute the upper tiles of
 the symmetric blocks only.  The measuring leg is a fresh child process under its own time limit; a failure ends the script there.
 Usage: python tools/eval_cost.py [out.txt]      (default out: profiles/eval_cost.txt; the record also goes to stdout)"""
@@ -102,6 +104,28 @@ def measure(out):
                  "%.2f s / %.2f s wall clock in two runs, the same sampling loop alone %.2f s / %.2f s; %d launches of this module; of the rest the host's "
                  "frechet_distance (two symmetric eigenproblems of %d x %d) takes %.2f s" % (D, rows[0][0], rows[1][0], rows[0][1], rows[1][1], n_launch, D, D, t_fid))
     lines.append("    result: " + ", ".join("%s %.6g" % kv for kv in sorted(res.items())))
+    # ---- (e) precision / recall and density / coverage ----
+    n = 10000
+    exe = tflop * 2.0 / 3.0 / ms * 1e3      # (b)'s executed rate: the upper tiles of the two symmetric blocks and the whole cross block, 2/3 of nominal
+    lines.append("(e) k-nearest-neighbour metrics, %d x %d, D = %d (5 timed after 2; yardstick dcv_eval_kid_sums above: %.1f TFLOP/s executed)" % (n, n, D, exe))
+    norm_a, norm_b = E.row_norms(fa), E.row_norms(fb)
+    lines.append("    dcv_eval_row_norms (%d, %d): %.1f us" % (n, D, timed(lambda: E.row_norms(fa)) * 1e3))
+    tf = 2.0 * n * n * D / 1e12
+    for k in (3, 5):
+        ms_k = timed(lambda: E.knn_radii(fa, k, norms=norm_a), 5, 2)
+        rad = E.knn_radii(fa, k, norms=norm_a)
+        ms_c = timed(lambda: E.manifold_counts(fb, fa, rad, norms_q=norm_b, norms_s=norm_a), 5, 2)
+        lines.append("    k = %d: dcv_eval_knn_radii %.2f ms, %.2f TFLOP -> %.1f TFLOP/s fp64; dcv_eval_manifold_counts %.2f ms -> %.1f TFLOP/s fp64" %
+                     (k, ms_k, tf, tf / ms_k * 1e3, ms_c, tf / ms_c * 1e3))
+    for cs in (1, 2, 3, 4, 6):
+        lines.append("    k = 5, col_splits %d: dcv_eval_knn_radii %.2f ms, dcv_eval_manifold_counts %.2f ms" %
+                     (cs, timed(lambda: E.knn_radii(fa, 5, cs, norms=norm_a), 3, 1), timed(lambda: E.manifold_counts(fb, fa, rad, cs, norms_q=norm_b, norms_s=norm_a), 3, 1)))
+    E.manifold_metrics(fa, fb)
+    torch.cuda.synchronize()
+    h0 = time.perf_counter(); l0 = E.launches()
+    res = E.manifold_metrics(fa, fb)
+    lines.append("    manifold_metrics end to end (k 3 and 5: norms, 3 radius vectors, 3 counts, reductions, host read): %.1f ms, %d launches; %s" %
+                 ((time.perf_counter() - h0) * 1e3, E.launches() - l0, ", ".join("%s %.4f" % kv for kv in sorted(res.items()))))
     print("\n".join(lines))
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     open(out, "w").write("\n".join(lines) + "\n")
