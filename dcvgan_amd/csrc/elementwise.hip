@@ -826,78 +826,150 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 // up to ADAM_MT tensors of one optimiser in one launch (the DCVGAN models have ~100 small parameter tensors:
 // one launch each was ~100 x 5 us of dispatch per step for 70 MB of state)
 #define ADAM_MT 24
+// THE multi-tensor table.  What every table shares, passed by value inside the kernel's own pack of pointers: the tensors' element counts and the
+// prefix sum of their block counts.  A block is 256 threads; for the elementwise kernels it covers 4096 elements (MT_BLOCK), the spectral matrix-vector kernels
+// count their own chunks in first_block.
+#define MT_BLOCK 4096
+struct MtTable {
+    int64_t n[ADAM_MT];
+    int32_t first_block[ADAM_MT + 1];
+};
+struct MtWhere {
+    int t, blk;      // this block's tensor, and its index among that tensor's blocks
+};
+__device__ __forceinline__ MtWhere mt_where(const MtTable& k, int nt) {
+    int t = 0;
+    while (t + 1 < nt && (int)blockIdx.x >= k.first_block[t + 1]) ++t;
+    return MtWhere{t, (int)blockIdx.x - k.first_block[t]};
+}
+// A block's (at most) 4096 elements from `base`, 16 per thread.  one(j) handles element j, quad(i) the four elements from i with 16-byte accesses.
+// strided: element base + e * 256 + tid for e = 0 .. 15.
+template <class One>
+__device__ __forceinline__ void mt_strided(int64_t base, int64_t n, One one) {
+#pragma unroll 4
+    for (int e = 0; e < 16; ++e) {
+        const int64_t i = base + e * 256 + threadIdx.x;
+        if (i >= n) break;
+        one(i);
+    }
+}
+// `aligned` (the caller's predicate: every base the functors touch is on a 16-byte boundary, hence so is every block's first element): four quads per thread at
+// base + (q * 256 + tid) * 4, the tensor's last 1..3 elements one at a time.  Otherwise one of exactly two orders.  MT_STRIDED hands a thread OTHER elements than
+// the aligned branch does: right for kernels whose elements are independent (their results cannot depend on who computes them), and its accesses coalesce.
+// MT_QUAD_ORDER visits the aligned branch's elements per thread in the aligned branch's order, one at a time: for a kernel that adds a thread's elements up in
+// fp32, where the order is the result, so that the sum's bits do not depend on the alignment.  Do not swap one for the other: it changes bits.
+enum MtOrder { MT_STRIDED, MT_QUAD_ORDER };
+template <MtOrder ORDER, class Quad, class One>
+__device__ __forceinline__ void mt_traverse(int64_t base, int64_t n, bool aligned, Quad quad, One one) {
+    if (aligned) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t i = base + (int64_t)(q * 256 + threadIdx.x) * 4;
+            if (i + 4 <= n) {
+                quad(i);
+            } else {
+                for (int64_t j = i; j < n; ++j) one(j);
+            }
+        }
+    } else if (ORDER == MT_QUAD_ORDER) {
+        for (int q = 0; q < 4; ++q) {
+            const int64_t i = base + (int64_t)(q * 256 + threadIdx.x) * 4;
+            for (int64_t j = i; j < i + 4 && j < n; ++j) one(j);
+        }
+    } else {
+        mt_strided(base, n, one);
+    }
+}
+__device__ __forceinline__ bool mt_aligned16(const void* a, const void* b = nullptr) {
+    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
+}
+
+// ---- the host side of the multi-tensor table (MtTable) ------------------------------------------------------------------------------------------------------
+static int64_t mt_blocks(int64_t numel) { return (numel + MT_BLOCK - 1) / MT_BLOCK; }
+// every table's block count fits the int the kernels index with (numels already known to be >= 0)
+static bool mt_tables_fit(int n_tensors, const int64_t* numel) {
+    int64_t blocks = 0;
+    for (int t = 0; t < n_tensors; ++t) {
+        blocks = (t % ADAM_MT ? blocks : 0) + mt_blocks(numel[t]);
+        if (blocks > INT32_MAX) return false;
+    }
+    return true;
+}
+// Walks n_tensors in tables of ADAM_MT.  Per table: a zeroed Pack, fill(k, slot, tensor) sets the kernel's own fields of a slot (pointers, tab.n), first_block is
+// the prefix sum of blocks_of(tensor); a table without blocks is skipped, every other goes to launch(k, nt, blocks, blocks of the tables before it), which returns
+// what DCV_LAUNCH_CHECK gave.  Every check of the arguments belongs BEFORE the call: nothing here refuses.
+template <class Pack, class Blocks, class Fill, class Launch>
+static int mt_for_tables(int n_tensors, Blocks blocks_of, Fill fill, Launch launch) {
+    int64_t before = 0;
+    for (int t0 = 0; t0 < n_tensors; t0 += ADAM_MT) {
+        Pack k;
+        memset(&k, 0, sizeof(k));
+        const int nt = std::min(ADAM_MT, n_tensors - t0);
+        int blocks = 0;
+        for (int t = 0; t < nt; ++t) {
+            fill(k, t, t0 + t);
+            k.tab.first_block[t] = blocks;
+            blocks += (int)blocks_of(t0 + t);
+        }
+        k.tab.first_block[nt] = blocks;
+        if (blocks == 0) continue;
+        const int rc = launch(k, nt, blocks, before);
+        if (rc != DCV_OK) return rc;
+        before += blocks;
+    }
+    return DCV_OK;
+}
+
 struct AdamPack {
     float* p[ADAM_MT];
     const float* g[ADAM_MT];
     float* m[ADAM_MT];
     float* v[ADAM_MT];
-    int64_t n[ADAM_MT];
-    int32_t first_block[ADAM_MT + 1];   // prefix sum of the tensors' block counts (4096 elements per block)
+    MtTable tab;
 };
 __device__ __forceinline__ void adam_multi_body(const AdamPack& k, int nt, const AdamScalars& sc) {
-    int t = 0;
-    while (t + 1 < nt && (int)blockIdx.x >= k.first_block[t + 1]) ++t;
-    const int64_t base = (int64_t)((int)blockIdx.x - k.first_block[t]) * 4096;
-    float* __restrict__ p = k.p[t];
-    const float* __restrict__ g = k.g[t];
-    float* __restrict__ m = k.m[t];
-    float* __restrict__ v = k.v[t];
-    const int64_t n = k.n[t];
-#pragma unroll 4
-    for (int e = 0; e < 16; ++e) {
-        const int64_t i = base + e * 256 + threadIdx.x;
-        if (i >= n) break;
+    const MtWhere at = mt_where(k.tab, nt);
+    float* __restrict__ p = k.p[at.t];
+    const float* __restrict__ g = k.g[at.t];
+    float* __restrict__ m = k.m[at.t];
+    float* __restrict__ v = k.v[at.t];
+    mt_strided((int64_t)at.blk * MT_BLOCK, k.tab.n[at.t], [&](int64_t i) {      // (no 16-byte branch here)
         float pi = p[i], mi = m[i], vi = v[i];
         adam_update(pi, g[i], mi, vi, sc);
         m[i] = mi; v[i] = vi; p[i] = pi;
-    }
+    });
 }
 __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamPack k, int nt, const AdamScalars sc) { adam_multi_body(k, nt, sc); }
 
 // ------------------------------------------------------------------------- //
 // Gradient guard: global norm, clip coefficient, non-finite skip and loss-scale update, all decided on the device
 // ------------------------------------------------------------------------- //
-// Stage 1 (guard_partial_kernel): adam_multi_kernel's block mapping over the gradients (4096 elements per 256-thread block, pointer table by value).  A thread
+// Stage 1 (guard_partial_kernel): the multi-tensor table's block mapping (MtTable) over the gradients.  A thread
 // squares and adds its (at most) 16 elements in fp32 and counts those whose exponent bits are all ones; the block combines both in double, in block_sum's fixed
 // order, and stores ONE partial sum and ONE count.  Stage 2 (guard_decide_kernel): one workgroup adds the partials in a fixed order and writes the decision into
 // the state array (DCV_GUARD_* in dcvgan_hip.h).  No atomics anywhere: the same gradients give the same bits.
 struct GuardPack {
     const float* g[ADAM_MT];
-    int64_t n[ADAM_MT];
-    int32_t first_block[ADAM_MT + 1];
+    MtTable tab;
 };
 __device__ __forceinline__ void guard_take(float x, float& ss, int& bad) {
-    ss += x * x;
+    // Explicitly fused, like ema_one.  Written `ss += x * x`, a thread's first two squares x0 x0 + x1 x1 may be contracted either way round (fma(x1, x1, x0 x0) or
+    // fma(x0, x0, x1 x1)): the compiler's pick, and it moved with the code around this function.  This is the chain every build so far has computed.
+    ss = fmaf(x, x, ss);
     bad += ((__float_as_uint(x) & 0x7f800000u) == 0x7f800000u) ? 1 : 0;
 }
 __global__ __launch_bounds__(256) void guard_partial_kernel(const GuardPack k, int nt, int block0, double* __restrict__ part, uint32_t* __restrict__ cnt) {
     __shared__ double red[8];
-    int t = 0;
-    while (t + 1 < nt && (int)blockIdx.x >= k.first_block[t + 1]) ++t;
-    const int64_t base = (int64_t)((int)blockIdx.x - k.first_block[t]) * 4096;
-    const float* __restrict__ g = k.g[t];
-    const int64_t n = k.n[t];
+    const MtWhere at = mt_where(k.tab, nt);
+    const float* __restrict__ g = k.g[at.t];
     float ss = 0.f;
     int bad = 0;
-    if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {      // base (hence every block's first element) on a 16-byte boundary: 4 x 16-byte loads per thread
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int64_t i = base + (int64_t)(e * 256 + threadIdx.x) * 4;
-            if (i + 4 <= n) {
-                const float4 x = *reinterpret_cast<const float4*>(g + i);
-                guard_take(x.x, ss, bad); guard_take(x.y, ss, bad); guard_take(x.z, ss, bad); guard_take(x.w, ss, bad);
-            } else {
-                for (int64_t j = i; j < n; ++j) guard_take(g[j], ss, bad);      // the tensor's last 1..3 elements
-            }
-        }
-    } else {
-#pragma unroll 4
-        for (int e = 0; e < 16; ++e) {
-            const int64_t i = base + e * 256 + threadIdx.x;
-            if (i >= n) break;
-            guard_take(g[i], ss, bad);
-        }
-    }
+    mt_traverse<MT_STRIDED>((int64_t)at.blk * MT_BLOCK, k.tab.n[at.t], mt_aligned16(g),
+        [&](int64_t i) {
+            const float4 x = *reinterpret_cast<const float4*>(g + i);
+            guard_take(x.x, ss, bad); guard_take(x.y, ss, bad); guard_take(x.z, ss, bad); guard_take(x.w, ss, bad);
+        },
+        [&](int64_t j) { guard_take(g[j], ss, bad); });
     double acc[2] = {(double)ss, (double)bad};      // (counts up to 4096: exact)
     block_sum<2>(acc, red);
     if (threadIdx.x == 0) {
@@ -984,7 +1056,7 @@ __global__ __launch_bounds__(256) void adam_multi_guarded_kernel(const AdamPack 
 // EMA of model weights (the sampling twin): e += w (p - e), count, warm-up and skip decided on the device
 // ------------------------------------------------------------------------- //
 // ema_prepare_kernel (one thread, like guard_adam_prepare_kernel) reads the guard's decision; unless the update is skipped it takes the number of updates applied
-// so far from the block, forms the weight 1 - d_t in double, rounds it once and advances the count.  ema_multi_kernel has adam_multi_kernel's block mapping; a
+// so far from the block, forms the weight 1 - d_t in double, rounds it once and advances the count.  ema_multi_kernel has the multi-tensor table's block mapping (MtTable); a
 // tensor is either averaged (fp32) or copied dword for dword (BatchNorm running statistics, num_batches_tracked).  No atomics: the same inputs give the same bits.
 struct EmaBlock {      // 16 x 4 bytes, caller-owned (DCV_EMA_BLOCK_BYTES); [0] is the number of updates applied, which a host may read back
     int32_t count, skip;
@@ -995,8 +1067,7 @@ static_assert(sizeof(EmaBlock) == 64, "EmaBlock is the 64-byte block the header 
 struct EmaPack {
     float* e[ADAM_MT];
     const float* s[ADAM_MT];
-    int64_t n[ADAM_MT];
-    int32_t first_block[ADAM_MT + 1];
+    MtTable tab;
     uint32_t copy_mask;      // bit t: tensor t is copied (mode 1), not averaged
 };
 __global__ void ema_prepare_kernel(EmaBlock* __restrict__ b, const float* __restrict__ state, double decay, int warmup) {
@@ -1013,57 +1084,28 @@ __device__ __forceinline__ float ema_one(float e, float p, float w) { return fma
 __global__ __launch_bounds__(256) void ema_multi_kernel(const EmaPack k, int nt, const EmaBlock* __restrict__ b) {
     if (b->skip) return;      // before any access to a tensor
     const float w = b->w;
-    int t = 0;
-    while (t + 1 < nt && (int)blockIdx.x >= k.first_block[t + 1]) ++t;
-    const int64_t base = (int64_t)((int)blockIdx.x - k.first_block[t]) * 4096;
+    const MtWhere at = mt_where(k.tab, nt);
+    const int t = at.t;
     float* __restrict__ e = k.e[t];
     const float* __restrict__ s = k.s[t];
-    const int64_t n = k.n[t];
-    const bool vec = ((reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(s)) & 15) == 0;      // both bases (hence every block's first element) on 16-byte boundaries
+    const int64_t n = k.tab.n[t], base = (int64_t)at.blk * MT_BLOCK;
+    const bool vec = mt_aligned16(e, s);
     if ((k.copy_mask >> t) & 1u) {      // bit patterns, no arithmetic
         uint32_t* __restrict__ eu = reinterpret_cast<uint32_t*>(e);
         const uint32_t* __restrict__ su = reinterpret_cast<const uint32_t*>(s);
-        if (vec) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int64_t i = base + (int64_t)(q * 256 + threadIdx.x) * 4;
-                if (i + 4 <= n) {
-                    *reinterpret_cast<uint4*>(eu + i) = *reinterpret_cast<const uint4*>(su + i);
-                } else {
-                    for (int64_t j = i; j < n; ++j) eu[j] = su[j];      // the tensor's last 1..3 dwords
-                }
-            }
-        } else {
-#pragma unroll 4
-            for (int q = 0; q < 16; ++q) {
-                const int64_t i = base + q * 256 + threadIdx.x;
-                if (i >= n) break;
-                eu[i] = su[i];
-            }
-        }
+        mt_traverse<MT_STRIDED>(base, n, vec,
+            [&](int64_t i) { *reinterpret_cast<uint4*>(eu + i) = *reinterpret_cast<const uint4*>(su + i); },
+            [&](int64_t j) { eu[j] = su[j]; });
         return;
     }
-    if (vec) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int64_t i = base + (int64_t)(q * 256 + threadIdx.x) * 4;
-            if (i + 4 <= n) {
-                const float4 p = *reinterpret_cast<const float4*>(s + i);
-                float4 x = *reinterpret_cast<const float4*>(e + i);
-                x.x = ema_one(x.x, p.x, w); x.y = ema_one(x.y, p.y, w); x.z = ema_one(x.z, p.z, w); x.w = ema_one(x.w, p.w, w);
-                *reinterpret_cast<float4*>(e + i) = x;
-            } else {
-                for (int64_t j = i; j < n; ++j) e[j] = ema_one(e[j], s[j], w);      // the tensor's last 1..3 elements
-            }
-        }
-    } else {
-#pragma unroll 4
-        for (int q = 0; q < 16; ++q) {
-            const int64_t i = base + q * 256 + threadIdx.x;
-            if (i >= n) break;
-            e[i] = ema_one(e[i], s[i], w);
-        }
-    }
+    mt_traverse<MT_STRIDED>(base, n, vec,
+        [&](int64_t i) {
+            const float4 p = *reinterpret_cast<const float4*>(s + i);
+            float4 x = *reinterpret_cast<const float4*>(e + i);
+            x.x = ema_one(x.x, p.x, w); x.y = ema_one(x.y, p.y, w); x.z = ema_one(x.z, p.z, w); x.w = ema_one(x.w, p.w, w);
+            *reinterpret_cast<float4*>(e + i) = x;
+        },
+        [&](int64_t j) { e[j] = ema_one(e[j], s[j], w); });
 }
 
 // ------------------------------------------------------------------------- //
@@ -1072,7 +1114,7 @@ __global__ __launch_bounds__(256) void ema_multi_kernel(const EmaPack k, int nt,
 // A weight is a matrix of M rows (cout) and K columns, contiguous.  Per table of up to ADAM_MT tensors:
 //   sn_cols_kernel   t = W^T u      one block per SN_KC columns of a tensor; leaves t and the block's sum of t^2 (double) in the workspace
 //   sn_rows_kernel   s = W v        one block per SN_MR rows (one wave each); v = t / max(|t|, eps); leaves s and the block's sum of s^2
-//   sn_scale_kernel  u = s / max(|s|, eps); sigma = u^T s; W_sn = W / max(sigma, eps)     adam_multi_kernel's block mapping over the M K elements
+//   sn_scale_kernel  u = s / max(|s|, eps); sigma = u^T s; W_sn = W / max(sigma, eps)     MtTable's block mapping over the M K elements
 // Every block that needs a norm adds the tensor's block partials itself, all in the same fixed order (so all of them get the same bits), and one thread forms the
 // square root and the reciprocal in double.  Products and a thread's running sums are fp32, everything above a thread is double.  No atomics.
 // The first block of a tensor writes the vector (v, u, sigma) that its kernel has just normalised.
@@ -1086,12 +1128,12 @@ struct SnPack {
     float* sigma[ADAM_MT];
     float* g[ADAM_MT];         // project only
     int32_t rows[ADAM_MT], cols[ADAM_MT];
-    int32_t first_block[ADAM_MT + 1];
+    MtTable tab;               // n = rows * cols; first_block counts the launched kernel's own blocks (column chunks, row chunks or blocks of 4096 elements)
     int64_t ws_off[ADAM_MT];   // the tensor's part of the workspace, in doubles: [partials of t | partials of s or of <G, W_sn> | t (floats) | s (floats)]
 };
 __host__ __device__ __forceinline__ int sn_kchunks(int K) { return (K + SN_KC - 1) / SN_KC; }
 __host__ __device__ __forceinline__ int sn_mchunks(int M) { return (M + SN_MR - 1) / SN_MR; }
-__host__ __device__ __forceinline__ int64_t sn_eblocks(int M, int K) { return ((int64_t)M * K + 4095) / 4096; }
+__host__ __device__ __forceinline__ int64_t sn_eblocks(int M, int K) { return ((int64_t)M * K + MT_BLOCK - 1) / MT_BLOCK; }
 // One tensor's workspace part, every array starting on a 16-byte boundary (counts in doubles, each rounded up to even; the part itself starts on an even offset of
 // a 256-byte aligned buffer).  The second partial array serves the update's s (mchunks) and the projection's inner product (eblocks).
 __host__ __device__ __forceinline__ int64_t sn_even(int64_t n) { return (n + 1) / 2 * 2; }
@@ -1126,11 +1168,6 @@ __device__ __forceinline__ float sn_inv_norm(double ss, double eps, float* slot)
     __syncthreads();
     return *slot;
 }
-__device__ __forceinline__ int sn_tensor_of_block(const SnPack& k, int nt) {
-    int t = 0;
-    while (t + 1 < nt && (int)blockIdx.x >= k.first_block[t + 1]) ++t;
-    return t;
-}
 
 __global__ void sn_prepare_kernel(int32_t* __restrict__ skip, const float* __restrict__ state) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -1143,8 +1180,8 @@ __global__ __launch_bounds__(256) void sn_cols_kernel(const SnPack k, int nt, in
     __shared__ double red[8];
     __shared__ float inv_slot;
     __shared__ float part[4][SN_KC];
-    const int ti = sn_tensor_of_block(k, nt);
-    const int chunk = (int)blockIdx.x - k.first_block[ti];
+    const MtWhere at = mt_where(k.tab, nt);
+    const int ti = at.t, chunk = at.blk;
     const int M = k.rows[ti], K = k.cols[ti];
     const float* __restrict__ w = k.w[ti];
     const SnWs a = sn_ws(ws, k, ti);
@@ -1195,8 +1232,8 @@ __global__ __launch_bounds__(256) void sn_rows_kernel(const SnPack k, int nt, in
     __shared__ double red[8];
     __shared__ float inv_slot;
     __shared__ float srow[SN_MR];
-    const int ti = sn_tensor_of_block(k, nt);
-    const int chunk = (int)blockIdx.x - k.first_block[ti];
+    const MtWhere at = mt_where(k.tab, nt);
+    const int ti = at.t, chunk = at.blk;
     const int M = k.rows[ti], K = k.cols[ti];
     const float* __restrict__ w = k.w[ti];
     const SnWs a = sn_ws(ws, k, ti);
@@ -1244,9 +1281,9 @@ __global__ __launch_bounds__(256) void sn_scale_kernel(const SnPack k, int nt, i
     if (skip != nullptr && *skip) return;
     __shared__ double red[8];
     __shared__ float inv_slot, sig_slot;
-    const int ti = sn_tensor_of_block(k, nt);
-    const int blk = (int)blockIdx.x - k.first_block[ti];
-    const int M = k.rows[ti], K = k.cols[ti];
+    const MtWhere at = mt_where(k.tab, nt);
+    const int ti = at.t, blk = at.blk;
+    const int M = k.rows[ti];
     const SnWs a = sn_ws(ws, k, ti);
     float inv = 1.f;
     const float* __restrict__ usrc = k.u[ti];
@@ -1271,27 +1308,13 @@ __global__ __launch_bounds__(256) void sn_scale_kernel(const SnPack k, int nt, i
     }
     const float* __restrict__ w = k.w[ti];
     float* __restrict__ o = k.w_sn[ti];
-    const int64_t n = (int64_t)M * K, base = (int64_t)blk * 4096;
-    if (((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(o)) & 15) == 0) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int64_t i = base + (int64_t)(q * 256 + threadIdx.x) * 4;
-            if (i + 4 <= n) {
-                float4 x = *reinterpret_cast<const float4*>(w + i);
-                x.x *= isg; x.y *= isg; x.z *= isg; x.w *= isg;
-                *reinterpret_cast<float4*>(o + i) = x;
-            } else {
-                for (int64_t j = i; j < n; ++j) o[j] = w[j] * isg;      // the tensor's last 1..3 elements
-            }
-        }
-    } else {
-#pragma unroll 4
-        for (int q = 0; q < 16; ++q) {
-            const int64_t i = base + q * 256 + threadIdx.x;
-            if (i >= n) break;
-            o[i] = w[i] * isg;
-        }
-    }
+    mt_traverse<MT_STRIDED>((int64_t)blk * MT_BLOCK, k.tab.n[ti], mt_aligned16(w, o),
+        [&](int64_t i) {
+            float4 x = *reinterpret_cast<const float4*>(w + i);
+            x.x *= isg; x.y *= isg; x.z *= isg; x.w *= isg;
+            *reinterpret_cast<float4*>(o + i) = x;
+        },
+        [&](int64_t j) { o[j] = w[j] * isg; });
 }
 
 // The projection of a gradient G = dL/dW_sn onto the raw weight: dW = (G - <G, W_sn> u v^T) / max(sigma, eps), in place on G.
@@ -1299,30 +1322,18 @@ __global__ __launch_bounds__(256) void sn_scale_kernel(const SnPack k, int nt, i
 // partials in the same order, one thread rounds the inner product and 1 / sigma to fp32, then g <- fmaf(-(c u_m), v_k, g) * (1 / sigma).
 __global__ __launch_bounds__(256) void sn_inner_kernel(const SnPack k, int nt, double* __restrict__ ws) {
     __shared__ double red[8];
-    const int ti = sn_tensor_of_block(k, nt);
-    const int blk = (int)blockIdx.x - k.first_block[ti];
+    const MtWhere at = mt_where(k.tab, nt);
+    const int ti = at.t, blk = at.blk;
     const float* __restrict__ g = k.g[ti];
     const float* __restrict__ y = k.w_sn[ti];
-    const int64_t n = (int64_t)k.rows[ti] * k.cols[ti], base = (int64_t)blk * 4096;
     float acc = 0.f;
-    if (((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(y)) & 15) == 0) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int64_t i = base + (int64_t)(q * 256 + threadIdx.x) * 4;
-            if (i + 4 <= n) {
-                const float4 a = *reinterpret_cast<const float4*>(g + i);
-                const float4 b = *reinterpret_cast<const float4*>(y + i);
-                acc += a.x * b.x; acc += a.y * b.y; acc += a.z * b.z; acc += a.w * b.w;
-            } else {
-                for (int64_t j = i; j < n; ++j) acc += g[j] * y[j];
-            }
-        }
-    } else {      // the same elements per thread in the same order, one at a time: the bits do not depend on the alignment
-        for (int q = 0; q < 4; ++q) {
-            const int64_t i = base + (int64_t)(q * 256 + threadIdx.x) * 4;
-            for (int64_t j = i; j < i + 4 && j < n; ++j) acc += g[j] * y[j];
-        }
-    }
+    mt_traverse<MT_QUAD_ORDER>((int64_t)blk * MT_BLOCK, k.tab.n[ti], mt_aligned16(g, y),      // a sum: the bits must not depend on the alignment
+        [&](int64_t i) {
+            const float4 a = *reinterpret_cast<const float4*>(g + i);
+            const float4 b = *reinterpret_cast<const float4*>(y + i);
+            acc += a.x * b.x; acc += a.y * b.y; acc += a.z * b.z; acc += a.w * b.w;
+        },
+        [&](int64_t j) { acc += g[j] * y[j]; });
     double s[1] = {(double)acc};
     block_sum<1>(s, red);
     if (threadIdx.x == 0) sn_ws(ws, k, ti).part_s[blk] = s[0];
@@ -1331,8 +1342,8 @@ __device__ __forceinline__ float sn_project_one(float g, float c, float um, floa
 __global__ __launch_bounds__(256) void sn_project_kernel(const SnPack k, int nt, double eps, double* __restrict__ ws) {
     __shared__ double red[8];
     __shared__ float c_slot, isg_slot;
-    const int ti = sn_tensor_of_block(k, nt);
-    const int blk = (int)blockIdx.x - k.first_block[ti];
+    const MtWhere at = mt_where(k.tab, nt);
+    const int ti = at.t, blk = at.blk;
     const int M = k.rows[ti], K = k.cols[ti];
     const double inner = sn_sum_partials(sn_ws(ws, k, ti).part_s, sn_eblocks(M, K), red);
     if (threadIdx.x == 0) {
@@ -1344,35 +1355,20 @@ __global__ __launch_bounds__(256) void sn_project_kernel(const SnPack k, int nt,
     float* __restrict__ g = k.g[ti];
     const float* __restrict__ u = k.u[ti];
     const float* __restrict__ v = k.v[ti];
-    const int64_t n = (int64_t)M * K, base = (int64_t)blk * 4096;
-    if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+    mt_traverse<MT_STRIDED>((int64_t)blk * MT_BLOCK, k.tab.n[ti], mt_aligned16(g),
+        [&](int64_t i) {
+            float4 x = *reinterpret_cast<const float4*>(g + i);
+            float e[4] = {x.x, x.y, x.z, x.w};
+            int m = (int)(i / K), c0 = (int)(i - (int64_t)m * K);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int64_t i = base + (int64_t)(q * 256 + threadIdx.x) * 4;
-            if (i + 4 <= n) {
-                float4 x = *reinterpret_cast<const float4*>(g + i);
-                float e[4] = {x.x, x.y, x.z, x.w};
-                int m = (int)(i / K), c0 = (int)(i - (int64_t)m * K);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    e[j] = sn_project_one(e[j], c, u[m], v[c0], isg);
-                    if (++c0 == K) { c0 = 0; ++m; }
-                }
-                x.x = e[0]; x.y = e[1]; x.z = e[2]; x.w = e[3];
-                *reinterpret_cast<float4*>(g + i) = x;
-            } else {
-                for (int64_t j = i; j < n; ++j) { const int m = (int)(j / K); g[j] = sn_project_one(g[j], c, u[m], v[(int)(j - (int64_t)m * K)], isg); }
+            for (int j = 0; j < 4; ++j) {
+                e[j] = sn_project_one(e[j], c, u[m], v[c0], isg);
+                if (++c0 == K) { c0 = 0; ++m; }
             }
-        }
-    } else {
-#pragma unroll 4
-        for (int q = 0; q < 16; ++q) {
-            const int64_t i = base + q * 256 + threadIdx.x;
-            if (i >= n) break;
-            const int m = (int)(i / K);
-            g[i] = sn_project_one(g[i], c, u[m], v[(int)(i - (int64_t)m * K)], isg);
-        }
-    }
+            x.x = e[0]; x.y = e[1]; x.z = e[2]; x.w = e[3];
+            *reinterpret_cast<float4*>(g + i) = x;
+        },
+        [&](int64_t j) { const int m = (int)(j / K); g[j] = sn_project_one(g[j], c, u[m], v[(int)(j - (int64_t)m * K)], isg); });
 }
 
 // ------------------------------------------------------------------------- //
@@ -2027,27 +2023,28 @@ int dcv_adam_step(float* p, const float* g, float* m, float* v, int64_t n, doubl
 }
 
 
+// both Adam entry points: every tensor checked before the first launch
+static int adam_tensors_ok(const char* who, int n_tensors, float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* numel) {
+    for (int t = 0; t < n_tensors; ++t)
+        if (!p[t] || !g[t] || !m[t] || !v[t] || numel[t] < 0) return fail(DCV_EINVAL, "%s: null tensor", who);
+    if (!mt_tables_fit(n_tensors, numel)) return fail(DCV_EINVAL, "%s: too many elements", who);
+    return DCV_OK;
+}
+static auto adam_fill(float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* numel) {
+    return [=](AdamPack& k, int t, int i) { k.p[t] = p[i]; k.g[t] = g[i]; k.m[t] = m[i]; k.v[t] = v[i]; k.tab.n[t] = numel[i]; };
+}
+
 int dcv_adam_step_multi(int n_tensors, float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* numel,
                         double lr, double beta1, double beta2, double eps, double weight_decay, int step, double grad_scale, void* stream) {
     if (n_tensors < 0 || (n_tensors > 0 && (!p || !g || !m || !v || !numel)) || step < 1) return fail(DCV_EINVAL, "adam_step_multi: bad arguments");
+    if (const int rc = adam_tensors_ok("adam_step_multi", n_tensors, p, g, m, v, numel)) return rc;
     const AdamScalars sc = adam_scalars(lr, beta1, beta2, eps, weight_decay, step, grad_scale);
-    for (int t0 = 0; t0 < n_tensors; t0 += ADAM_MT) {
-        AdamPack k;
-        memset(&k, 0, sizeof(k));
-        const int nt = std::min(ADAM_MT, n_tensors - t0);
-        int blocks = 0;
-        for (int t = 0; t < nt; ++t) {
-            if (!p[t0 + t] || !g[t0 + t] || !m[t0 + t] || !v[t0 + t] || numel[t0 + t] < 0) return fail(DCV_EINVAL, "adam_step_multi: null tensor");
-            k.p[t] = p[t0 + t]; k.g[t] = g[t0 + t]; k.m[t] = m[t0 + t]; k.v[t] = v[t0 + t]; k.n[t] = numel[t0 + t];
-            k.first_block[t] = blocks;
-            blocks += (int)((numel[t0 + t] + 4095) / 4096);
-        }
-        k.first_block[nt] = blocks;
-        if (blocks == 0) continue;
-        hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), k, nt, sc);
-        DCV_LAUNCH_CHECK();
-    }
-    return DCV_OK;
+    return mt_for_tables<AdamPack>(n_tensors, [&](int i) { return mt_blocks(numel[i]); }, adam_fill(p, g, m, v, numel),
+        [&](const AdamPack& k, int nt, int blocks, int64_t) {
+            hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), k, nt, sc);
+            DCV_LAUNCH_CHECK();
+            return DCV_OK;
+        });
 }
 
 // blocks of stage 1 <= total / 4096 + one ragged block per tensor; a double and a count for each
@@ -2065,30 +2062,21 @@ int dcv_grad_guard_measure(int n_tensors, const float* const* g, const int64_t* 
     int64_t nb = 0;
     for (int t = 0; t < n_tensors; ++t) {
         if (!g[t] || numel[t] < 0) return fail(DCV_EINVAL, "grad_guard_measure: null tensor");
-        nb += (numel[t] + 4095) / 4096;
+        nb += mt_blocks(numel[t]);
     }
     if (nb > INT32_MAX) return fail(DCV_EINVAL, "grad_guard_measure: too many elements");
     if ((size_t)nb * (sizeof(double) + sizeof(uint32_t)) > ws_bytes) return fail(DCV_EWORKSPACE, "grad_guard_measure: workspace too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
     double* part = static_cast<double*>(ws);
     uint32_t* cnt = reinterpret_cast<uint32_t*>(part + nb);
-    int block0 = 0;
-    for (int t0 = 0; t0 < n_tensors; t0 += ADAM_MT) {
-        GuardPack k;
-        memset(&k, 0, sizeof(k));
-        const int nt = std::min(ADAM_MT, n_tensors - t0);
-        int blocks = 0;
-        for (int t = 0; t < nt; ++t) {
-            k.g[t] = g[t0 + t]; k.n[t] = numel[t0 + t];
-            k.first_block[t] = blocks;
-            blocks += (int)((numel[t0 + t] + 4095) / 4096);
-        }
-        k.first_block[nt] = blocks;
-        if (blocks == 0) continue;
-        hipLaunchKernelGGL(guard_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, block0, part, cnt);
-        DCV_LAUNCH_CHECK();
-        block0 += blocks;
-    }
+    const int rc = mt_for_tables<GuardPack>(n_tensors, [&](int i) { return mt_blocks(numel[i]); },
+        [&](GuardPack& k, int t, int i) { k.g[t] = g[i]; k.tab.n[t] = numel[i]; },
+        [&](const GuardPack& k, int nt, int blocks, int64_t block0) {
+            hipLaunchKernelGGL(guard_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, (int)block0, part, cnt);
+            DCV_LAUNCH_CHECK();
+            return DCV_OK;
+        });
+    if (rc != DCV_OK) return rc;
     const GuardRule r{grad_scale, max_norm, growth_factor, backoff_factor, skip_nonfinite ? 1 : 0, dynamic ? 1 : 0, growth_interval};
     hipLaunchKernelGGL(guard_decide_kernel, dim3(1), dim3(256), 0, s, part, cnt, (int)nb, r, state);
     DCV_LAUNCH_CHECK();
@@ -2098,64 +2086,42 @@ int dcv_grad_guard_measure(int n_tensors, const float* const* g, const int64_t* 
 int dcv_adam_step_multi_guarded(int n_tensors, float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* numel,
                                 double lr, double beta1, double beta2, double eps, double weight_decay, int32_t* step_block, const float* state, void* stream) {
     if (n_tensors < 0 || (n_tensors > 0 && (!p || !g || !m || !v || !numel)) || !step_block || !state) return fail(DCV_EINVAL, "adam_step_multi_guarded: bad arguments");
-    for (int t = 0; t < n_tensors; ++t)
-        if (!p[t] || !g[t] || !m[t] || !v[t] || numel[t] < 0) return fail(DCV_EINVAL, "adam_step_multi_guarded: null tensor");
+    if (const int rc = adam_tensors_ok("adam_step_multi_guarded", n_tensors, p, g, m, v, numel)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     AdamStepBlock* b = reinterpret_cast<AdamStepBlock*>(step_block);
     hipLaunchKernelGGL(guard_adam_prepare_kernel, dim3(1), dim3(1), 0, s, b, state, lr, beta1, beta2, eps, weight_decay);
     DCV_LAUNCH_CHECK();
-    for (int t0 = 0; t0 < n_tensors; t0 += ADAM_MT) {
-        AdamPack k;
-        memset(&k, 0, sizeof(k));
-        const int nt = std::min(ADAM_MT, n_tensors - t0);
-        int blocks = 0;
-        for (int t = 0; t < nt; ++t) {
-            k.p[t] = p[t0 + t]; k.g[t] = g[t0 + t]; k.m[t] = m[t0 + t]; k.v[t] = v[t0 + t]; k.n[t] = numel[t0 + t];
-            k.first_block[t] = blocks;
-            blocks += (int)((numel[t0 + t] + 4095) / 4096);
-        }
-        k.first_block[nt] = blocks;
-        if (blocks == 0) continue;
-        hipLaunchKernelGGL(adam_multi_guarded_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, b);
-        DCV_LAUNCH_CHECK();
-    }
-    return DCV_OK;
+    return mt_for_tables<AdamPack>(n_tensors, [&](int i) { return mt_blocks(numel[i]); }, adam_fill(p, g, m, v, numel),
+        [&](const AdamPack& k, int nt, int blocks, int64_t) {
+            hipLaunchKernelGGL(adam_multi_guarded_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, b);
+            DCV_LAUNCH_CHECK();
+            return DCV_OK;
+        });
 }
 
 int dcv_ema_update_multi(int n_tensors, float* const* ema, const float* const* src, const int64_t* numel, const int32_t* mode,
                          double decay, int warmup, int32_t* ema_block, const float* guard_state, void* stream) {
     if (n_tensors < 0 || (n_tensors > 0 && (!ema || !src || !numel || !mode)) || !(decay >= 0.0 && decay < 1.0) || !ema_block)
         return fail(DCV_EINVAL, "ema_update_multi: bad arguments");
-    for (int t0 = 0; t0 < n_tensors; t0 += ADAM_MT) {      // every check before any launch
-        int64_t blocks = 0;
-        for (int t = t0; t < std::min(n_tensors, t0 + ADAM_MT); ++t) {
-            if (numel[t] < 0 || (numel[t] > 0 && (!ema[t] || !src[t]))) return fail(DCV_EINVAL, "ema_update_multi: null tensor or negative numel");
-            if (mode[t] != 0 && mode[t] != 1) return fail(DCV_EINVAL, "ema_update_multi: mode must be 0 (average) or 1 (copy)");
-            blocks += (numel[t] + 4095) / 4096;
-        }
-        if (blocks > INT32_MAX) return fail(DCV_EINVAL, "ema_update_multi: too many elements");
+    for (int t = 0; t < n_tensors; ++t) {      // every check before any launch
+        if (numel[t] < 0 || (numel[t] > 0 && (!ema[t] || !src[t]))) return fail(DCV_EINVAL, "ema_update_multi: null tensor or negative numel");
+        if (mode[t] != 0 && mode[t] != 1) return fail(DCV_EINVAL, "ema_update_multi: mode must be 0 (average) or 1 (copy)");
     }
+    if (!mt_tables_fit(n_tensors, numel)) return fail(DCV_EINVAL, "ema_update_multi: too many elements");
     hipStream_t s = static_cast<hipStream_t>(stream);
     EmaBlock* b = reinterpret_cast<EmaBlock*>(ema_block);
     hipLaunchKernelGGL(ema_prepare_kernel, dim3(1), dim3(1), 0, s, b, guard_state, decay, warmup ? 1 : 0);
     DCV_LAUNCH_CHECK();
-    for (int t0 = 0; t0 < n_tensors; t0 += ADAM_MT) {
-        EmaPack k;
-        memset(&k, 0, sizeof(k));
-        const int nt = std::min(ADAM_MT, n_tensors - t0);
-        int blocks = 0;
-        for (int t = 0; t < nt; ++t) {
-            k.e[t] = ema[t0 + t]; k.s[t] = src[t0 + t]; k.n[t] = numel[t0 + t];
-            if (mode[t0 + t]) k.copy_mask |= 1u << t;
-            k.first_block[t] = blocks;
-            blocks += (int)((numel[t0 + t] + 4095) / 4096);
-        }
-        k.first_block[nt] = blocks;
-        if (blocks == 0) continue;
-        hipLaunchKernelGGL(ema_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, b);
-        DCV_LAUNCH_CHECK();
-    }
-    return DCV_OK;
+    return mt_for_tables<EmaPack>(n_tensors, [&](int i) { return mt_blocks(numel[i]); },
+        [&](EmaPack& k, int t, int i) {
+            k.e[t] = ema[i]; k.s[t] = src[i]; k.tab.n[t] = numel[i];
+            if (mode[i]) k.copy_mask |= 1u << t;
+        },
+        [&](const EmaPack& k, int nt, int blocks, int64_t) {
+            hipLaunchKernelGGL(ema_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, b);
+            DCV_LAUNCH_CHECK();
+            return DCV_OK;
+        });
 }
 
 // workspace: 256 bytes (the skip flag), then every tensor's part (sn_ws_doubles)
@@ -2175,18 +2141,14 @@ size_t dcv_spectral_workspace_bytes(int n_tensors, const int32_t* rows, const in
     return sn_workspace_bytes(n_tensors, rows, cols);
 }
 
-// the table of tensors t0 .. t0 + nt - 1; `which` picks the block count per tensor: 0 column chunks, 1 row chunks, 2 blocks of 4096 elements
-static int sn_fill(SnPack& k, int t0, int nt, const int32_t* rows, const int32_t* cols, const int64_t* ws_off, int which) {
-    int64_t blocks = 0;
-    for (int t = 0; t < nt; ++t) {
-        const int M = rows[t0 + t], K = cols[t0 + t];
-        k.rows[t] = M; k.cols[t] = K; k.ws_off[t] = ws_off[t0 + t];
-        k.first_block[t] = (int32_t)blocks;
-        blocks += which == 0 ? sn_kchunks(K) : which == 1 ? sn_mchunks(M) : sn_eblocks(M, K);
-    }
-    k.first_block[nt] = (int32_t)blocks;      // (<= 24 * 2^30 / 4 elements per block ... / 4096: far below 2^31)
-    return (int)blocks;
+// every tensor's offset into the workspace, in doubles
+static std::vector<int64_t> sn_ws_offsets(int n, const int32_t* rows, const int32_t* cols) {
+    std::vector<int64_t> off(std::max(n, 1));
+    int64_t d = 0;
+    for (int t = 0; t < n; ++t) { off[t] = d; d += sn_ws_doubles(rows[t], cols[t]); }
+    return off;
 }
+static void sn_slot_shape(SnPack& k, int t, int M, int K, int64_t ws_off) { k.rows[t] = M; k.cols[t] = K; k.tab.n[t] = (int64_t)M * K; k.ws_off[t] = ws_off; }
 
 int dcv_spectral_update_multi(int n_tensors, const float* const* w, float* const* w_sn, float* const* u, float* const* v, float* const* sigma,
                               const int32_t* rows, const int32_t* cols, int n_iter, double eps, const float* guard_state, void* ws, size_t ws_bytes, void* stream) {
@@ -2203,32 +2165,29 @@ int dcv_spectral_update_multi(int n_tensors, const float* const* w, float* const
         hipLaunchKernelGGL(sn_prepare_kernel, dim3(1), dim3(1), 0, s, skip, guard_state);
         DCV_LAUNCH_CHECK();
     }
-    std::vector<int64_t> off(std::max(n_tensors, 1));
-    int64_t d = 0;
-    for (int t = 0; t < n_tensors; ++t) { off[t] = d; d += sn_ws_doubles(rows[t], cols[t]); }
-    for (int t0 = 0; t0 < n_tensors; t0 += ADAM_MT) {
-        SnPack k;
-        memset(&k, 0, sizeof(k));
-        const int nt = std::min(ADAM_MT, n_tensors - t0);
-        for (int t = 0; t < nt; ++t) { k.w[t] = w[t0 + t]; k.w_sn[t] = w_sn[t0 + t]; k.u[t] = u[t0 + t]; k.v[t] = v[t0 + t]; k.sigma[t] = sigma[t0 + t]; }
-        for (int it = 0; it < n_iter; ++it) {
-            int blocks = sn_fill(k, t0, nt, rows, cols, off.data(), 0);
-            hipLaunchKernelGGL(sn_cols_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, it > 0 ? 1 : 0, eps, wsd, skip);
-            DCV_LAUNCH_CHECK();
-            blocks = sn_fill(k, t0, nt, rows, cols, off.data(), 1);
-            hipLaunchKernelGGL(sn_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, 1, eps, wsd, skip);
-            DCV_LAUNCH_CHECK();
-        }
-        if (n_iter == 0) {      // sigma of the stored u, v
-            const int blocks = sn_fill(k, t0, nt, rows, cols, off.data(), 1);
-            hipLaunchKernelGGL(sn_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, 0, eps, wsd, skip);
-            DCV_LAUNCH_CHECK();
-        }
-        const int blocks = sn_fill(k, t0, nt, rows, cols, off.data(), 2);
-        hipLaunchKernelGGL(sn_scale_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, n_iter > 0 ? 1 : 0, eps, wsd, skip);
-        DCV_LAUNCH_CHECK();
+    const std::vector<int64_t> off = sn_ws_offsets(n_tensors, rows, cols);
+    // One kernel over every table, then the next kernel (a tensor's kernels still follow each other on the stream; tensors do not depend on each other).
+    auto stage = [&](auto kernel, auto blocks_of, int from_prev) {
+        return mt_for_tables<SnPack>(n_tensors, [&](int i) { return blocks_of(rows[i], cols[i]); },
+            [&](SnPack& k, int t, int i) {
+                k.w[t] = w[i]; k.w_sn[t] = w_sn[i]; k.u[t] = u[i]; k.v[t] = v[i]; k.sigma[t] = sigma[i];
+                sn_slot_shape(k, t, rows[i], cols[i], off[i]);
+            },
+            [&](const SnPack& k, int nt, int blocks, int64_t) {
+                hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, from_prev, eps, wsd, skip);
+                DCV_LAUNCH_CHECK();
+                return DCV_OK;
+            });
+    };
+    const auto kchunks = [](int, int K) { return (int64_t)sn_kchunks(K); };
+    const auto mchunks = [](int M, int) { return (int64_t)sn_mchunks(M); };
+    for (int it = 0; it < n_iter; ++it) {
+        if (const int rc = stage(sn_cols_kernel, kchunks, it > 0 ? 1 : 0)) return rc;
+        if (const int rc = stage(sn_rows_kernel, mchunks, 1)) return rc;
     }
-    return DCV_OK;
+    if (n_iter == 0)      // sigma of the stored u, v
+        if (const int rc = stage(sn_rows_kernel, mchunks, 0)) return rc;
+    return stage(sn_scale_kernel, sn_eblocks, n_iter > 0 ? 1 : 0);
 }
 
 int dcv_spectral_project_multi(int n_tensors, float* const* g, const float* const* w_sn, const float* const* u, const float* const* v, const float* const* sigma,
@@ -2240,24 +2199,20 @@ int dcv_spectral_project_multi(int n_tensors, float* const* g, const float* cons
     if (sn_workspace_bytes(n_tensors, rows, cols) > ws_bytes) return fail(DCV_EWORKSPACE, "spectral_project_multi: workspace too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
     double* wsd = reinterpret_cast<double*>(static_cast<char*>(ws) + 256);
-    std::vector<int64_t> off(std::max(n_tensors, 1));
-    int64_t d = 0;
-    for (int t = 0; t < n_tensors; ++t) { off[t] = d; d += sn_ws_doubles(rows[t], cols[t]); }
-    for (int t0 = 0; t0 < n_tensors; t0 += ADAM_MT) {
-        SnPack k;
-        memset(&k, 0, sizeof(k));
-        const int nt = std::min(ADAM_MT, n_tensors - t0);
-        for (int t = 0; t < nt; ++t) {
-            k.g[t] = g[t0 + t]; k.w_sn[t] = const_cast<float*>(w_sn[t0 + t]); k.u[t] = const_cast<float*>(u[t0 + t]); k.v[t] = const_cast<float*>(v[t0 + t]);
-            k.sigma[t] = const_cast<float*>(sigma[t0 + t]);
-        }
-        const int blocks = sn_fill(k, t0, nt, rows, cols, off.data(), 2);
-        hipLaunchKernelGGL(sn_inner_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, wsd);
-        DCV_LAUNCH_CHECK();
-        hipLaunchKernelGGL(sn_project_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, eps, wsd);
-        DCV_LAUNCH_CHECK();
-    }
-    return DCV_OK;
+    const std::vector<int64_t> off = sn_ws_offsets(n_tensors, rows, cols);
+    return mt_for_tables<SnPack>(n_tensors, [&](int i) { return sn_eblocks(rows[i], cols[i]); },
+        [&](SnPack& k, int t, int i) {
+            k.g[t] = g[i]; k.w_sn[t] = const_cast<float*>(w_sn[i]); k.u[t] = const_cast<float*>(u[i]); k.v[t] = const_cast<float*>(v[i]);
+            k.sigma[t] = const_cast<float*>(sigma[i]);
+            sn_slot_shape(k, t, rows[i], cols[i], off[i]);
+        },
+        [&](const SnPack& k, int nt, int blocks, int64_t) {
+            hipLaunchKernelGGL(sn_inner_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, wsd);
+            DCV_LAUNCH_CHECK();
+            hipLaunchKernelGGL(sn_project_kernel, dim3((unsigned)blocks), dim3(256), 0, s, k, nt, eps, wsd);
+            DCV_LAUNCH_CHECK();
+            return DCV_OK;
+        });
 }
 
 int dcv_decode_video(const void* in, int in_is_u8, int B, int T, int H, int W, int Cc, float div, float sub, float* out, void* stream) {

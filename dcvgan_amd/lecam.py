@@ -20,7 +20,7 @@ from torch.autograd import Function
 from . import loss as Lm
 from . import native as N
 from . import ops
-from .native import NativeError, check, lib, ptr, stream_ptr
+from .native import NativeError, c_array, check, lib, ptr, stream_ptr
 
 STATE_WORDS = 8                                        # anchor_real (fp32 bits), anchor_fake (fp32 bits), updates, active, 4 reserved
 ANCHOR_REAL, ANCHOR_FAKE, UPDATES, ACTIVE = range(4)   # include/dcvgan_hip.h: DCV_LECAM_*
@@ -43,10 +43,6 @@ def _require_logits(t, what: str):
     N._require(t, what)        # a HIP device tensor, float32 (a 16-bit tensor is refused), on the current device
     if not 1 <= t.numel() <= MAX_N:
         raise NativeError(f"{what}: 1 to 2^24 logits, got {t.numel()}")
-
-
-def _table(ts, ctype=C.c_void_p):
-    return (ctype * len(ts))(*[t.data_ptr() if isinstance(t, torch.Tensor) else t for t in ts])
 
 
 class _DisLosses(Function):
@@ -136,8 +132,8 @@ class LeCam:
                 _require_logits(t, f"LeCam: {what} of discriminator {k}")
                 if not t.is_contiguous() or (like is not None and t.numel() != like.numel()) or (what == "loss" and t.numel() != 1):
                     raise NativeError(f"LeCam: {what} of discriminator {k}: expected a contiguous tensor of matching size, got {tuple(t.shape)}")
-        yr, yf = _table(y_reals), _table(y_fakes)
-        nr, nf = _table([t.numel() for t in y_reals], C.c_int64), _table([t.numel() for t in y_fakes], C.c_int64)
+        yr, yf = c_array(y_reals), c_array(y_fakes)
+        nr, nf = c_array([t.numel() for t in y_reals], C.c_int64), c_array([t.numel() for t in y_fakes], C.c_int64)
         reg = torch.empty(n, dtype=torch.float32, device=self.state.device)
         L, s = lib(), stream_ptr()
         check(L.dcv_lecam_sums(n, yr, yf, nr, nf, ptr(self.sums), s), "dcv_lecam_sums")
@@ -146,7 +142,7 @@ class LeCam:
             dist.all_reduce(self.sums, op=dist.ReduceOp.SUM, group=self.pg)
             self.collectives += 1
         check(L.dcv_lecam_apply(n, yr, yf, nr, nf, ptr(self.sums), ptr(self.state), self.decay, self.start, self.weight, int(self.one_sided),
-                                _table(losses), _table(dy_reals), _table(dy_fakes), ptr(reg), s), "dcv_lecam_apply")
+                                c_array(losses), c_array(dy_reals), c_array(dy_fakes), ptr(reg), s), "dcv_lecam_apply")
         self.reg = reg
         self.calls += 1
 

@@ -300,6 +300,28 @@ def ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def c_array(xs, ctype=C.c_void_p):
+    """One argument column of a multi-tensor call as a ctypes array: tensors give their ``data_ptr()``, ints themselves.  An empty column becomes one zeroed
+    slot (ctypes hands a zero-length array over as a dangling pointer; with a count of 0 nobody reads the slot)."""
+    vals = [x.data_ptr() if isinstance(x, torch.Tensor) else x for x in xs]
+    return (ctype * max(len(vals), 1))(*vals)
+
+
+class PointerTable:
+    """The argument arrays of a multi-tensor call as named fields, valid for as long as ``key`` — the ``data_ptr()``s they were built from — stays the same."""
+
+    def __init__(self, key, **fields):
+        self.key = key
+        self.__dict__.update(fields)
+
+    @staticmethod
+    def cached(old: Optional["PointerTable"], key, build) -> "PointerTable":
+        """``old`` itself while it was built from ``key`` (no ctypes array is rebuilt in the steady state), else a new table of the fields ``build()`` returns."""
+        if old is not None and old.key == key:
+            return old
+        return PointerTable(key, **build())
+
+
 def stream_ptr():
     if not torch.cuda.is_available():
         raise NativeError("no HIP device: the DCVGAN kernels run on the GPU only (there is no CPU fallback)")

@@ -27,7 +27,7 @@ from typing import Iterable, List, Optional
 
 import torch
 
-from .native import NativeError, _require, check, lib, ptr, stream_ptr
+from .native import NativeError, PointerTable, _require, c_array, check, lib, ptr, stream_ptr
 
 
 class GradGuard:
@@ -110,16 +110,13 @@ class GradGuard:
                 _require(g, "GradGuard gradient")
                 g = g.contiguous()
                 gs.append(g.data_ptr()); ns.append(g.numel()); keep.append(g)
-        key = (tuple(gs), tuple(ns))
-        if self._tables is None or self._tables[0] != key:
-            n = len(gs)
-            self._tables = (key, (C.c_void_p * max(n, 1))(*gs), (C.c_int64 * max(n, 1))(*ns), n)
-        _, garr, narr, n = self._tables
+        tab = self._tables = PointerTable.cached(self._tables, (tuple(gs), tuple(ns)),
+                                                 lambda: dict(n=len(gs), g=c_array(gs), numel=c_array(ns, C.c_int64)))
         L = lib()
-        need = L.dcv_grad_guard_workspace_bytes(sum(ns), n)
+        need = L.dcv_grad_guard_workspace_bytes(sum(ns), tab.n)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=state.device)
-        check(L.dcv_grad_guard_measure(n, garr, narr, scales.pop(), self.max_norm if self.max_norm is not None else 0.0, int(self.skip_nonfinite), int(self.dynamic),
+        check(L.dcv_grad_guard_measure(tab.n, tab.g, tab.numel, scales.pop(), self.max_norm if self.max_norm is not None else 0.0, int(self.skip_nonfinite), int(self.dynamic),
                                        self.growth_factor, self.backoff_factor, self.growth_interval, ptr(state), ptr(self._ws), self._ws.numel(), stream_ptr()),
               "dcv_grad_guard_measure")
         self.measurements += 1
@@ -172,9 +169,7 @@ class Adam:
             grp[0].append(p.data.data_ptr()); grp[1].append(g.data_ptr()); grp[2].append(s["exp_avg"].data_ptr()); grp[3].append(s["exp_avg_sq"].data_ptr())
             grp[4].append(p.numel()); grp[5].append(g)
         for block, (ps, gs, ms, vs, ns, _) in groups.items():
-            n = len(ps)
-            arr = lambda xs: (C.c_void_p * n)(*xs)
-            check(L.dcv_adam_step_multi_guarded(n, arr(ps), arr(gs), arr(ms), arr(vs), (C.c_int64 * n)(*ns), self.lr, self.betas[0], self.betas[1],
+            check(L.dcv_adam_step_multi_guarded(len(ps), c_array(ps), c_array(gs), c_array(ms), c_array(vs), c_array(ns, C.c_int64), self.lr, self.betas[0], self.betas[1],
                                                 self.eps, self.weight_decay, C.c_void_p(block), ptr(guard.state), st), "dcv_adam_step_multi_guarded")
         if touched:
             torch.autograd.graph.increment_version(touched)
@@ -209,10 +204,8 @@ class Adam:
                 continue
             ps.append(p.data.data_ptr()); gs.append(g.data_ptr()); ms.append(s["exp_avg"].data_ptr()); vs.append(s["exp_avg_sq"].data_ptr())
             ns.append(p.numel()); keep.append(g)
-        n = len(ps)
-        if n:
-            arr = lambda xs: (C.c_void_p * n)(*xs)
-            check(L.dcv_adam_step_multi(n, arr(ps), arr(gs), arr(ms), arr(vs), (C.c_int64 * n)(*ns), self.lr, self.betas[0], self.betas[1],
+        if ps:
+            check(L.dcv_adam_step_multi(len(ps), c_array(ps), c_array(gs), c_array(ms), c_array(vs), c_array(ns, C.c_int64), self.lr, self.betas[0], self.betas[1],
                                         self.eps, self.weight_decay, step, self.grad_scale, st), "dcv_adam_step_multi")
         if touched:
             # the kernels wrote through raw pointers: tell autograd (and the packed-weight caches keyed on it) that
@@ -279,12 +272,13 @@ class ModelEma:
     def module(self, name: str) -> torch.nn.Module:
         return self.twins[name]
 
-    def _table(self, name: str):
+    def _table(self, name: str) -> PointerTable:
+        key = tuple(t.data_ptr() for pair in self._pairs[name] for t in pair)
+        tab = self._tables[name] = PointerTable.cached(self._tables.get(name), key, lambda: self._build_table(name))
+        return tab
+
+    def _build_table(self, name: str) -> dict:
         pairs = self._pairs[name]
-        key = tuple(t.data_ptr() for pair in pairs for t in pair)
-        tab = self._tables.get(name)
-        if tab is not None and tab[0] == key:
-            return tab
         es, ss, ns, ms = [], [], [], []
         for i, (e, s) in enumerate(pairs):
             what = f"ModelEma({name}) " + ("parameter" if i < self._n_params[name] else "buffer")
@@ -308,10 +302,7 @@ class ModelEma:
             if dwords == 0:
                 continue
             es.append(e.data_ptr()); ss.append(s.data_ptr()); ns.append(dwords); ms.append(mode)
-        n = len(es)
-        tab = self._tables[name] = (key, n, (C.c_void_p * max(n, 1))(*es), (C.c_void_p * max(n, 1))(*ss), (C.c_int64 * max(n, 1))(*ns), (C.c_int32 * max(n, 1))(*ms),
-                                    [e for e, _ in pairs])
-        return tab
+        return dict(n=len(es), ema=c_array(es), src=c_array(ss), numel=c_array(ns, C.c_int64), mode=c_array(ms, C.c_int32), touched=[e for e, _ in pairs])
 
     @torch.no_grad()
     def update(self):
@@ -319,10 +310,10 @@ class ModelEma:
         state = ptr(self.guard._need_state()) if self.guard is not None else None
         L = lib()
         st = stream_ptr()
-        for name, (_, n, es, ss, ns, ms, touched) in zip(self.names, tabs):
-            check(L.dcv_ema_update_multi(n, es, ss, ns, ms, self.decay, int(self.warmup), ptr(self._blocks[name]), state, st), "dcv_ema_update_multi")
+        for name, t in zip(self.names, tabs):
+            check(L.dcv_ema_update_multi(t.n, t.ema, t.src, t.numel, t.mode, self.decay, int(self.warmup), ptr(self._blocks[name]), state, st), "dcv_ema_update_multi")
             # the kernels wrote through raw pointers: the twin's packed-weight caches are keyed on the version counter, as in Adam.step (harmless after a skipped update)
-            torch.autograd.graph.increment_version(touched)
+            torch.autograd.graph.increment_version(t.touched)
 
     def num_updates(self) -> int:
         """Updates applied so far (a host read of the device count: on request only)."""
@@ -826,11 +817,12 @@ class SpectralNorm:
                 c._non_persistent_buffers_set.discard(k)
         self.convs = []
 
-    def _table(self):
+    def _table(self) -> PointerTable:
         ts = [(c.weight, c.__dict__["_dcv_spectral"].w_sn, c.weight_u, c.weight_v, c.weight_sigma) for c in self.convs]
-        key = tuple(t.data_ptr() for row in ts for t in row)
-        if self._tables is not None and self._tables[0] == key:
-            return self._tables
+        self._tables = PointerTable.cached(self._tables, tuple(t.data_ptr() for row in ts for t in row), lambda: self._build_table(ts))
+        return self._tables
+
+    def _build_table(self, ts) -> dict:
         for i, row in enumerate(ts):
             for t in row:
                 _require(t.data, f"SpectralNorm tensor of convolution {i}")
@@ -840,25 +832,24 @@ class SpectralNorm:
             if w_sn.shape != w.shape or u.numel() != w.shape[0] or v.numel() != w[0].numel() or sg.numel() != 1:
                 raise NativeError(f"SpectralNorm: the buffers of convolution {i} do not fit its weight {tuple(w.shape)}")
         n = len(ts)
-        col = lambda j: (C.c_void_p * n)(*[row[j].data_ptr() for row in ts])
-        rows, cols = (C.c_int32 * n)(*[row[0].shape[0] for row in ts]), (C.c_int32 * n)(*[row[0][0].numel() for row in ts])
+        w, w_sn, u, v, sigma = (c_array(col) for col in zip(*ts))
+        rows, cols = c_array([row[0].shape[0] for row in ts], C.c_int32), c_array([row[0][0].numel() for row in ts], C.c_int32)
         need = lib().dcv_spectral_workspace_bytes(n, rows, cols)
         if need == 0:
             raise NativeError("dcv_spectral_workspace_bytes: " + lib().dcv_last_error().decode(errors="replace"))
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=ts[0][0].device)
-        self._tables = (key, n, col(0), col(1), col(2), col(3), col(4), rows, cols, [row[1] for row in ts])
-        return self._tables
+        return dict(n=n, w=w, w_sn=w_sn, u=u, v=v, sigma=sigma, rows=rows, cols=cols, touched=[row[1] for row in ts])
 
     @torch.no_grad()
     def update(self, n_iter: int = 1, _guarded: bool = True):
         """`n_iter` power iterations from the stored u, v, then sigma and W / sigma, for every marked convolution; records each weight's version."""
-        _, n, w, w_sn, u, v, sg, rows, cols, touched = self._table()      # every refusal before the first launch
+        t = self._table()      # every refusal before the first launch
         state = ptr(self.guard._need_state()) if (self.guard is not None and _guarded) else None
-        check(lib().dcv_spectral_update_multi(n, w, w_sn, u, v, sg, rows, cols, int(n_iter), self.eps, state, ptr(self._ws), self._ws.numel(), stream_ptr()),
-              "dcv_spectral_update_multi")
+        check(lib().dcv_spectral_update_multi(t.n, t.w, t.w_sn, t.u, t.v, t.sigma, t.rows, t.cols, int(n_iter), self.eps, state, ptr(self._ws), self._ws.numel(),
+                                              stream_ptr()), "dcv_spectral_update_multi")
         # the kernels wrote through raw pointers: the packed-weight caches of W / sigma are keyed on its version counter (harmless after a skipped update)
-        torch.autograd.graph.increment_version(touched)
+        torch.autograd.graph.increment_version(t.touched)
         for c in self.convs:
             c.__dict__["_dcv_spectral"].version = c.weight._version
 
@@ -872,7 +863,7 @@ class SpectralNorm:
         W / sigma since zero_grad.  Once per optimiser step, before the guard measures."""
         for w in list(self._dp) + (list(self.guard._dp) if self.guard is not None else []):
             w.reduce_gradients()      # data parallel: never write a slice a collective is still reading, and project the SUM over the ranks (linear)
-        key, n, _, w_sn, u, v, sg, rows, cols, _ = self._table()
+        t = self._table()
         idx, gs = [], []
         for i, c in enumerate(self.convs):
             g = c.weight.grad
@@ -884,11 +875,9 @@ class SpectralNorm:
             idx.append(i); gs.append(g.data_ptr())
         if not idx:
             return
-        m = len(idx)
-        pick = lambda arr, ty: (ty * m)(*[arr[i] for i in idx])
-        check(lib().dcv_spectral_project_multi(m, (C.c_void_p * m)(*gs), pick(w_sn, C.c_void_p), pick(u, C.c_void_p), pick(v, C.c_void_p), pick(sg, C.c_void_p),
-                                               pick(rows, C.c_int32), pick(cols, C.c_int32), self.eps, ptr(self._ws), self._ws.numel(), stream_ptr()),
-              "dcv_spectral_project_multi")
+        pick = lambda arr, ty=C.c_void_p: c_array([arr[i] for i in idx], ty)
+        check(lib().dcv_spectral_project_multi(len(idx), c_array(gs), pick(t.w_sn), pick(t.u), pick(t.v), pick(t.sigma), pick(t.rows, C.c_int32),
+                                               pick(t.cols, C.c_int32), self.eps, ptr(self._ws), self._ws.numel(), stream_ptr()), "dcv_spectral_project_multi")
 
     def state_dict(self):
         """u, v, sigma per marked convolution in marking order (they are also buffers of the modules, so a model checkpoint already carries them) and eps."""

@@ -21,11 +21,9 @@ def _decay(t, decay=0.999, warmup=True):
 
 
 def _update(es, ss, modes, decay, warmup, block, state=None):
-    from dcvgan_amd.native import check, lib, ptr, stream_ptr
-    n = len(es)
-    arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
-    dwords = (C.c_int64 * n)(*[e.numel() * (e.element_size() // 4) for e in es])
-    check(lib().dcv_ema_update_multi(n, arr(es), arr(ss), dwords, (C.c_int32 * n)(*modes), decay, int(warmup), ptr(block), ptr(state), stream_ptr()), "dcv_ema_update_multi")
+    from dcvgan_amd.native import c_array as arr, check, lib, ptr, stream_ptr
+    dwords = arr([e.numel() * (e.element_size() // 4) for e in es], C.c_int64)
+    check(lib().dcv_ema_update_multi(len(es), arr(es), arr(ss), dwords, arr(modes, C.c_int32), decay, int(warmup), ptr(block), ptr(state), stream_ptr()), "dcv_ema_update_multi")
 
 
 def _block():

@@ -35,12 +35,13 @@ def project_launches(n):
 
 # ---- raw calls -------------------------------------------------------------------------------------------------------------------------------------------
 def _arr(ts):
-    return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+    from dcvgan_amd.native import c_array
+    return c_array(ts)
 
 
 def _shape_arrays(ws):
-    n = len(ws)
-    return (C.c_int32 * n)(*[w.shape[0] for w in ws]), (C.c_int32 * n)(*[w.shape[1] for w in ws])
+    from dcvgan_amd.native import c_array
+    return c_array([w.shape[0] for w in ws], C.c_int32), c_array([w.shape[1] for w in ws], C.c_int32)
 
 
 def _workspace(ws):
