@@ -10,11 +10,14 @@ caller's, handed over as a callable; everything after it is this module's:
   written),
 * ``manifold_metrics``: improved precision / recall and density / coverage (``dcv_eval_row_norms``, ``dcv_eval_knn_radii``, ``dcv_eval_manifold_counts``,
   ``dcv_eval_manifold_reduce``; the n x n distance matrices are never written), with ``manifold_host`` as its numpy mirror,
+* ``prd_metrics``: PRD, the reference's third metric (R runs of k-means over the union of the two feature sets — ``dcv_eval_prd_seed``,
+  ``dcv_eval_prd_assign``, ``dcv_eval_prd_update``, ``dcv_eval_prd_count`` — then the precision-recall curve of the cluster histograms in host numpy), with
+  ``prd_host`` as its numpy mirror,
 * ``frechet_distance``: the O(D^3) eigenvalue step on the host in numpy — it runs once per evaluation and produces a number for the host's logger anyway,
 * ``Evaluator``: generator -> extractor -> statistics without a clip or a feature crossing PCIe.
 
 Every accumulation has one fixed order and no floating-point atomic: the same sequence of calls gives the same bits.  ``draw_host`` is an integer-exact numpy mirror
-of the subset draw, as ``clipstore.permute_host`` is of the epoch shuffle: the specification the kernel is tested against.  PRD (its k-means) is not attempted.
+of the subset draw, as ``clipstore.permute_host`` is of the epoch shuffle: the specification the kernel is tested against.
 """
 from __future__ import annotations
 
@@ -31,16 +34,18 @@ MAX_DIM = 4096                       # features per row (D) and classes per row 
 MAX_SUBSETS, MAX_SUBSET_SIZE = 4096, 65536
 KID_SALT = 0x9FB21C651E98DF25        # DCV_EVAL_KID_SALT: the draw's Philox key is the seed plus this constant
 _M64 = 0xFFFFFFFFFFFFFFFF
-METRICS = ("is", "fid", "kid", "pr", "dc")
+METRICS = ("is", "fid", "kid", "pr", "dc", "prcurve")
 DEFAULT_METRICS = ("is", "fid", "kid")
 MAX_K, MAX_COL_SPLITS = 16, 64        # neighbours and column shares of the k-nearest-neighbour metrics: the kernels' limits
+PRD_SALT = 0xC2B2AE3D27D4EB4F        # DCV_EVAL_PRD_SALT: the seeding's Philox key is the seed plus this constant
+PRD_MAX_CLUSTERS, PRD_MAX_RUNS, PRD_MAX_ITERS, PRD_MAX_ROW_SPLITS = 64, 64, 1000, 64      # PRD's k-means: the kernels' limits, and the Lloyd iterations of one call
 
 _STATS = {"launches": 0}
 
 
 def launches() -> int:
-    """Kernel launches this module has issued so far, in this process (dcv_eval_inception_update, dcv_eval_kid_sums, dcv_eval_knn_radii and
-    dcv_eval_manifold_counts are two each, every other entry one)."""
+    """Kernel launches this module has issued so far, in this process (dcv_eval_inception_update, dcv_eval_kid_sums, dcv_eval_knn_radii, dcv_eval_manifold_counts
+    and dcv_eval_prd_assign are two each, dcv_eval_prd_update is three, every other entry one)."""
     return _STATS["launches"]
 
 
@@ -568,12 +573,312 @@ def manifold_host(a, b, k: int) -> dict:
 
 
 # --------------------------------------------------------------------------- #
+# PRD: k-means over the union of the two feature sets, and the precision-recall curve
+# --------------------------------------------------------------------------- #
+def _prd_int(v, lo: int, hi: int, name: str, what: str) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError(f"{what}: {lo} <= {name} <= {hi}, got {v!r}")
+    return int(v)
+
+
+def _prd_seed_value(seed, what: str) -> int:
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise ValueError(f"{what}: the seed is an integer, got {seed!r}")
+    return int(seed)
+
+
+def _prd_sides(real, fake, what: str):
+    na, D, sa = _rows(real, None, f"{what}: real features")
+    nb, _, sb = _rows(fake, D, f"{what}: fake features")
+    if na + nb >= 2 ** 31:
+        raise NativeError(f"{what}: the union must have fewer than 2^31 rows, got {na} + {nb}")
+    if fake.device != real.device:
+        raise NativeError(f"{what}: the two sides are on {real.device} and {fake.device}")
+    return na, nb, D, sa, sb
+
+
+def _prd_table(t, shape, dtype, device, what: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        got = f"{t.dtype}{tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise NativeError(f"{what}: expected a contiguous {tuple(shape)} {dtype} tensor on {device}, got {got}")
+    return t
+
+
+def _prd_cent(cent, D: int, n: int, device, what: str) -> Tuple[int, int]:
+    if not isinstance(cent, torch.Tensor) or cent.dim() != 3:
+        got = tuple(cent.shape) if isinstance(cent, torch.Tensor) else type(cent).__name__
+        raise NativeError(f"{what}: the centroids are a (R, C, {D}) float64 device tensor, got {got}")
+    R, C = int(cent.shape[0]), int(cent.shape[1])
+    if not 1 <= R <= PRD_MAX_RUNS or not 1 <= C <= PRD_MAX_CLUSTERS or C > n:
+        raise NativeError(f"{what}: 1 <= R <= {PRD_MAX_RUNS} runs and 1 <= C <= min({PRD_MAX_CLUSTERS}, n = {n}) clusters, got centroids {tuple(cent.shape)}")
+    _prd_table(cent, (R, C, D), torch.float64, device, f"{what}: centroids")
+    return R, C
+
+
+def _prd_norms(real, fake, norms_a, norms_b, na: int, nb: int, what: str):
+    if norms_a is not None:      # what the caller hands over is checked before a missing side is launched
+        _vector(norms_a, na, torch.float64, f"{what}: norms_a")
+    if norms_b is not None:
+        _vector(norms_b, nb, torch.float64, f"{what}: norms_b")
+    return row_norms(real) if norms_a is None else norms_a, row_norms(fake) if norms_b is None else norms_b
+
+
+def _keyed_perm_host(x: np.ndarray, n_rows: int, e0, e1, k0: int, k1: int) -> np.ndarray:
+    """perm(x) on [0, n_rows) for uint64 arrays x, e0 (and a scalar e1): the bijection ``draw_host`` walks, the counter's last two words given."""
+    h = clipstore.half_bits(n_rows)
+    mask = np.uint64((1 << h) - 1)
+    x = np.array(x, dtype=np.uint64)
+    e0 = np.broadcast_to(np.asarray(e0, dtype=np.uint64), x.shape)
+    todo = np.ones(x.shape, dtype=bool)
+    while todo.any():      # cycle walking: only the values still outside [0, n_rows) go round again
+        v = x[todo]
+        L, R = v >> np.uint64(h), v & mask
+        for r in range(clipstore.FEISTEL_ROUNDS):
+            f = clipstore.philox4x32_10(R, r, e0[todo], e1, k0, k1)[0] & mask
+            L, R = R, L ^ f
+        v = (L << np.uint64(h)) | R
+        x[todo] = v
+        todo[todo] = v >= np.uint64(n_rows)
+    return x
+
+
+def prd_seed_host(seed: int, num_runs: int, num_clusters: int, n: int) -> np.ndarray:
+    """The (R, C) int32 union rows dcv_eval_prd_seed starts the centroids from — integers only, the specification of the kernel.  rows[r][c] = perm_r(c): the clip
+    store's keyed bijection on [0, n) (what ``draw_host`` uses) with key = seed + PRD_SALT and the Philox counter {R, round, r, 0}; a run's rows are distinct."""
+    R, C, n = int(num_runs), int(num_clusters), int(n)
+    if not (1 <= R <= PRD_MAX_RUNS and 1 <= C <= PRD_MAX_CLUSTERS and C <= n < 2 ** 31):
+        raise ValueError(f"prd_seed_host: 1 <= R <= {PRD_MAX_RUNS}, 1 <= C <= {PRD_MAX_CLUSTERS}, C <= n < 2^31; got {R}, {C}, {n}")
+    key = (int(seed) + PRD_SALT) & _M64
+    x = np.tile(np.arange(C, dtype=np.uint64), R)
+    runs = np.repeat(np.arange(R, dtype=np.uint64), C)
+    return _keyed_perm_host(x, n, runs, 0, key & 0xFFFFFFFF, key >> 32).reshape(R, C).astype(np.int32)
+
+
+def prd_seed(real: torch.Tensor, fake: torch.Tensor, num_clusters: int = 20, num_runs: int = 10, seed: int = 0) -> torch.Tensor:
+    """The (R, C, D) fp64 device tensor of starting centroids: union row ``prd_seed_host(seed, R, C, n)[r][c]`` as doubles.  One launch."""
+    na, nb, D, sa, sb = _prd_sides(real, fake, "prd_seed")
+    C, R = _prd_int(num_clusters, 1, PRD_MAX_CLUSTERS, "num_clusters", "prd_seed"), _prd_int(num_runs, 1, PRD_MAX_RUNS, "num_runs", "prd_seed")
+    seed = _prd_seed_value(seed, "prd_seed")
+    if C > na + nb:
+        raise NativeError(f"prd_seed: {C} clusters need at least as many rows, got {na} + {nb}")
+    cent = torch.empty((R, C, D), dtype=torch.float64, device=real.device)
+    _call("dcv_eval_prd_seed", 1, ptr(real), sa, na, ptr(fake), sb, nb, D, C, R, seed & _M64, ptr(cent), stream_ptr())
+    return cent
+
+
+def prd_assign(real: torch.Tensor, fake: torch.Tensor, cent: torch.Tensor, norms_a: Optional[torch.Tensor] = None,
+               norms_b: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The (R, n) int32 device tensor ``assign[r][u]``: the LOWEST cluster c of minimal ``cn[r][c] - 2 x_u . cent[r][c]`` among the scores that are not NaN, for
+    union row u (the ``real`` rows, then the ``fake`` rows); C, "unassigned", for a row whose norm is not finite or that has no comparable score.  ``norms_a`` /
+    ``norms_b``: ``row_norms`` of the sides if the caller has them.  Two launches (one more per side without its norms), no host read."""
+    na, nb, D, sa, sb = _prd_sides(real, fake, "prd_assign")
+    R, C = _prd_cent(cent, D, na + nb, real.device, "prd_assign")
+    norms_a, norms_b = _prd_norms(real, fake, norms_a, norms_b, na, nb, "prd_assign")
+    need = int(lib().dcv_eval_prd_assign_workspace_bytes(C, R))
+    ws = N.scratch.get("eval_prd_assign", need, real.device)
+    assign = torch.empty((R, na + nb), dtype=torch.int32, device=real.device)
+    _call("dcv_eval_prd_assign", 2, ptr(real), sa, na, ptr(fake), sb, nb, ptr(norms_a), ptr(norms_b), D, ptr(cent), C, R, ptr(assign), ptr(ws), ws.numel(),
+          stream_ptr())
+    return assign
+
+
+def prd_count(assign: torch.Tensor, norms_a: torch.Tensor, norms_b: torch.Tensor, num_clusters: int) -> torch.Tensor:
+    """The (R, 2, C + 1) int32 device tensor ``hist[r][side][c]``: the side's rows (0 = real) assigned to c; column C: the unassigned rows.  One launch."""
+    C = _prd_int(num_clusters, 1, PRD_MAX_CLUSTERS, "num_clusters", "prd_count")
+    if not isinstance(norms_a, torch.Tensor) or not isinstance(norms_b, torch.Tensor) or norms_a.dim() != 1 or norms_b.dim() != 1:
+        raise NativeError("prd_count: the norms of the two sides are (na,) and (nb,) float64 device tensors")
+    na, nb = int(norms_a.shape[0]), int(norms_b.shape[0])
+    _vector(norms_a, na, torch.float64, "prd_count: norms_a")
+    _vector(norms_b, nb, torch.float64, "prd_count: norms_b")
+    if not isinstance(assign, torch.Tensor) or assign.dim() != 2 or not 1 <= assign.shape[0] <= PRD_MAX_RUNS or na < 1 or nb < 1:
+        raise NativeError(f"prd_count: the assignments are a (R <= {PRD_MAX_RUNS}, na + nb) int32 device tensor")
+    R = int(assign.shape[0])
+    _prd_table(assign, (R, na + nb), torch.int32, norms_a.device, "prd_count: assignments")
+    hist = torch.empty((R, 2, C + 1), dtype=torch.int32, device=assign.device)
+    _call("dcv_eval_prd_count", 1, ptr(assign), ptr(norms_a), na, ptr(norms_b), nb, C, R, ptr(hist), stream_ptr())
+    return hist
+
+
+def prd_update(real: torch.Tensor, fake: torch.Tensor, assign: torch.Tensor, cent: torch.Tensor, row_splits: int = 0, norms_a: Optional[torch.Tensor] = None,
+               norms_b: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One Lloyd update, ``cent`` in place: ``cent[r][c] = (sum of the rows with assign[r][u] == c) / count`` in fp64 where the count is positive; an empty cluster
+    keeps its centroid bit for bit (sklearn relocates it).  -> the (R, 2, C + 1) int32 device tensor ``hist`` of these assignments.  A row whose norm is not finite
+    is left out and counted as unassigned whatever its entry.  ``row_splits``: the slabs the rows are summed in (0: the library chooses from the shapes alone); with
+    integer features the result is the same bits for every value.  Three launches (one more per side without its norms), no host read."""
+    na, nb, D, sa, sb = _prd_sides(real, fake, "prd_update")
+    R, C = _prd_cent(cent, D, na + nb, real.device, "prd_update")
+    _prd_table(assign, (R, na + nb), torch.int32, real.device, "prd_update: assignments")
+    S = _prd_int(row_splits, 0, PRD_MAX_ROW_SPLITS, "row_splits", "prd_update")
+    norms_a, norms_b = _prd_norms(real, fake, norms_a, norms_b, na, nb, "prd_update")
+    need = int(lib().dcv_eval_prd_update_workspace_bytes(na + nb, D, C, R, S))
+    ws = N.scratch.get("eval_prd_update", need, real.device)
+    hist = torch.empty((R, 2, C + 1), dtype=torch.int32, device=real.device)
+    _call("dcv_eval_prd_update", 3, ptr(real), sa, na, ptr(fake), sb, nb, ptr(norms_a), ptr(norms_b), ptr(assign), D, C, R, S, ptr(cent), ptr(hist), ptr(ws),
+          ws.numel(), stream_ptr())
+    return hist
+
+
+def prd_launches(iters: int = 20, with_norms: bool = True) -> int:
+    """The launches of one ``prd_kmeans`` / ``prd_metrics`` call: the two sides' norms (``with_norms``), 1 for the seeding, 2 + 3 per Lloyd iteration (assignment:
+    cn and the sweep; update: counts, slab sums, fold), then the final assignment's 2 and its count's 1 — 106 at the default 20 iterations."""
+    return (2 if with_norms else 0) + 1 + 5 * int(iters) + 3
+
+
+def prd_kmeans(real: torch.Tensor, fake: torch.Tensor, num_clusters: int = 20, num_runs: int = 10, iters: int = 20, seed: int = 0,
+               row_splits: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(hist, cent)`` on the device: ``num_runs`` independent k-means runs of ``num_clusters`` clusters over the union of the ``real`` (na, D) and ``fake`` (nb, D)
+    fp32 device rows.  Seeding (``prd_seed``), then ``iters`` times assignment and update, then a final assignment and count: ``hist`` (R, 2, C + 1) int32 belongs to
+    the final centroids ``cent`` (R, C, D) fp64.  Every iteration is launched (a converged one is a fixed point and changes no bit) and nothing is read back in
+    between: ``prd_launches(iters)`` launches.  Full-batch Lloyd with a fixed number of iterations is this project's choice; the published PRD code runs mini-batch
+    k-means, whose random batches have no fixed order of sums, and sklearn relocates an empty cluster where this one keeps its centroid."""
+    na, nb, D, _, _ = _prd_sides(real, fake, "prd_kmeans")
+    C, R = _prd_int(num_clusters, 1, PRD_MAX_CLUSTERS, "num_clusters", "prd_kmeans"), _prd_int(num_runs, 1, PRD_MAX_RUNS, "num_runs", "prd_kmeans")
+    T, S = _prd_int(iters, 0, PRD_MAX_ITERS, "iters", "prd_kmeans"), _prd_int(row_splits, 0, PRD_MAX_ROW_SPLITS, "row_splits", "prd_kmeans")
+    seed = _prd_seed_value(seed, "prd_kmeans")
+    if C > na + nb:
+        raise NativeError(f"prd_kmeans: {C} clusters need at least as many rows, got {na} + {nb}")
+    norms_a, norms_b = row_norms(real), row_norms(fake)
+    cent = prd_seed(real, fake, C, R, seed)
+    for _ in range(T):
+        assign = prd_assign(real, fake, cent, norms_a, norms_b)
+        prd_update(real, fake, assign, cent, S, norms_a, norms_b)
+    assign = prd_assign(real, fake, cent, norms_a, norms_b)
+    return prd_count(assign, norms_a, norms_b, C), cent
+
+
+def prd_curve(hist, num_angles: int = 1001) -> Tuple[np.ndarray, np.ndarray]:
+    """``(precision, recall)``, two (num_angles,) fp64 arrays: the PRD curve of Sajjadi et al. 2018 from the (R, 2, C + 1) histograms (side 0 = real; column C: the
+    unassigned rows), averaged over the runs.  Per run ``pr = hist[r][0][:C] / sum``, ``pf = hist[r][1][:C] / sum`` (each side normalised on its own: unequal sizes are
+    fine), ``slope = tan(linspace(1e-10, pi / 2 - 1e-10, num_angles))``, ``precision[l] = sum_c min(pr_c slope_l, pf_c)``, ``recall[l] = precision[l] / slope_l``,
+    both clipped to [0, 1].  If any run has an unassigned row, both curves are NaN.  The constants are the published code's as recalled — that code is not at hand, so
+    this function is the specification."""
+    h = np.asarray(hist)
+    if h.ndim != 3 or h.shape[1] != 2 or h.shape[2] < 2 or h.shape[0] < 1 or not np.issubdtype(h.dtype, np.integer) or (h < 0).any():
+        raise ValueError(f"prd_curve: a (R, 2, C + 1) table of counts, got {h.dtype}{h.shape}")
+    num_angles = _prd_int(num_angles, 2, 1 << 20, "num_angles", "prd_curve")
+    if h[:, :, -1].any():
+        nan = np.full(num_angles, np.nan)
+        return nan, nan.copy()
+    h = h[:, :, :-1].astype(np.float64)
+    if (h.sum(axis=2) == 0).any():
+        raise ValueError("prd_curve: a side has no rows")
+    slope = np.tan(np.linspace(1e-10, np.pi / 2 - 1e-10, num_angles))
+    precision, recall = np.zeros(num_angles), np.zeros(num_angles)
+    for r in range(h.shape[0]):
+        pr, pf = h[r, 0] / h[r, 0].sum(), h[r, 1] / h[r, 1].sum()
+        p = np.minimum(pr[None, :] * slope[:, None], pf[None, :]).sum(axis=1)
+        precision += np.clip(p, 0.0, 1.0)
+        recall += np.clip(p / slope, 0.0, 1.0)
+    return precision / h.shape[0], recall / h.shape[0]
+
+
+def prd_f_beta(precision, recall, beta: float = 8) -> float:
+    """``max_l (1 + beta^2) p_l r_l / (beta^2 p_l + r_l + 1e-10)`` over the curve: beta = 8 weighs recall, beta = 1 / 8 precision.  NaN for a NaN curve."""
+    p, r = np.asarray(precision, dtype=np.float64), np.asarray(recall, dtype=np.float64)
+    if p.shape != r.shape or p.ndim != 1 or p.size < 1 or not float(beta) > 0.0:
+        raise ValueError(f"prd_f_beta: two curves of one length and beta > 0, got {p.shape}, {r.shape}, {beta!r}")
+    if np.isnan(p).any() or np.isnan(r).any():
+        return float("nan")
+    b2 = float(beta) ** 2
+    return float(np.max((1.0 + b2) * p * r / (b2 * p + r + 1e-10)))
+
+
+def _prd_scores(hist, num_angles: int = 1001) -> dict:
+    p, r = prd_curve(hist, num_angles)
+    return {"prd_f8": prd_f_beta(p, r, 8), "prd_f1_8": prd_f_beta(p, r, 1.0 / 8.0)}
+
+
+def prd_metrics(real: torch.Tensor, fake: torch.Tensor, num_clusters: int = 20, num_runs: int = 10, iters: int = 20, seed: int = 0, row_splits: int = 0) -> dict:
+    """``{"prd_f8", "prd_f1_8"}`` as Python floats: ``prd_kmeans`` on the device, ONE device-to-host read of its histograms (R x 2 x (C + 1) integers), then
+    ``prd_curve`` and ``prd_f_beta`` in host fp64.  ``prd_f8`` is F_8 (recall-weighted), ``prd_f1_8`` F_1/8 (precision-weighted); both NaN if a feature is not
+    finite.  The cluster and run counts follow the published PRD code; see ``prd_kmeans`` for what differs from it."""
+    hist, _ = prd_kmeans(real, fake, num_clusters, num_runs, iters, seed, row_splits)
+    return _prd_scores(hist.cpu().numpy())
+
+
+def _prd_assign_host(x: np.ndarray, norms: np.ndarray, cent: np.ndarray) -> np.ndarray:
+    """(R, n) int32: the mirror of dcv_eval_prd_assign for fp64 rows x (n, D), their norms and centroids (R, C, D)."""
+    R, C, D = cent.shape
+    out = np.empty((R, x.shape[0]), dtype=np.int32)
+    with np.errstate(all="ignore"):
+        ok = np.isfinite(norms)
+        for r in range(R):
+            cn = _norms_host(cent[r])
+            score = cn[None, :] - 2.0 * (x @ cent[r].T)
+            valid = ~np.isnan(score)
+            masked = np.where(valid, score, np.inf)
+            first = (valid & (masked == masked.min(axis=1, keepdims=True))).argmax(axis=1)      # the lowest index of the minimum among the comparable ones
+            out[r] = np.where(ok & valid.any(axis=1), first, C)
+    return out
+
+
+def _prd_count_host(assign: np.ndarray, norms: np.ndarray, na: int, C: int) -> np.ndarray:
+    R, n = assign.shape
+    hist = np.zeros((R, 2, C + 1), dtype=np.int32)
+    ok = np.isfinite(norms)
+    for r in range(R):
+        slot = np.where(ok & (assign[r] >= 0) & (assign[r] < C), assign[r], C)
+        hist[r, 0] = np.bincount(slot[:na], minlength=C + 1)
+        hist[r, 1] = np.bincount(slot[na:], minlength=C + 1)
+    return hist
+
+
+def _prd_update_host(x: np.ndarray, norms: np.ndarray, na: int, assign: np.ndarray, cent: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """(cent', hist): the mirror of dcv_eval_prd_update; the rows of a cluster are added in ascending order."""
+    R, C, D = cent.shape
+    hist = _prd_count_host(assign, norms, na, C)
+    new = cent.copy()
+    ok = np.isfinite(norms)
+    for r in range(R):
+        for c in range(C):
+            rows = np.flatnonzero(ok & (assign[r] == c))
+            if rows.size:
+                new[r, c] = np.add.accumulate(x[rows], axis=0)[-1] / float(rows.size)      # accumulate: strictly one row after the other
+    return new, hist
+
+
+def prd_host(real, fake, num_clusters: int = 20, num_runs: int = 10, iters: int = 20, seed: int = 0, cent=None) -> dict:
+    """The numpy fp64 mirror of ``prd_metrics`` — the specification the kernels are tested against.  -> ``assign``: the T + 1 assignments (R, n) int32, ``cent``: the
+    T + 1 centroid tensors (R, C, D) (``cent[t]`` is what ``assign[t]`` was formed against: ``cent[0]`` the seeds), ``hist``: the T + 1 histograms (R, 2, C + 1),
+    ``seed_rows`` (R, C), and ``prd_f8`` / ``prd_f1_8`` of the last histogram.  ``cent``: explicit starting centroids instead of the seeding."""
+    a, b = np.asarray(real, dtype=np.float32), np.asarray(fake, dtype=np.float32)
+    if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1] or not 1 <= a.shape[1] <= MAX_DIM or a.shape[0] < 1 or b.shape[0] < 1:
+        raise ValueError(f"prd_host: two (n, D) arrays with 1 <= D <= {MAX_DIM}, got {a.shape} and {b.shape}")
+    C, R = _prd_int(num_clusters, 1, PRD_MAX_CLUSTERS, "num_clusters", "prd_host"), _prd_int(num_runs, 1, PRD_MAX_RUNS, "num_runs", "prd_host")
+    T = _prd_int(iters, 0, PRD_MAX_ITERS, "iters", "prd_host")
+    na, n = a.shape[0], a.shape[0] + b.shape[0]
+    if C > n:
+        raise ValueError(f"prd_host: {C} clusters need at least as many rows, got {n}")
+    x = np.concatenate([a, b]).astype(np.float64)
+    with np.errstate(all="ignore"):
+        norms = _norms_host(x)
+    rows = prd_seed_host(seed, R, C, n)
+    c = x[rows] if cent is None else np.array(cent, dtype=np.float64).reshape(R, C, a.shape[1])
+    assigns, cents, hists = [], [], []
+    for t in range(T + 1):
+        with np.errstate(all="ignore"):
+            assign = _prd_assign_host(x, norms, c)
+            cents.append(c)
+            assigns.append(assign)
+            if t < T:
+                c, hist = _prd_update_host(x, norms, na, assign, c)
+            else:
+                hist = _prd_count_host(assign, norms, na, C)
+            hists.append(hist)
+    out = dict(assign=assigns, cent=cents, hist=hists, seed_rows=rows)
+    out.update(_prd_scores(hists[-1]))
+    return out
+
+
+# --------------------------------------------------------------------------- #
 # generator -> extractor -> statistics
 # --------------------------------------------------------------------------- #
 class Evaluator:
     """``Evaluator(extractor, metrics=("is", "fid", "kid"), max_features=50000)``: the replacement of ``Trainer.evaluate`` (trainer.py:171-224).  ``metrics`` are chosen
-    from ``("is", "fid", "kid", "pr", "dc")``: "pr" adds improved precision and recall (``pr_k`` = 3 neighbours), "dc" density and coverage (``dc_k`` = 5), both
-    over the stored features of the two sides (``manifold_metrics``).
+    from ``("is", "fid", "kid", "pr", "dc", "prcurve")``: "pr" adds improved precision and recall (``pr_k`` = 3 neighbours), "dc" density and coverage (``dc_k`` = 5),
+    both over the stored features of the two sides (``manifold_metrics``).  "prcurve" is the reference's ``"prd"`` (trainer.py:216-219; the name "prd" itself stays
+    refused): ``prd_metrics`` over the stored features with ``prd_clusters`` = 20, ``prd_runs`` = 10, ``prd_iters`` = 20 and the Evaluator's seed, adding
+    ``"prd_f8"`` and ``"prd_f1_8"``.  Like "pr" and "dc" it is not additive across data-parallel ranks: gathering the features is the caller's.
 
     ``extractor(xc)`` takes a (B, 3, T, H, W) fp32 device clip in [-1, 1] and returns ``(features (B, D), logits (B, K) or None)`` on the device — the caller's
     network (the reference's is a Kinetics ResNeXt-101).  ``observe_real(xc)`` feeds real batches (a ``clipstore.ClipSampler``'s ``batch["color"]`` for instance);
@@ -584,7 +889,8 @@ class Evaluator:
     filled by the library's strided copy; rows past the buffer still enter the moments."""
 
     def __init__(self, extractor: Callable, metrics: Sequence[str] = DEFAULT_METRICS, max_features: int = 50000, kid_subsets: int = 100, kid_subset_size: int = 1000,
-                 seed: int = 0, real_moments: Optional[FeatureMoments] = None, pr_k: int = 3, dc_k: int = 5):
+                 seed: int = 0, real_moments: Optional[FeatureMoments] = None, prd_clusters: int = 20, prd_runs: int = 10, prd_iters: int = 20, pr_k: int = 3,
+                 dc_k: int = 5):
         metrics = tuple(metrics)
         unknown = [m for m in metrics if m not in METRICS]
         if unknown or not metrics:
@@ -596,7 +902,9 @@ class Evaluator:
         self.extractor, self.metrics, self.max_features = extractor, metrics, int(max_features)
         self.kid_subsets, self.kid_subset_size, self.seed = int(kid_subsets), int(kid_subset_size), int(seed)
         self.pr_k, self.dc_k = _k(pr_k, "Evaluator: pr_k"), _k(dc_k, "Evaluator: dc_k")
-        self._stores = any(m in metrics for m in ("kid", "pr", "dc"))      # the metrics computed from the stored features of both sides
+        self.prd_clusters = _prd_int(prd_clusters, 1, PRD_MAX_CLUSTERS, "prd_clusters", "Evaluator")
+        self.prd_runs, self.prd_iters = _prd_int(prd_runs, 1, PRD_MAX_RUNS, "prd_runs", "Evaluator"), _prd_int(prd_iters, 0, PRD_MAX_ITERS, "prd_iters", "Evaluator")
+        self._stores = any(m in metrics for m in ("kid", "pr", "dc", "prcurve"))      # the metrics computed from the stored features of both sides
         self.real: Optional[FeatureMoments] = real_moments
         self.real_feats: Optional[torch.Tensor] = None      # (max_features, D) fp32, the first n_real_feats rows filled
         self.n_real_feats = 0
@@ -665,10 +973,16 @@ class Evaluator:
             if name in self.metrics and min(num_samples, self.max_features) < k + 1:
                 raise NativeError(f'Evaluator: "{name}" with k = {k} needs at least {k + 1} generated samples within max_features, got num_samples {num_samples}, '
                                   f'max_features {self.max_features}')
+        if "prcurve" in self.metrics:
+            if self.n_real_feats < 1:
+                raise NativeError('Evaluator: "prcurve" needs real features (observe_real() on at least one clip)')
+            if self.n_real_feats + min(num_samples, self.max_features) < self.prd_clusters:
+                raise NativeError(f'Evaluator: "prcurve" with {self.prd_clusters} clusters needs at least as many rows, got {self.n_real_feats} real features and '
+                                  f'num_samples {num_samples} within max_features {self.max_features}')
 
     def evaluate(self, ggen=None, cgen=None, num_samples: int = 0, batchsize: int = 20) -> dict:
         """Generate ``num_samples`` clips in batches of ``batchsize`` (eval mode, no_grad, the last batch truncated), run the extractor on each batch and accumulate;
-        then finalise.  -> ``{"is": .., "fid": .., "kid": .., "kid_std": .., "precision": .., "recall": .., "density": .., "coverage": ..}`` (the requested ones) as
+        then finalise.  -> ``{"is": .., "fid": .., "kid": .., "kid_std": .., "precision": .., "recall": .., "density": .., "coverage": .., "prd_f8": .., "prd_f1_8": ..}`` (the requested ones) as
         Python floats.  A metric whose inputs are missing is refused
         by name before this module launches anything.  ``ggen`` / ``cgen`` default to the generators trainer.build_evaluator bound."""
         ggen, cgen = ggen if ggen is not None else self.ggen, cgen if cgen is not None else self.cgen
@@ -723,4 +1037,6 @@ class Evaluator:
         wanted = tuple(m for m in ("pr", "dc") if m in self.metrics)
         if wanted:
             out.update(manifold_metrics(self.real_feats[:self.n_real_feats], self.fake_feats[:self.n_fake_feats], self.pr_k, self.dc_k, wanted))
+        if "prcurve" in self.metrics:
+            out.update(prd_metrics(self.real_feats[:self.n_real_feats], self.fake_feats[:self.n_fake_feats], self.prd_clusters, self.prd_runs, self.prd_iters, self.seed))
         return out

@@ -164,6 +164,13 @@ _SIGS = {
     "dcv_eval_manifold_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
     "dcv_eval_manifold_counts": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int, C.c_int, _P, C.c_size_t, _P, _P, _P]),
     "dcv_eval_manifold_reduce": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, _P]),
+    # on-device evaluation: PRD's k-means (added symbols only: the ABI version stays 4)
+    "dcv_eval_prd_seed": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_uint64, _P, _P]),
+    "dcv_eval_prd_assign_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "dcv_eval_prd_assign": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
+    "dcv_eval_prd_count": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, _P, _P]),
+    "dcv_eval_prd_update_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "dcv_eval_prd_update": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     # synchronised BatchNorm for data parallel, fp32 path (added symbols only: the ABI version stays 4)
     "dcv_bn_sync_row_doubles": (C.c_size_t, [C.c_int]),
     "dcv_bn_sync_sums": (C.c_int, [_P, _D, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),

@@ -121,8 +121,8 @@ def build_evaluator(cfg: StepConfig, models, extractor, ema=None, **kw) -> "eval
     """On-device evaluation in place of Trainer.evaluate (trainer.py:171-224): an evaluation.Evaluator bound to the two generators — with `ema`
     (optim.ModelEma, build_ema) to their EMA twins, the weights a GAN is evaluated from — so that ``ev.evaluate(num_samples=..., batchsize=...)`` needs no models.
     `extractor(xc) -> (features, logits or None)` is the caller's feature network; keyword arguments are the Evaluator's (metrics, max_features, kid_subsets,
-    kid_subset_size, seed, real_moments, pr_k, dc_k): ``metrics=("fid", "pr", "dc")`` adds improved precision / recall (pr_k = 3 neighbours) and density / coverage
-    (dc_k = 5) over the stored features.  Feed the real statistics once with ``ev.observe_real(batch["color"])``."""
+    kid_subset_size, seed, real_moments, prd_clusters, prd_runs, prd_iters, pr_k, dc_k): ``metrics=("fid", "pr", "dc")`` adds improved precision / recall
+    (pr_k = 3 neighbours) and density / coverage (dc_k = 5) over the stored features, ``"prcurve"`` the reference's "prd" (DESIGN §18).  Feed the real statistics once with ``ev.observe_real(batch["color"])``."""
     from . import evaluation
     ev = evaluation.Evaluator(extractor, **kw)
     ev.ggen, ev.cgen = (ema.module("ggen"), ema.module("cgen")) if ema is not None else (models["ggen"], models["cgen"])

@@ -583,6 +583,41 @@ int dcv_eval_manifold_counts(const float* queries, int64_t stride_q, int64_t nq,
  * own_rad2: the QUERIES' own radii (coverage compares a real row's nearest fake with the real row's radius); norms: the queries' norms.  One launch, one workgroup. */
 int dcv_eval_manifold_reduce(const int32_t* count, const double* dmin2, const double* own_rad2, const double* norms, int64_t n, double* out, void* stream);
 
+/* ---- on-device evaluation: PRD, the k-means of the precision-recall curve (added symbols only: the ABI version stays 4) ---------------- *
+ * The reference's third metric (trainer.py:216-219: "prd"; Sajjadi et al. 2018) clusters the UNION of the real rows A (na) and the fake rows B (nb) — D fp32 features,
+ * row strides >= D; union row u is a_u for u < na, else b_{u - na}; n = na + nb < 2^31; the union is never copied together — and compares the two sides' cluster
+ * histograms.  R independent runs of C clusters, full-batch Lloyd; the centroids are one (R, C, D) fp64 tensor.  1 <= C <= 64, C <= n, 1 <= R <= 64, 1 <= D <= 4096.
+ * No floating-point atomic: one owner per output element and one order per sum.  Every refusal (DCV_EINVAL, DCV_EWORKSPACE) is returned before the first launch.
+ *
+ * Seeding (trainer.py:216-219): cent[r][c] = union row perm_r(c) as doubles, perm_r = the bijection of dcv_clipstore_draw on [0, n) with key {lo, hi} of
+ * seed + DCV_EVAL_PRD_SALT and the Philox counter {R, round, r, 0}: the run where dcv_eval_kid_draw puts the subset.  A run's rows are distinct.  One launch. */
+#define DCV_EVAL_PRD_SALT 0xC2B2AE3D27D4EB4Full
+int dcv_eval_prd_seed(const float* fa, int64_t stride_a, int64_t na, const float* fb, int64_t stride_b, int64_t nb, int D, int C, int R, uint64_t seed, double* cent,
+                      void* stream);
+/* Assignment (trainer.py:216-219): cn[r][c] = sum_d cent[r][c][d]^2 (features ascending), score(u, r, c) = cn[r][c] - 2 x_u.cent[r][c] in fp64, every operation
+ * rounded on its own; the dot runs through v_mfma_f64_16x16x4_f64 with the contraction over D in dcv_eval_knn_radii's order (fp32 features converted on load, fp64
+ * centroids as they are; one 16-byte read of the features feeding four MFMAs where D, the strides and the bases allow it, guarded single reads otherwise).
+ *   assign[r][u] (int32, (R, n)) = the LOWEST c of minimal score among the scores that are not NaN; C ("unassigned") where the row's norm (dcv_eval_row_norms of its
+ *   side) is not finite or no score is comparable.
+ * A workgroup owns 64 union rows and sweeps the runs — 4, 2 or 1 of them per 64-column tile for C <= 16, 32, 64 —: the rows are fetched once for all R runs.  Two launches (cn, the sweep); workspace of
+ * at least dcv_eval_prd_assign_workspace_bytes(C, R) = R * C * 8 (0: out of range). */
+size_t dcv_eval_prd_assign_workspace_bytes(int C, int R);
+int dcv_eval_prd_assign(const float* fa, int64_t stride_a, int64_t na, const float* fb, int64_t stride_b, int64_t nb, const double* norms_a, const double* norms_b, int D,
+                        const double* cent, int C, int R, int32_t* assign, void* workspace, size_t workspace_bytes, void* stream);
+/* Counts (trainer.py:216-219): hist[r][side][c] (int32, (R, 2, C + 1); side 0 = real) = the side's rows with assign[r][u] == c; column C counts every other row, and
+ * every row whose norm is not finite whatever its entry.  One launch. */
+int dcv_eval_prd_count(const int32_t* assign, const double* norms_a, int64_t na, const double* norms_b, int64_t nb, int C, int R, int32_t* hist, void* stream);
+/* Update (trainer.py:216-219): hist as dcv_eval_prd_count writes it; sum[r][c][d] = the fp64 sum of x_u[d] over the rows counted in hist[r][.][c]; then
+ * cent[r][c][d] = sum / count (one division) where count > 0 — an empty cluster keeps its centroid bit for bit.  The sums are a GEMM with the contraction over the
+ * union's rows on v_mfma_f64_16x16x4_f64, the A operand the selector assign[r][u] == c (a product of 0 / 1 and an fp32 value is exact); the rows are cut into S slabs
+ * of ceil(n / S) rows rounded up to 16, a slab's rows added ascending (four per instruction) into the workspace and the slabs ascending by the last launch.
+ * row_splits = 0: S = max(1, min(64, ceil(n / 64), 1024 / (ceil(R C / 64) * ceil(D / 64)))), from the shapes alone; 1 .. 64 forces S.  With integer features every
+ * sum is exact and the result is the same bits for every S.  Three launches (counts, slab sums, fold); workspace of at least
+ * dcv_eval_prd_update_workspace_bytes(n, D, C, R, row_splits) = S * R * C * D * 8 (0: out of range). */
+size_t dcv_eval_prd_update_workspace_bytes(int64_t n, int D, int C, int R, int row_splits);
+int dcv_eval_prd_update(const float* fa, int64_t stride_a, int64_t na, const float* fb, int64_t stride_b, int64_t nb, const double* norms_a, const double* norms_b,
+                        const int32_t* assign, int D, int C, int R, int row_splits, double* cent, int32_t* hist, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- bf16 channels-last ("CL16") data path -------------------------------------------------- *
  * BASELINE.json configs[2] ("surreal-depth1, bf16 MFMA") and configs[4] ("fp16 MFMA") name 16-bit variants of the same step
  * (config/surreal-depth1.yml:5,47-76, config/isogd-flow.yml; the reference itself is fp32-only).  This is that path as a DATA path:
