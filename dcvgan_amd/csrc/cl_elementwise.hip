@@ -18,6 +18,7 @@
 #include <algorithm>
 
 namespace dcv {
+extern thread_local char g_last_kernel[160];   // dcv_debug_last_kernel's text (conv_mfma.hip)
 #ifdef DCV_CL_FP16
 inline namespace clf16 {
 #endif
@@ -619,6 +620,11 @@ static int cl_bn_setup(const dcv_dims5* xd, ClBnArgs* a, int* blocks, const char
     *blocks = (int)std::min<int64_t>(std::max<int64_t>(nb, 1), 1024);
     return DCV_OK;
 }
+// the note for dcv_debug_last_kernel: which statistics source ran, the block shape, and cl_bn_block_out's combine scheme (its own condition)
+static void cl_bn_note(const char* pass, const ClBnArgs& a, int blocks) {
+    const bool xor_tree = (a.G & (a.G - 1)) == 0 && a.G <= 64;
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "%s: G %d, pb %d, blocks %d, %s combine", pass, a.G, a.pb, blocks, xor_tree ? "xor" : "serial");
+}
 
 static int cl_bn_forward(const void* x, const dcv_dims5* xd, void* y, const dcv_dims5* yd, const float* gamma, const float* beta,
                          float* running_mean, float* running_var, int64_t* num_batches_tracked, float* save_mean, float* save_invstd,
@@ -663,15 +669,18 @@ static int cl_bn_forward(const void* x, const dcv_dims5* xd, void* y, const dcv_
     if (training && stat) {
         hipLaunchKernelGGL(cl_bn_finalize_stat_kernel, dim3((unsigned)a.C), dim3(256), 0, st, stat, nparts, pitch, a.C, (double)a.P, eps, momentum, running_mean, running_var,
                            num_batches_tracked, save_mean, save_invstd, gamma, beta, coef, coef + a.C);
+        snprintf(g_last_kernel, sizeof(g_last_kernel), "cl_bn_finalize_stat_kernel (%d partials, pitch %d) + cl_bn_apply_kernel: G %d, pb %d", nparts, pitch, a.G, a.pb);
     } else if (training) {
         hipLaunchKernelGGL(cl_bn_stats_kernel, dim3((unsigned)blocks), dim3(256), (size_t)4 * a.C * 2 * sizeof(double), st, a);
         DCV_LAUNCH_CHECK();
         hipLaunchKernelGGL(cl_bn_finalize_kernel, dim3((unsigned)a.C), dim3(256), 0, st, partial, blocks, a.C, (double)a.P, eps, momentum, running_mean, running_var,
                            num_batches_tracked, save_mean, save_invstd, gamma, beta, coef, coef + a.C);
+        cl_bn_note("cl_bn_stats_kernel + cl_bn_finalize_kernel + cl_bn_apply_kernel", a, blocks);
     } else {
         if (!running_mean || !running_var) return fail(DCV_EINVAL, "cl_bn_act_forward: eval mode needs running statistics");
         hipLaunchKernelGGL(cl_bn_coeff_kernel, dim3((unsigned)cb), dim3(64), 0, st, a.C, gamma, beta, (const float*)nullptr, (const float*)nullptr, running_mean, running_var, eps,
                            coef, coef + a.C, save_mean, save_invstd);
+        snprintf(g_last_kernel, sizeof(g_last_kernel), "cl_bn_coeff_kernel (running statistics) + cl_bn_apply_kernel: G %d, pb %d", a.G, a.pb);
     }
     DCV_LAUNCH_CHECK();
     const int64_t total = a.P * a.G;
@@ -706,6 +715,7 @@ int dcv_cl_bn_act_backward(const void* dy, const dcv_dims5* dyd, const void* x, 
                        dgamma, dbeta, k1, k2, k3);
     DCV_LAUNCH_CHECK();
     a.c1 = k1; a.c2 = k2; a.c3 = k3;
+    cl_bn_note("cl_bn_bwd_reduce_kernel + cl_bn_bwd_finalize_kernel + cl_bn_bwd_apply_kernel", a, blocks);
     const int64_t total = a.P * a.G;
     hipLaunchKernelGGL(cl_bn_bwd_apply_kernel, dim3((unsigned)std::min<int64_t>(std::max<int64_t>((a.P + (int64_t)a.pb * 4 - 1) / ((int64_t)a.pb * 4), 1), 8192)), dim3(256), 0, st, a, total);
     DCV_LAUNCH_CHECK();

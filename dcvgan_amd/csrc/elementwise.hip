@@ -137,12 +137,18 @@ static bool ew_rows_off() {
     return off;
 }
 
+// which kernel launch_ew takes for this map (the same conditions, for the BatchNorm entries' dcv_debug_last_kernel notes)
+static bool ew_rows_ok(const RowMap& m) {
+    return m.vec == 4 && m.inner != 1 && m.gpr % 256 == 0 && m.groups / m.gpr < (1ll << 31) && !ew_rows_off();
+}
+static const char* ew_name(const RowMap& m) { return m.groups == 0 ? "none" : ew_rows_ok(m) ? "ew_rows" : m.vec == 4 ? "ew<4>" : "ew<1>"; }
+
 template <class F>
 static int launch_ew(const RowMap& m, const F& f, hipStream_t s) {
     if (m.groups >= (1ll << 32)) return fail(DCV_EUNSUPPORTED, "elementwise: tensor too large");
     if (m.groups == 0) return DCV_OK;
     const int64_t rows = m.groups / m.gpr;
-    if (m.vec == 4 && m.inner != 1 && m.gpr % 256 == 0 && rows < (1ll << 31) && !ew_rows_off())
+    if (ew_rows_ok(m))
         hipLaunchKernelGGL((ew_rows_kernel<F>), dim3((unsigned)rows), dim3(256), 0, s, m, f);
     else if (m.vec == 4) hipLaunchKernelGGL((ew_kernel<4, F>), dim3(grid_for(m.groups)), dim3(256), 0, s, m, f);
     else hipLaunchKernelGGL((ew_kernel<1, F>), dim3(grid_for(m.groups)), dim3(256), 0, s, m, f);
@@ -1777,6 +1783,7 @@ int dcv_bn_act_forward(const float* x, const dcv_dims5* xd, float* y, const dcv_
             hipLaunchKernelGGL(bn_fwd_small_kernel, dim3(C), dim3(SMALL_NT), 0, s, cm, x, rv(*xd), y, rv(*yd), gamma, beta, running_mean, running_var, num_batches_tracked,
                                save_mean, save_invstd, mask, cnt, eps, momentum, act, slope);
             DCV_LAUNCH_CHECK();
+            snprintf(g_last_kernel, sizeof(g_last_kernel), "bn_fwd_small_kernel (%lld groups per channel, one launch)", (long long)cm.per_chan);
             return DCV_OK;
         }
         double* partial = static_cast<double*>(ws);
@@ -1786,10 +1793,12 @@ int dcv_bn_act_forward(const float* x, const dcv_dims5* xd, float* y, const dcv_
         const double count = (double)xd->n * xd->d * xd->h * xd->w;
         hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, s, partial, C, cm.split, count, eps, momentum, save_mean, save_invstd, running_mean, running_var, num_batches_tracked);
         DCV_LAUNCH_CHECK();
+        snprintf(g_last_kernel, sizeof(g_last_kernel), "bn_stats_kernel<%d> x %d blocks per channel + bn_finalize_kernel + BnApply %s", m.vec, cm.split, ew_name(m));
     } else {
         if (!running_mean || !running_var) return fail(DCV_EINVAL, "bn_act_forward: eval mode needs running stats");
         hipLaunchKernelGGL(bn_eval_stats_kernel, dim3((C + 255) / 256), dim3(256), 0, s, C, eps, running_mean, running_var, save_mean, save_invstd);
         DCV_LAUNCH_CHECK();
+        snprintf(g_last_kernel, sizeof(g_last_kernel), "bn_eval_stats_kernel + BnApply %s", ew_name(m));
     }
     BnApply f{x, y, rv(*xd), rv(*yd), gamma, beta, save_mean, save_invstd, mask, act, slope};
     return launch_ew(m, f, s);
@@ -1815,12 +1824,14 @@ int dcv_bn_act_forward_stats(const float* x, const dcv_dims5* xd, float* y, cons
             hipLaunchKernelGGL(bn_fwd_small_kernel, dim3(C), dim3(SMALL_NT), 0, s, cm, x, rv(*xd), y, rv(*yd), gamma, beta, running_mean, running_var, num_batches_tracked,
                                save_mean, save_invstd, mask, count, eps, momentum, act, slope);
             DCV_LAUNCH_CHECK();
+            snprintf(g_last_kernel, sizeof(g_last_kernel), "bn_fwd_small_kernel (%lld groups per channel, one launch; the %d partials are not read)", (long long)cm.per_chan, nparts);
             return DCV_OK;
         }
     }
     hipLaunchKernelGGL(bn_partials_finalize_kernel, dim3(C), dim3(256), 0, s, stat, nparts, pitch, count, eps, momentum, save_mean, save_invstd, running_mean, running_var,
                        num_batches_tracked);
     DCV_LAUNCH_CHECK();
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "bn_partials_finalize_kernel (%d partials, pitch %d) + BnApply %s", nparts, pitch, ew_name(m));
     BnApply f{x, y, rv(*xd), rv(*yd), gamma, beta, save_mean, save_invstd, mask, act, slope};
     return launch_ew(m, f, s);
 }
@@ -1834,6 +1845,7 @@ int dcv_bn_forward_stats_only(const float* x, const dcv_dims5* xd, float* runnin
     hipLaunchKernelGGL(bn_partials_finalize_kernel, dim3(xd->c), dim3(256), 0, static_cast<hipStream_t>(stream), stat, nparts, pitch, count, eps, momentum, save_mean, save_invstd,
                        running_mean, running_var, num_batches_tracked);
     DCV_LAUNCH_CHECK();
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "bn_partials_finalize_kernel (%d partials, pitch %d), statistics only", nparts, pitch);
     return DCV_OK;
 }
 
@@ -1845,6 +1857,7 @@ int dcv_bn_apply(const float* x, const dcv_dims5* xd, float* y, const dcv_dims5*
     const void* ptrs[2] = {x, y};
     RowMap m = make_rowmap(*xd, views, 2, ptrs);
     if (m.groups >= (1ll << 32)) return fail(DCV_EUNSUPPORTED, "bn: tensor too large");
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "BnApply %s (saved statistics)", ew_name(m));
     BnApply f{x, y, rv(*xd), rv(*yd), gamma, beta, save_mean, save_invstd, mask, act, slope};
     return launch_ew(m, f, static_cast<hipStream_t>(stream));
 }
@@ -1867,11 +1880,13 @@ int dcv_bn_act_backward(const float* dy, const dcv_dims5* dyd, const float* x, c
         hipLaunchKernelGGL(bn_bwd_small_kernel, dim3(C), dim3(SMALL_NT), 0, s, cm, dy, rv(*dyd), x, rv(*xd), dx, rv(*dxd), gamma, beta, save_mean, save_invstd, mask,
                            cnt, act, slope, training, dgamma, dbeta);
         DCV_LAUNCH_CHECK();
+        snprintf(g_last_kernel, sizeof(g_last_kernel), "bn_bwd_small_kernel (%lld groups per channel, one launch)", (long long)cm.per_chan);
         return DCV_OK;
     }
     double* partial = static_cast<double*>(ws);
     float* coef = reinterpret_cast<float*>(static_cast<char*>(ws) + (size_t)(2048 + C) * 2 * sizeof(double) * 2);
-    if (m.vec == 4 && m.inner != 1 && m.gpr % 256 == 0 && !ew_rows_off())
+    const bool rows_kernel = m.vec == 4 && m.inner != 1 && m.gpr % 256 == 0 && !ew_rows_off();
+    if (rows_kernel)
         hipLaunchKernelGGL(bn_bwd_reduce_rows_kernel, dim3(C * cm.split), dim3(256), 0, s, cm, dy, rv(*dyd), x, rv(*xd), gamma, beta, save_mean, save_invstd, mask, act, slope, partial);
     else if (m.vec == 4)
         hipLaunchKernelGGL((bn_bwd_reduce_kernel<4>), dim3(C * cm.split), dim3(256), 0, s, cm, dy, rv(*dyd), x, rv(*xd), gamma, beta, save_mean, save_invstd, mask, act, slope, partial);
@@ -1881,6 +1896,8 @@ int dcv_bn_act_backward(const float* dy, const dcv_dims5* dyd, const float* x, c
     const double count = (double)xd->n * xd->d * xd->h * xd->w;
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, s, partial, C, cm.split, count, dgamma, dbeta, coef);
     DCV_LAUNCH_CHECK();
+    if (rows_kernel) snprintf(g_last_kernel, sizeof(g_last_kernel), "bn_bwd_reduce_rows_kernel x %d blocks per channel + bn_bwd_finalize_kernel + BnBwdApply %s", cm.split, ew_name(m));
+    else snprintf(g_last_kernel, sizeof(g_last_kernel), "bn_bwd_reduce_kernel<%d> x %d blocks per channel + bn_bwd_finalize_kernel + BnBwdApply %s", m.vec, cm.split, ew_name(m));
     BnBwdApply f{dy, x, dx, rv(*dyd), rv(*xd), rv(*dxd), gamma, beta, save_mean, save_invstd, mask, coef, act, slope, training};
     return launch_ew(m, f, s);
 }
