@@ -1711,7 +1711,7 @@ int dcv_act_forward(const float* x, const dcv_dims5* xd, float* y, const dcv_dim
 }
 
 int dcv_act_backward(const float* dy, const dcv_dims5* dyd, const float* y, const dcv_dims5* yd, float* dx, const dcv_dims5* dxd, int act, float slope, void* stream) {
-    if (!dy || !y || !dx || !same_shape(*dyd, *yd) || !same_shape(*dyd, *dxd)) return fail(DCV_EINVAL, "act_backward: bad arguments");
+    if (!dy || !y || !dx || !dyd || !yd || !dxd || !same_shape(*dyd, *yd) || !same_shape(*dyd, *dxd)) return fail(DCV_EINVAL, "act_backward: bad arguments");
     const dcv_dims5* views[3] = {dyd, yd, dxd};
     const void* ptrs[3] = {dy, y, dx};
     RowMap m = make_rowmap(*dyd, views, 3, ptrs);
@@ -1729,7 +1729,7 @@ int dcv_axpby(const float* x, const dcv_dims5* xd, float a, const float* z, cons
 }
 
 int dcv_noise_add(const float* x, const dcv_dims5* xd, float* y, const dcv_dims5* yd, float sigma, uint64_t seed, uint64_t offset, void* stream) {
-    if (!x || !y || !same_shape(*xd, *yd)) return fail(DCV_EINVAL, "noise_add: bad arguments");
+    if (!x || !y || !xd || !yd || !same_shape(*xd, *yd)) return fail(DCV_EINVAL, "noise_add: bad arguments");
     const dcv_dims5* views[2] = {xd, yd};
     const void* ptrs[2] = {x, y};
     RowMap m = make_rowmap(*xd, views, 2, ptrs);
@@ -2331,7 +2331,7 @@ int dcv_gru_forward(const float* e, const float* h0, const float* w_ih, const fl
 int dcv_gru_backward(const float* dout, const float* e, const float* h0, const float* out, const float* gates, const float* w_ih, const float* w_hh,
                      float* dw_ih, float* dw_hh, float* db_ih, float* db_hh, int T, int B, int dm, void* ws, size_t ws_bytes, void* stream) {
     (void)w_ih;
-    if (!dout || !e || !h0 || !out || !gates || !w_hh || !dw_ih || !dw_hh || !db_ih || !db_hh || dm > GRU_MAXD) return fail(DCV_EINVAL, "gru_backward: bad arguments");
+    if (!dout || !e || !h0 || !out || !gates || !w_hh || !dw_ih || !dw_hh || !db_ih || !db_hh || T < 1 || B < 1 || dm < 1 || dm > GRU_MAXD) return fail(DCV_EINVAL, "gru_backward: bad arguments");
     if (!ws || ws_bytes < dcv_gru_workspace_bytes(B, dm)) return fail(DCV_EWORKSPACE, "gru_backward: workspace too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
     float* part = static_cast<float*>(ws);
