@@ -171,6 +171,11 @@ _SIGS = {
     "dcv_eval_prd_count": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, _P, _P]),
     "dcv_eval_prd_update_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
     "dcv_eval_prd_update": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    # RunState: pack / unpack / digest of the state tensors (added symbols only: the ABI version stays 4)
+    "dcv_state_workspace_bytes": (C.c_size_t, [C.c_int, _P]),
+    "dcv_state_pack_multi": (C.c_int, [C.c_int, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_size_t, _P]),
+    "dcv_state_unpack_multi": (C.c_int, [C.c_int, _P, _P, _P, C.c_int64, _P, _P]),
+    "dcv_state_digest_multi": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
     # synchronised BatchNorm for data parallel, fp32 path (added symbols only: the ABI version stays 4)
     "dcv_bn_sync_row_doubles": (C.c_size_t, [C.c_int]),
     "dcv_bn_sync_sums": (C.c_int, [_P, _D, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),

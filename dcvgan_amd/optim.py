@@ -92,6 +92,29 @@ class GradGuard:
         s = self._need_state()
         return {k: s[self.FIELDS.index(k)] for k in ("grad_norm", "clip_coef", "skipped", "skipped_total", "loss_scale", "nonfinite")}
 
+    RULE = ("max_norm", "skip_nonfinite", "dynamic", "init_scale", "growth_factor", "backoff_factor", "growth_interval")
+
+    def state_dict(self):
+        """The eight device floats (a host read: on request only; None while no optimiser with device parameters is registered), the number of measurements and
+        the rule's constants."""
+        sd = {k: getattr(self, k) for k in self.RULE}
+        sd.update(state=None if self.state is None else self.state.detach().cpu().clone(), measurements=self.measurements)
+        return sd
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        st = sd["state"]
+        if st is not None:
+            if self.state is None:
+                raise NativeError("GradGuard.load_state_dict: the checkpoint carries device state, but no optimiser with HIP device parameters is registered")
+            if st.dtype != torch.float32 or st.numel() != len(self.FIELDS):
+                raise ValueError(f"GradGuard.load_state_dict: the state is {len(self.FIELDS)} float32 values, the checkpoint holds {st.dtype} x {st.numel()}")
+            self.state.copy_(st.reshape(-1))      # (host -> device: a copy, no kernel)
+        self.max_norm = None if sd["max_norm"] is None else float(sd["max_norm"])
+        self.skip_nonfinite, self.dynamic, self.init_scale = bool(sd["skip_nonfinite"]), bool(sd["dynamic"]), float(sd["init_scale"])
+        self.growth_factor, self.backoff_factor, self.growth_interval = float(sd["growth_factor"]), float(sd["backoff_factor"]), int(sd["growth_interval"])
+        self.measurements = int(sd["measurements"])
+
     @torch.no_grad()
     def measure(self):
         state = self._need_state()
@@ -141,6 +164,58 @@ class Adam:
                 p.grad = None
             elif p.grad is not None:
                 p.grad.zero_()
+
+    def state_dict(self):
+        """torch.optim.Adam's layout — ``{"state": {index: {"step", "exp_avg", "exp_avg_sq"}}, "param_groups": [one group]}``, ``step`` a 0-d float32 host tensor —
+        so that a ``torch.optim.Adam`` over the same parameters loads it, and this class loads torch's.  The moments are clones on the parameters' device.  Under a
+        guard the step counts are read from the device blocks (a host read: on request only)."""
+        state = {}
+        for i, p in enumerate(self.params):
+            s = self.state.get(p)
+            if s is None:
+                continue
+            step = int(s["step"].item()) if isinstance(s["step"], torch.Tensor) else int(s["step"])
+            state[i] = {"step": torch.tensor(float(step), dtype=torch.float32), "exp_avg": s["exp_avg"].detach().clone(), "exp_avg_sq": s["exp_avg_sq"].detach().clone()}
+        group = {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay, "amsgrad": False, "maximize": False, "foreach": None,
+                 "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": False, "params": list(range(len(self.params)))}
+        return {"state": state, "param_groups": [group]}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        """The inverse, also of ``torch.optim.Adam.state_dict()``: one parameter group over the same parameters in the same order, no amsgrad, no maximize.  State
+        of parameters the checkpoint does not list is dropped.  Under a guard, parameters with the same step count share one device step block.  Every refusal
+        comes before anything is changed."""
+        groups = sd["param_groups"]
+        if len(groups) != 1 or list(groups[0]["params"]) != list(range(len(self.params))):
+            raise ValueError(f"Adam.load_state_dict: expected one parameter group over {len(self.params)} parameters, got "
+                             f"{[len(g['params']) for g in groups]}")
+        g = groups[0]
+        if g.get("amsgrad") or g.get("maximize") or g.get("decoupled_weight_decay"):
+            raise ValueError("Adam.load_state_dict: amsgrad / maximize / decoupled weight decay checkpoints have no counterpart here")
+        new = {}
+        for i, st in sd["state"].items():
+            i = int(i)
+            if not 0 <= i < len(self.params):
+                raise ValueError(f"Adam.load_state_dict: state of parameter {i} of {len(self.params)}")
+            p = self.params[i]
+            for k in ("exp_avg", "exp_avg_sq"):
+                if tuple(st[k].shape) != tuple(p.shape):
+                    raise ValueError(f"Adam.load_state_dict: {k} of parameter {i} is {tuple(st[k].shape)}, the parameter {tuple(p.shape)}")
+            step = float(st["step"])
+            if step != int(step) or step < 0:
+                raise ValueError(f"Adam.load_state_dict: step {step!r} of parameter {i}")
+            new[i] = (int(step), st["exp_avg"], st["exp_avg_sq"])
+        self.lr, self.betas, self.eps, self.weight_decay = float(g["lr"]), (float(g["betas"][0]), float(g["betas"][1])), float(g["eps"]), float(g["weight_decay"])
+        self.state = {}
+        blocks = {}
+        for i, (step, m, v) in new.items():
+            p = self.params[i]
+            s = self.state[p] = {"step": step, "exp_avg": torch.empty_like(p.data).copy_(m), "exp_avg_sq": torch.empty_like(p.data).copy_(v)}
+            if self.guard is not None:      # (host tensor -> device copy: no kernel)
+                key = (step, p.device)
+                if key not in blocks:
+                    blocks[key] = torch.tensor([step] + [0] * 15, dtype=torch.int32).to(p.device)
+                s["step_block"], s["step"] = blocks[key], blocks[key][0]
 
     def _step_guarded(self):
         """The step under a GradGuard: the step count lives on the device (a skipped step must not advance it, and the host does not know), one 64-byte step block
@@ -612,6 +687,12 @@ class DataParallelAdam:
 
     def reduce_gradients(self):
         self.bucket.reduce()
+
+    def state_dict(self):
+        return self.inner.state_dict()
+
+    def load_state_dict(self, sd):
+        self.inner.load_state_dict(sd)
 
     def step(self):
         self.bucket.reduce()

@@ -30,6 +30,20 @@ class PhiloxRng:
         self._counter += 1
         return seed & 0xFFFFFFFFFFFFFFFF, self._counter
 
+    def state_dict(self):
+        """The stream's whole state: the constructor's seed, the seed of the last draw and the number of draws made on it (host values: nothing is read back)."""
+        return dict(fixed_seed=self._fixed_seed, seed_seen=self._seed_seen, counter=self._counter)
+
+    def load_state_dict(self, sd):
+        """Takes the three fields as they are.  A stream without a fixed seed follows ``torch.initial_seed()``: if that differs from ``seed_seen`` at the next draw,
+        the draw starts a new stream at counter 0 (``_next``) — a caller who resumes under another torch seed pins the stream first (runstate.RunState does)."""
+        counter = int(sd["counter"])
+        if counter < 0:
+            raise ValueError(f"PhiloxRng: counter {counter} < 0")
+        self._fixed_seed = None if sd["fixed_seed"] is None else int(sd["fixed_seed"])
+        self._seed_seen = None if sd["seed_seen"] is None else int(sd["seed_seen"])
+        self._counter = counter
+
     def normal(self, shape: Sequence[int], device) -> torch.Tensor:
         seed, off = self._next()
         return ops.normal(shape, device, seed, off)

@@ -129,6 +129,17 @@ def build_evaluator(cfg: StepConfig, models, extractor, ema=None, **kw) -> "eval
     return ev
 
 
+def build_run_state(cfg: StepConfig, models, optimizers, runner=None, ema=None, spectral=None, augment=None, lecam=None, sampler=None, rngs=(), extra=None,
+                    slots: int = 2) -> "runstate.RunState":
+    """Everything the run has become, as one object (runstate.RunState): ``capture()`` packs the models, Adam moments, guard, EMA twins, augmentation
+    and LeCam state into a device arena on the current stream and copies the host scalars; the snapshot restores in memory (rollback) or through one file (resume in
+    fresh objects, bit for bit); ``fingerprint()`` digests the live state without a copy.  Hand over the same objects StepRunner got; ``rngs`` are random streams
+    of the caller's own, ``extra`` a dict of the caller's plain values (the generator behind ``t_rand`` belongs there).  The iteration itself is untouched."""
+    from . import runstate
+    return runstate.RunState(models, optimizers, runner=runner, ema=ema, spectral=spectral, augment=augment, lecam=lecam, sampler=sampler, rngs=rngs, extra=extra,
+                             slots=slots)
+
+
 class StepRunner:
     """`elide_dead_backward=True` builds the D-phase fakes without a tape (they are detached): the
     reference backpropagates `loss_dis` through cgen/ggen too (trainer.py:304-319, fakes not detached)

@@ -618,6 +618,25 @@ size_t dcv_eval_prd_update_workspace_bytes(int64_t n, int D, int C, int R, int r
 int dcv_eval_prd_update(const float* fa, int64_t stride_a, int64_t na, const float* fb, int64_t stride_b, int64_t nb, const double* norms_a, const double* norms_b,
                         const int32_t* assign, int D, int C, int R, int row_splits, double* cent, int32_t* hist, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- RunState: snapshot, fingerprint and restore of a run's state tensors (added symbols only: the ABI version stays 4) ---- *
+ * Every tensor is handled as 32-bit words ("dwords": an fp32 or int32 element is one, an int64 element two), 0 <= dwords < 2^32 per tensor, on a 4-byte
+ * boundary; a tensor without dwords is skipped (its digest is (0, 0)) and may be null.  Up to 24 tensors per launch (the multi-tensor table of DESIGN §10a), any
+ * number per call; every check comes before the first launch.
+ * The digest of w[0 .. n): with z = i * 0x9E3779B97F4A7C15 + w[i] (mod 2^64) and h_i = the splitmix64 finaliser of z (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9;
+ * z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31), the pair (sum of h_i mod 2^64, xor of h_i): exact and independent of the traversal.  `digests` is
+ * n_tensors x 2 uint64 in device memory.  Per-block partial pairs go through `workspace`, at least dcv_state_workspace_bytes(n_tensors, dwords) bytes on an 8-byte
+ * boundary (0: a size out of range), and one block per tensor folds them: two launches per table of 24 (one for a table without dwords).
+ * dcv_state_pack_multi: tensor t's dwords -> arena[offsets[t] ..), the dwords up to the next multiple of 4 written as zero, and the digests in the same pass.  The
+ * arena is on a 16-byte boundary; offsets are multiples of 4 dwords, ascending, the (padded) segments disjoint and inside arena_dwords.  16-byte accesses where
+ * the source is on a 16-byte boundary too.
+ * dcv_state_unpack_multi: the inverse copy (no digest, no workspace; one launch per table that has dwords).
+ * dcv_state_digest_multi: the digests alone, of live tensors or of arena segments; nothing is written but digests and workspace. */
+size_t dcv_state_workspace_bytes(int n_tensors, const int64_t* dwords);
+int dcv_state_pack_multi(int n_tensors, const void* const* src, const int64_t* dwords, void* arena, int64_t arena_dwords, const int64_t* offsets,
+                         uint64_t* digests, void* workspace, size_t workspace_bytes, void* stream);
+int dcv_state_unpack_multi(int n_tensors, void* const* dst, const int64_t* dwords, const void* arena, int64_t arena_dwords, const int64_t* offsets, void* stream);
+int dcv_state_digest_multi(int n_tensors, const void* const* src, const int64_t* dwords, uint64_t* digests, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- bf16 channels-last ("CL16") data path -------------------------------------------------- *
  * BASELINE.json configs[2] ("surreal-depth1, bf16 MFMA") and configs[4] ("fp16 MFMA") name 16-bit variants of the same step
  * (config/surreal-depth1.yml:5,47-76, config/isogd-flow.yml; the reference itself is fp32-only).  This is that path as a DATA path:
