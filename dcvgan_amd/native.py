@@ -176,6 +176,11 @@ _SIGS = {
     "dcv_state_pack_multi": (C.c_int, [C.c_int, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_size_t, _P]),
     "dcv_state_unpack_multi": (C.c_int, [C.c_int, _P, _P, _P, C.c_int64, _P, _P]),
     "dcv_state_digest_multi": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
+    # RunMonitor: the device-side training log and the sample log's histogram and mosaic (added symbols only: the ABI version stays 4)
+    "dcv_monitor_observe": (C.c_int, [C.c_int, _P, C.c_int, _P, _P, _P, _P]),
+    "dcv_monitor_roll": (C.c_int, [C.c_int, C.c_int, _P, _P, C.c_int64, _P]),
+    "dcv_hist_u8": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "dcv_video_grid_u8": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     # synchronised BatchNorm for data parallel, fp32 path (added symbols only: the ABI version stays 4)
     "dcv_bn_sync_row_doubles": (C.c_size_t, [C.c_int]),
     "dcv_bn_sync_sums": (C.c_int, [_P, _D, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),

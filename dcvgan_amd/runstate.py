@@ -208,7 +208,8 @@ def _words_view(t: torch.Tensor) -> np.ndarray:
 
 
 class RunState:
-    def __init__(self, models, optimizers, runner=None, ema=None, spectral=None, augment=None, lecam=None, sampler=None, rngs=(), extra=None, slots: int = 2):
+    def __init__(self, models, optimizers, runner=None, ema=None, spectral=None, augment=None, lecam=None, sampler=None, rngs=(), extra=None, slots: int = 2,
+                 monitor=None):
         if int(slots) < 1:
             raise ValueError(f"RunState: slots >= 1, got {slots!r}")
         if extra is not None and not isinstance(extra, dict):
@@ -216,6 +217,9 @@ class RunState:
         self.models, self.optimizers, self.runner, self.ema, self.spectral, self.augment, self.lecam, self.sampler = \
             models, optimizers, runner, ema, spectral, augment, lecam, sampler
         self.rngs, self.extra, self.slots = tuple(rngs), extra, int(slots)
+        # monitor.RunMonitor: its live window is one more entry and its names, interval and ring position one more block of host scalars; records already published
+        # (on their way to the host or waiting for poll()) are the caller's and are not part of the state.  None: manifests and files are what they are without it
+        self.monitor = monitor
         self._lay: Optional[_Layout] = None
         self._arenas: List[Optional[torch.Tensor]] = [None] * self.slots
         self._digests: List[Optional[torch.Tensor]] = [None] * self.slots
@@ -296,6 +300,8 @@ class RunState:
             out.append(("augment.state", self.augment.state))
         if self.lecam is not None:
             out.append(("lecam.state", self.lecam.state))
+        if self.monitor is not None:
+            out.append(("monitor.state", self.monitor.state))
         return out
 
     def _layout(self) -> _Layout:
@@ -334,6 +340,8 @@ class RunState:
         h["lecam"] = None if self.lecam is None else {k: getattr(self.lecam, k) for k in LECAM_RULE}
         h["spectral"] = None if self.spectral is None else dict(eps=self.spectral.eps)
         h["extra"] = copy.deepcopy(self.extra)
+        if self.monitor is not None:      # (no key at all without one: the host scalars of such a run are what they were)
+            h["monitor"] = dict(slots=list(self.monitor.slots), groups=list(self.monitor.groups), interval=self.monitor.interval, rolled=self.monitor.rolled)
         return h
 
     # ---- compatibility of a snapshot with the live objects ----------------------------------------------------------------------------------------------
@@ -384,6 +392,13 @@ class RunState:
                            ("spectral", self.spectral)):
             if (host[what] is None) != (live is None):
                 raise NativeError(f"RunState: {what}: " + ("the snapshot has none, the live run has one" if host[what] is None else "the snapshot has one, the live run none"))
+        theirs_mon = host.get("monitor")
+        if (theirs_mon is None) != (self.monitor is None):
+            raise NativeError("RunState: monitor: " + ("the snapshot has none, the live run has one" if theirs_mon is None else "the snapshot has one, the live run none"))
+        if theirs_mon is not None:
+            for k, mine_k in (("slots", list(self.monitor.slots)), ("groups", list(self.monitor.groups))):
+                if list(theirs_mon[k]) != mine_k:
+                    raise NativeError(f"RunState: monitor: the snapshot's {k} are {list(theirs_mon[k])}, the live monitor's {mine_k}")
         if len(host["rngs"]) != len(self._philox()) or len(host["guards"]) != len(self._guards()):
             raise NativeError(f"RunState: the snapshot holds {len(host['rngs'])} random streams and {len(host['guards'])} guards, the live run "
                               f"{len(self._philox())} and {len(self._guards())}")
@@ -440,6 +455,8 @@ class RunState:
             if obj is not None:
                 for k, v in d.items():
                     setattr(obj, k, v)
+        if self.monitor is not None:
+            self.monitor.interval, self.monitor.rolled = int(host["monitor"]["interval"]), int(host["monitor"]["rolled"])
         if self.extra is not None:
             self.extra.clear()
             self.extra.update(copy.deepcopy(host["extra"]))

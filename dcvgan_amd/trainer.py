@@ -129,15 +129,38 @@ def build_evaluator(cfg: StepConfig, models, extractor, ema=None, **kw) -> "eval
     return ev
 
 
+MONITOR_GROUPS = tuple(f"{d}_{k}" for d in ("idis", "vdis", "gdis") for k in ("real", "fake_d", "fake_g"))
+
+
+def build_monitor(cfg: StepConfig, models, optimizers, interval: int = 100, lecam=None, **kw) -> "monitor.RunMonitor":
+    """The training log kept on the device (monitor.RunMonitor) in place of the reference's logger.update(..., loss.cpu().item()) / logger.log()
+    (trainer.py:326-328,363; logger.py:144-148,280-283).  The slots are what the run's ``step()`` returns, in this fixed order: loss_idis, loss_vdis, loss_gdis,
+    loss_gen; lecam_idis, lecam_vdis, lecam_gdis if `lecam` is given; grad_norm_dis, skipped_dis, grad_norm_gen, skipped_gen if the optimisers are guarded.  The
+    nine logit groups are {idis, vdis, gdis} x {real, fake_d (the D phase's fakes), fake_g (the G phase's)}.  Hand it to StepRunner(..., monitor=...), which observes
+    once per iteration and rolls every `interval` iterations; keyword arguments are the constructor's (ring).  Data parallel: each rank monitors its own batch; no
+    collective is added."""
+    from . import monitor
+    slots = ["loss_idis", "loss_vdis", "loss_gdis", "loss_gen"]
+    if lecam is not None:
+        slots += ["lecam_idis", "lecam_vdis", "lecam_gdis"]
+    if getattr(optimizers["idis"], "guard", None) is not None:
+        slots += ["grad_norm_dis", "skipped_dis"]
+    if getattr(optimizers["ggen"], "guard", None) is not None:
+        slots += ["grad_norm_gen", "skipped_gen"]
+    kw.setdefault("device", next(models["idis"].parameters()).device)
+    return monitor.RunMonitor(slots, MONITOR_GROUPS, interval=interval, **kw)
+
+
 def build_run_state(cfg: StepConfig, models, optimizers, runner=None, ema=None, spectral=None, augment=None, lecam=None, sampler=None, rngs=(), extra=None,
-                    slots: int = 2) -> "runstate.RunState":
+                    slots: int = 2, monitor=None) -> "runstate.RunState":
     """Everything the run has become, as one object (runstate.RunState): ``capture()`` packs the models, Adam moments, guard, EMA twins, augmentation
     and LeCam state into a device arena on the current stream and copies the host scalars; the snapshot restores in memory (rollback) or through one file (resume in
     fresh objects, bit for bit); ``fingerprint()`` digests the live state without a copy.  Hand over the same objects StepRunner got; ``rngs`` are random streams
-    of the caller's own, ``extra`` a dict of the caller's plain values (the generator behind ``t_rand`` belongs there).  The iteration itself is untouched."""
+    of the caller's own, ``extra`` a dict of the caller's plain values (the generator behind ``t_rand`` belongs there).  The iteration itself is untouched.
+    `monitor` (build_monitor): its live window becomes part of the state."""
     from . import runstate
     return runstate.RunState(models, optimizers, runner=runner, ema=ema, spectral=spectral, augment=augment, lecam=lecam, sampler=sampler, rngs=rngs, extra=extra,
-                             slots=slots)
+                             slots=slots, monitor=monitor)
 
 
 class StepRunner:
@@ -149,8 +172,15 @@ class StepRunner:
 
     def __init__(self, cfg: StepConfig, models, optimizers, loss, sync_losses: bool = False, elide_dead_backward: bool = False,
                  side_streams: Optional[bool] = None, ema: Optional["optim.ModelEma"] = None, spectral: Optional["optim.SpectralNorm"] = None,
-                 augment: Optional["augment.ClipAugment"] = None, lecam: Optional["lecam.LeCam"] = None):
+                 augment: Optional["augment.ClipAugment"] = None, lecam: Optional["lecam.LeCam"] = None, monitor: Optional["monitor.RunMonitor"] = None):
         self.cfg, self.models, self.opt, self.loss = cfg, models, optimizers, loss
+        # monitor.RunMonitor (build_monitor): at the end of step() the iteration's scalars and the nine logits tensors are folded into its device window (one launch,
+        # on the main stream after the lanes have joined), and every monitor.interval iterations the window is published (one more); it only reads: parameters,
+        # buffers, losses and random draws are those of the run without it; None leaves the iteration as it is
+        if monitor is not None and sync_losses:
+            raise ValueError("StepRunner: monitor and sync_losses=True exclude one another: with sync_losses the iteration's values are Python floats read on the host "
+                             "(the reference's way), and the monitor takes device scalars and does not upload")
+        self.monitor = monitor
         # lecam.LeCam (build_lecam): the D phase forms its three losses through it — loss_idis / loss_vdis / loss_gdis of step()'s result then INCLUDE their regulariser
         # term, which the result also carries alone as lecam_idis / lecam_vdis / lecam_gdis — and the anchors move every iteration, also one whose D update is gated
         # off or skipped by the guard (they are statistics of the outputs, not of the weights); the G phase is untouched; None leaves the iteration as it is
@@ -298,7 +328,8 @@ class StepRunner:
             loss_vdis = self.loss.compute_dis_loss(y_real[1], y_fake[1])
             loss_gdis = self.loss.compute_dis_loss(y_real[2], y_fake[2])
         loss_dis = ops.sum_scalars(loss_idis, loss_vdis, loss_gdis) if loss_idis.is_cuda else loss_idis + loss_vdis + loss_gdis      # trainer.py:315
-        if self.iteration % c.num_gen_update == 0:
+        d_steps = self.iteration % c.num_gen_update == 0      # the D phase's gate, decided once (the monitor reads it again below)
+        if d_steps:
             loss_dis.backward(guard_dis.root(loss_dis) if guard_dis is not None else self._root(loss_dis))
             self._mark("D: backward (D lanes, then the generators' dead backward)")
             if self.spectral is not None:
@@ -322,6 +353,9 @@ class StepRunner:
             self._guard_report(out, guard_dis, "dis")
         if self.augment is not None:
             self.augment.end_of_iteration(self.iteration)      # every `interval` iterations: p follows r (one thread; after an all-reduce of the sums under data parallelism)
+        if self.monitor is not None:
+            seen = {f"{n}_real": y.detach() for n, y in zip(("idis", "vdis", "gdis"), y_real)}
+            seen.update({f"{n}_fake_d": y.detach() for n, y in zip(("idis", "vdis", "gdis"), y_fake)})
         del y_real, y_fake, xg_fake, xc_fake, loss_dis
         # ---- generator phase (trainer.py:338-363) ----
         ggen.train(); cgen.train()
@@ -332,7 +366,8 @@ class StepRunner:
         y_fake = self._fakes_through(dis, idis, xg_fake, xc_fake, t_rand)
         loss_gen = self.loss.compute_gen_loss(*y_fake)
         self._mark("G: discriminators forward on the fakes")
-        if self.iteration % c.num_dis_update == 0:
+        g_steps = self.iteration % c.num_dis_update == 0      # the G phase's gate
+        if g_steps:
             loss_gen.backward(guard_gen.root(loss_gen) if guard_gen is not None else self._root(loss_gen))
             self._mark("G: backward (D lanes, then the generators)")
             if guard_gen is not None:
@@ -346,6 +381,14 @@ class StepRunner:
         out["loss_gen"] = loss_gen.cpu().item() if self.sync_losses else loss_gen.detach()     # trainer.py:363
         if guard_gen is not None:
             self._guard_report(out, guard_gen, "gen")
+        if self.monitor is not None:
+            seen.update({f"{n}_fake_g": y.detach() for n, y in zip(("idis", "vdis", "gdis"), y_fake)})
+            gated = ([] if d_steps else ["grad_norm_dis", "skipped_dis"]) + ([] if g_steps else ["grad_norm_gen", "skipped_gen"])
+            # a gated phase measured nothing: its guard fields still hold the measurement before, and their slots are not observed
+            self.monitor.observe({k: v for k, v in out.items() if k not in gated}, seen)
+            if self.iteration % self.monitor.interval == 0:
+                self.monitor.roll(self.iteration)
+            del seen
         if xc_real.is_cuda:
             e = torch.cuda.Event()
             e.record(torch.cuda.current_stream())      # (the lanes and the companion stream have joined the main stream by now)

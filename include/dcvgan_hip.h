@@ -637,6 +637,55 @@ int dcv_state_pack_multi(int n_tensors, const void* const* src, const int64_t* d
 int dcv_state_unpack_multi(int n_tensors, void* const* dst, const int64_t* dwords, const void* arena, int64_t arena_dwords, const int64_t* offsets, void* stream);
 int dcv_state_digest_multi(int n_tensors, const void* const* src, const int64_t* dwords, uint64_t* digests, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- RunMonitor: the training log kept on the device (added symbols only: the ABI version stays 4) ---------------------------- *
+ * The reference reads four losses on the host every iteration (trainer.py:326-328,363: logger.update("loss_*", loss.cpu().item())), averages them between
+ * logger.log() calls (logger.py:144-148,280-283) and histograms / tiles its samples in numpy (trainer.py:109-169).  These entries keep all of that on the device.
+ * The state is ONE tensor of 8-byte words in device memory, owned by the caller: a header, then n_slots scalar slots, then n_groups logit groups.  Fields marked
+ * f64 hold the bits of a double, the others an int64.  A fresh state is all zero except every slot's MIN = +inf and MAX = -inf (and FIRST_ITERATION, the caller's). */
+#define DCV_MONITOR_MAX_SLOTS 32
+#define DCV_MONITOR_MAX_GROUPS 16
+#define DCV_MONITOR_HEADER_WORDS 4
+#define DCV_MONITOR_FIRST_ITERATION 0   /* i64: the first iteration of the window (the roll before it stamped iteration + 1)                    */
+#define DCV_MONITOR_LAST_ITERATION 1    /* i64: in a record the iteration of its roll; in the live window that of the roll before               */
+#define DCV_MONITOR_OBSERVATIONS 2      /* i64: dcv_monitor_observe calls in the window                                                         */
+#define DCV_MONITOR_ROLLS 3             /* i64: rolls before this window: survives the reset and increments                                     */
+#define DCV_MONITOR_SLOT_WORDS 6
+#define DCV_MONITOR_SLOT_SUM 0          /* f64: sum of the finite values, in call order, one rounding per value                                 */
+#define DCV_MONITOR_SLOT_COUNT 1        /* i64: finite values                                                                                   */
+#define DCV_MONITOR_SLOT_NONFINITE 2    /* i64: inf / NaN values (left out of SUM, MIN, MAX)                                                    */
+#define DCV_MONITOR_SLOT_MIN 3          /* f64: +inf while COUNT == 0                                                                           */
+#define DCV_MONITOR_SLOT_MAX 4          /* f64: -inf while COUNT == 0                                                                           */
+#define DCV_MONITOR_SLOT_LAST 5         /* f64: the last observed value, non-finite ones included                                               */
+#define DCV_MONITOR_GROUP_WORDS 6
+#define DCV_MONITOR_GROUP_N 0           /* i64: logits seen, non-finite ones included                                                           */
+#define DCV_MONITOR_GROUP_SUM 1         /* f64: sum of the finite logits                                                                        */
+#define DCV_MONITOR_GROUP_SUMSQ 2       /* f64: sum of (double)y * (double)y over the finite logits                                             */
+#define DCV_MONITOR_GROUP_POS 3         /* i64: finite logits > 0 (+-0 counts in neither)                                                       */
+#define DCV_MONITOR_GROUP_NEG 4         /* i64: finite logits < 0                                                                               */
+#define DCV_MONITOR_GROUP_NONFINITE 5   /* i64: inf / NaN logits (left out of both sums and both sign counts)                                   */
+/* trainer.py:326-328,363 + logger.py:144-148 (Logger.update).  slots[s]: a HOST table of n_slots pointers to fp32 device scalars; NULL = not observed this
+ * iteration.  A finite v: SUM = SUM + (double)v (one rounding), COUNT += 1, MIN / MAX by `<` / `>` on doubles; a non-finite v: NONFINITE += 1; LAST = (double)v
+ * either way.  groups[g]: a HOST table of n_groups contiguous fp32 device tensors of group_n[g] elements, 1 <= n <= 2^24; NULL = skipped.  Per group the batch
+ * sums S = sum (double)y and Q = sum (double)y * (double)y over the finite elements in dcv_lecam_sums' order (256 lanes, lane l adds elements l, l + 256, ... into
+ * a double that starts at +0.0; then p[l] += p[l + s] for s = 128 .. 1), then SUM = SUM + S and SUMSQ = SUMSQ + Q, one rounding each; POS, NEG, NONFINITE and N
+ * are exact integer counts.  OBSERVATIONS += 1.  One launch: one workgroup per group plus one for the scalars; no atomics; nothing but the state is written.
+ * DCV_EINVAL before any launch unless 0 <= n_slots <= 32, 0 <= n_groups <= 16, no needed table NULL, the state non-null on an 8-byte boundary. */
+int dcv_monitor_observe(int n_slots, const float* const* slots, int n_groups, const float* const* groups, const int64_t* group_n, int64_t* state, void* stream);
+/* logger.py:280-283 (Logger.log: publish the averages' ingredients, start over).  record[i] = state[i] for every word, with record[LAST_ITERATION] = iteration;
+ * then the window is reset: every slot's MIN = +inf, MAX = -inf, every other slot and group word 0, OBSERVATIONS = 0, FIRST_ITERATION = iteration + 1,
+ * LAST_ITERATION = iteration, ROLLS += 1.  `record`: 4 + 6 n_slots + 6 n_groups words of device memory on an 8-byte boundary, not the state.  One launch. */
+int dcv_monitor_roll(int n_slots, int n_groups, int64_t* state, int64_t* record, int64_t iteration, void* stream);
+/* trainer.py:134-135,159-160 (tf_log_histgram(x[:, 0])): counts[b] (+)= the number of bytes equal to b in channel `channel` of the contiguous uint8 tensor
+ * x (N, C, T, H, W); counts: 256 int64 in device memory.  accumulate = 0 overwrites counts (one more launch that zeroes them), otherwise adds (batched sampling).
+ * A workgroup takes up to 16 KiB of one clip's run of T*H*W bytes: 16-byte loads between the run's 16-byte boundaries, single bytes before and after (runs start
+ * misaligned whenever C*T*H*W % 16 != 0); counters privatised per wave in LDS, equal neighbouring bytes folded into one add; one 64-bit global atomic add per
+ * non-empty bin and workgroup.  Integer adds commute: exact.  DCV_EINVAL before any launch for an extent < 1, channel outside [0, C), a NULL pointer. */
+int dcv_hist_u8(const uint8_t* x, int N, int C, int T, int H, int W, int channel, int64_t* counts, int accumulate, void* stream);
+/* trainer.py:138-143,163-168 (make_video_grid twice, np.concatenate on the last axis, transpose(0, 2, 1, 3, 4)) as one gather: geo, colour: contiguous uint8
+ * (N, 3, T, H, W), N = rows * cols; out: contiguous uint8 (1, T, 3, rows*H, 2*cols*W); clip r*cols + c lands in cell (r, c) of its half, geo on the left.
+ * 16-byte copies when W % 16 == 0 and all three pointers are on 16-byte boundaries, single bytes otherwise.  One launch. */
+int dcv_video_grid_u8(const uint8_t* geo, const uint8_t* colour, int rows, int cols, int N, int T, int H, int W, uint8_t* out, void* stream);
+
 /* ---- bf16 channels-last ("CL16") data path -------------------------------------------------- *
  * BASELINE.json configs[2] ("surreal-depth1, bf16 MFMA") and configs[4] ("fp16 MFMA") name 16-bit variants of the same step
  * (config/surreal-depth1.yml:5,47-76, config/isogd-flow.yml; the reference itself is fp32-only).  This is that path as a DATA path:
