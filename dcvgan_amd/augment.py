@@ -10,6 +10,7 @@ block that ``dcv_aug_observe`` / ``dcv_aug_adjust`` update.  No value is read on
 from __future__ import annotations
 
 import ctypes as C
+import math
 import struct
 from typing import Optional
 
@@ -17,19 +18,36 @@ import torch
 from torch.autograd import Function
 
 from . import native as N
-from .native import AugLimits, NativeError, check, dims5, lib, ptr, stream_ptr
+from .native import AugLimits, AugWarpLimits, NativeError, check, dims5, lib, ptr, stream_ptr
 from .rng import PhiloxRng
 
 FLIP, TRANSLATE, CUTOUT, COLOUR = 1, 2, 4, 8          # dcv_aug_limits.mask
-OPS = {"flip": FLIP, "translate": TRANSLATE, "cutout": CUTOUT, "colour": COLOUR}
+SCALE, ROTATE, ANISO, SUBPIXEL, SATURATION = 16, 32, 64, 128, 256      # dcv_aug_warp_limits.mask: the interpolated warps and saturation
+WARP_MASK = SCALE | ROTATE | ANISO | SUBPIXEL | SATURATION
+OPS = {"flip": FLIP, "translate": TRANSLATE, "cutout": CUTOUT, "colour": COLOUR,
+       "scale": SCALE, "rotate": ROTATE, "aniso": ANISO, "subpixel": SUBPIXEL, "saturation": SATURATION}
+ROW_WORDS, WARP_ROW_WORDS = 8, 24                      # a table is (B, 8) with none of the five new ops enabled, else (B, 24)
 STATE_WORDS = 8                                        # p (fp32 bits), sum_sign, count, adjusts, 4 reserved
 MAX_HW = 4096                                          # the kernels' limit on H and W
 IDENTITY_ROW = (0, 0, 0, 0, 0, 0, struct.unpack("<i", struct.pack("<f", 1.0))[0], 0)
+_ONE = IDENTITY_ROW[6]
+IDENTITY_WARP_ROW = IDENTITY_ROW + (0, _ONE, 0, 0, 0, _ONE, 0, _ONE, 0, 0, _ONE, _ONE, 0, 0, 0, 0)
 # The draws' Philox key is the seed plus this constant: a model's latent draw with the same (seed, offset) runs the same counters (idx 0, 1, ..) through another key.
 SEED_SALT = 0x9E3779B97F4A7C15
 
 
 _STATS = {"launches": 0}
+
+
+def _check_warp_limits(scale_max, aniso_max, rot_max_deg, frac, sat):
+    """scale_max * aniso_max <= 2 and |theta| < 180 degrees keep every drawn L inside the adjoint's 9 x 9 candidate box (|l00| + |l01| <= 2 sqrt 2 < 3)."""
+    if not (float(scale_max) >= 1.0 and float(aniso_max) >= 1.0 and float(rot_max_deg) >= 0.0 and 0.0 <= float(frac) <= 1.0 and float(sat) >= 0.0):
+        raise ValueError(f"ClipAugment: scale_max >= 1, aniso_max >= 1, rot_max_deg >= 0, 0 <= frac <= 1, sat >= 0 (each op's identity or above), got "
+                         f"{scale_max!r}, {aniso_max!r}, {rot_max_deg!r}, {frac!r}, {sat!r}")
+    if float(scale_max) * float(aniso_max) > 2.0:
+        raise ValueError(f"ClipAugment: scale_max * aniso_max must be <= 2 (the adjoint's candidate box), got {scale_max!r} * {aniso_max!r}")
+    if float(rot_max_deg) >= 180.0:
+        raise ValueError(f"ClipAugment: rot_max_deg must be below 180, got {rot_max_deg!r}")
 
 
 def launches() -> int:
@@ -53,9 +71,15 @@ def _require_clip(t: torch.Tensor, what: str):
         raise NativeError(f"{what}: H and W up to {MAX_HW}, got {t.shape[3]} x {t.shape[4]}")
 
 
-def _require_table(table: torch.Tensor, batch: int):
-    if not table.is_cuda or table.dtype != torch.int32 or tuple(table.shape) != (batch, 8) or not table.is_contiguous():
-        raise NativeError(f"augmentation table: expected a contiguous ({batch}, 8) int32 device tensor, got {table.dtype}{tuple(table.shape)} on {table.device}")
+def _require_table(table: torch.Tensor, batch: int, words: int = ROW_WORDS):
+    if not table.is_cuda or table.dtype != torch.int32 or tuple(table.shape) != (batch, words) or not table.is_contiguous():
+        raise NativeError(f"augmentation table: expected a contiguous ({batch}, {words}) int32 device tensor, got {table.dtype}{tuple(table.shape)} on {table.device}")
+
+
+def _entry(table: torch.Tensor, what: str) -> str:
+    """The C entry for this table's width: dcv_aug_<what> for (B, 8), dcv_aug_warp_<what> for (B, 24).  The last integer argument of an entry is
+    flip_negate_channel for the first family and vector_channels for the second."""
+    return ("dcv_aug_warp_" if table.shape[1] == WARP_ROW_WORDS else "dcv_aug_") + what
 
 
 def _launch(fn_name: str, x: torch.Tensor, table: torch.Tensor, colour: bool, neg_ch: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -97,6 +121,31 @@ def apply_backward(dy: torch.Tensor, table: torch.Tensor, colour: bool, flip_neg
     return _launch("dcv_aug_apply_backward", dy, table, colour, flip_negate_channel, out)
 
 
+def warp_apply(x: torch.Tensor, table: torch.Tensor, colour: bool, vector_channels: int = 0) -> torch.Tensor:
+    """One stream's forward under a (B, 24) table without a tape: dcv_aug_warp_apply."""
+    _require_clip(x, "augment input")
+    _require_table(table, x.shape[0], WARP_ROW_WORDS)
+    _require_streams(colour, vector_channels)
+    return _launch("dcv_aug_warp_apply", x, table, colour, vector_channels)
+
+
+def warp_apply_backward(dy: torch.Tensor, table: torch.Tensor, colour: bool, vector_channels: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One stream's adjoint under a (B, 24) table: dcv_aug_warp_apply_backward (into `out`, a strided view of dy's shape, or a fresh contiguous tensor)."""
+    _require_clip(dy, "augment cotangent")
+    _require_table(table, dy.shape[0], WARP_ROW_WORDS)
+    _require_streams(colour, vector_channels)
+    return _launch("dcv_aug_warp_apply_backward", dy, table, colour, vector_channels, out)
+
+
+def _require_streams(colour, vector_channels):
+    if int(vector_channels) not in (0, 1) or (colour and vector_channels):
+        raise NativeError(f"augment: vector_channels is 0 or 1, and 0 on the colour stream (got {vector_channels!r}, colour {colour!r})")
+
+
+def _adjoint(dy, table, colour, ch, out):
+    return _launch(_entry(table, "apply_backward"), dy, table, colour, ch, out)
+
+
 class _AugPair(Function):
     """(xg, xc) -> (yg, yc) under one table.  The backward launches one adjoint per stream that received a cotangent and whose input asked for a gradient, and
     writes each gradient in its input's own layout."""
@@ -106,16 +155,16 @@ class _AugPair(Function):
         ctx.table, ctx.neg = table, (int(neg_g), int(neg_c))
         ctx.layouts = [(tuple(x.shape), _layout_of(tuple(x.shape), tuple(x.stride()))) for x in (xg, xc)]
         ctx.set_materialize_grads(False)
-        return _launch("dcv_aug_apply", xg, table, False, neg_g), _launch("dcv_aug_apply", xc, table, True, neg_c)
+        return _launch(_entry(table, "apply"), xg, table, False, neg_g), _launch(_entry(table, "apply"), xc, table, True, neg_c)
 
     @staticmethod
     def backward(ctx, dyg, dyc):
         from .ops import _dense
         dg = dc = None
         if dyg is not None and ctx.needs_input_grad[0]:
-            dg = apply_backward(_dense(dyg), ctx.table, False, ctx.neg[0], _grad_like(*ctx.layouts[0], dyg.device))
+            dg = _adjoint(_dense(dyg), ctx.table, False, ctx.neg[0], _grad_like(*ctx.layouts[0], dyg.device))
         if dyc is not None and ctx.needs_input_grad[1]:
-            dc = apply_backward(_dense(dyc), ctx.table, True, ctx.neg[1], _grad_like(*ctx.layouts[1], dyc.device))
+            dc = _adjoint(_dense(dyc), ctx.table, True, ctx.neg[1], _grad_like(*ctx.layouts[1], dyc.device))
         return dg, dc, None, None, None
 
 
@@ -126,12 +175,12 @@ class _AugOne(Function):
     def forward(ctx, x, table, colour, neg):
         ctx.table, ctx.colour, ctx.neg = table, bool(colour), int(neg)
         ctx.layout = (tuple(x.shape), _layout_of(tuple(x.shape), tuple(x.stride())))
-        return _launch("dcv_aug_apply", x, table, colour, neg)
+        return _launch(_entry(table, "apply"), x, table, colour, neg)
 
     @staticmethod
     def backward(ctx, dy):
         from .ops import _dense
-        return apply_backward(_dense(dy), ctx.table, ctx.colour, ctx.neg, _grad_like(*ctx.layout, dy.device)), None, None, None
+        return _adjoint(_dense(dy), ctx.table, ctx.colour, ctx.neg, _grad_like(*ctx.layout, dy.device)), None, None, None
 
 
 class _AugFan(Function):
@@ -146,7 +195,7 @@ class _AugFan(Function):
         ctx.table, ctx.neg, ctx.t = table, int(neg), int(t)
         ctx.layout = (tuple(x.shape), _layout_of(tuple(x.shape), tuple(x.stride())))
         ctx.set_materialize_grads(False)
-        y = _launch("dcv_aug_apply", x, table, False, neg)
+        y = _launch(_entry(table, "apply"), x, table, False, neg)
         return x.view_as(x), y[:, :, ctx.t], y.view_as(y), y.view_as(y)
 
     @staticmethod
@@ -166,7 +215,7 @@ class _AugFan(Function):
         dd = lambda g: (ptr(g), C.byref(dims5(g))) if g is not None else (None, None)
         g0, g1 = (full + [None, None])[:2]
         od = dims5(out)
-        _call("dcv_aug_fan_backward", *dd(d_c), *dd(g0), *dd(g1), *dd(d_f), ctx.t, ptr(ctx.table), int(ctx.table.shape[0]), ptr(out), C.byref(od), 0, ctx.neg,
+        _call(_entry(ctx.table, "fan_backward"), *dd(d_c), *dd(g0), *dd(g1), *dd(d_f), ctx.t, ptr(ctx.table), int(ctx.table.shape[0]), ptr(out), C.byref(od), 0, ctx.neg,
               stream_ptr())
         return out, None, None, None
 
@@ -181,13 +230,20 @@ class ClipAugment:
     ``ops``: the enabled transforms, any of "flip", "translate", "cutout", "colour".  ``max_dx`` / ``max_dy`` / ``cut_size`` default to W/8, H/8 and min(H, W)/2 of
     the clip at hand; ``contrast`` 0.5 (gain in (0.5, 1.5]) and ``brightness`` 1.0 (bias in (-0.5, 0.5]) are DiffAugment's.
     The geometry stream of an optical-flow config negates channel 0 (the horizontal component) under a flip.
+    Interpolated warps and saturation, off unless named in ``ops``: "scale" (isotropic, ratio in [1/scale_max, scale_max]), "rotate" (up to
+    ``rot_max_deg`` either way; the draw is uniform in tan(theta / 2), so theta is slightly denser towards 0), "aniso" (sx / sy ratio up to aniso_max^2),
+    "subpixel" (a shift of up to ``frac`` of the plane on top of the integer one), "saturation" (about the pixel's channel mean, s in 1 + sat * (-1, 1]; RGB only).
+    The defaults (1.3, 45, 1.25, 0.125, 1.0) are ADA-like; nobody has tuned them for clips.  With any of the five enabled the table is (B, 24) and the
+    dcv_aug_warp_* entries run — bilinear taps, a gather adjoint, still no atomics and no torch kernel; an optical-flow clip's vectors turn with the warp.
+    With none enabled nothing changes: the (B, 8) table, the same entries, the same draws, the same state_dict keys.
     The draws come from a PhiloxRng of this object's own: the models' random streams are what they are without augmentation.
     Data parallel: with torch.distributed initialised and more than one rank, the two accumulators are all-reduced (SUM, int32: exact, order-free) over a process
     group of this object's own before every adjustment, so every rank holds the same p.  Constructing it is then a collective call."""
 
     def __init__(self, cfg, device, p: float = 0.0, adaptive: bool = True, target: float = 0.6, interval: int = 4, p_max: float = 0.8,
                  adjust_clips: int = 500_000, ops=("flip", "translate", "cutout", "colour"), max_dx: Optional[int] = None, max_dy: Optional[int] = None,
-                 cut_size: Optional[int] = None, contrast: float = 0.5, brightness: float = 1.0, batch: Optional[int] = None, seed: Optional[int] = None):
+                 cut_size: Optional[int] = None, contrast: float = 0.5, brightness: float = 1.0, batch: Optional[int] = None, seed: Optional[int] = None,
+                 scale_max: float = 1.3, aniso_max: float = 1.25, rot_max_deg: float = 45.0, frac: float = 0.125, sat: float = 1.0):
         if not 0.0 <= float(p) <= 1.0 or not 0.0 <= float(p_max) <= 1.0:
             raise ValueError(f"ClipAugment: p and p_max must be in [0, 1], got {p!r}, {p_max!r}")
         if not -1.0 <= float(target) <= 1.0 or int(interval) < 1 or int(adjust_clips) < 1 or contrast < 0 or brightness < 0:
@@ -195,6 +251,8 @@ class ClipAugment:
         unknown = [o for o in ops if o not in OPS]
         if unknown:
             raise ValueError(f"ClipAugment: unknown ops {unknown}; known: {sorted(OPS)}")
+        _check_warp_limits(scale_max, aniso_max, rot_max_deg, frac, sat)
+        self.scale_max, self.aniso_max, self.rot_max_deg, self.frac, self.sat = float(scale_max), float(aniso_max), float(rot_max_deg), float(frac), float(sat)
         self.cfg, self.device = cfg, torch.device(device)
         self.adaptive, self.target, self.interval, self.p_max, self.adjust_clips = bool(adaptive), float(target), int(interval), float(p_max), int(adjust_clips)
         self.batch = int(batch if batch is not None else cfg.batchsize)
@@ -204,6 +262,7 @@ class ClipAugment:
         self.max_dx, self.max_dy, self.cut_size, self.contrast, self.brightness = max_dx, max_dy, cut_size, float(contrast), float(brightness)
         self.neg_g = 0 if getattr(cfg, "geometric_info", None) == "optical-flow" else -1      # a mirrored flow field's horizontal component changes sign
         self.neg_c = -1
+        self.vector_channels = 1 if self.neg_g == 0 else 0      # what the (B, 24) entries take in flip_negate_channel's place
         self.rng = PhiloxRng(seed)
         # the state block: a host tensor copied to the device once (no kernel)
         self.state = self._host_state(float(p), 0, 0, 0).to(self.device)
@@ -226,15 +285,37 @@ class ClipAugment:
 
     def limits(self, H: int, W: int) -> AugLimits:
         return AugLimits(int(self.max_dx if self.max_dx is not None else W // 8), int(self.max_dy if self.max_dy is not None else H // 8),
-                         int(self.cut_size if self.cut_size is not None else min(H, W) // 2), self.mask, self.contrast, self.brightness)
+                         int(self.cut_size if self.cut_size is not None else min(H, W) // 2), self.mask & 15, self.contrast, self.brightness)
+
+    @property
+    def warp(self) -> bool:
+        """Any of scale / rotate / aniso / subpixel / saturation enabled: the (B, 24) table and the dcv_aug_warp_* entries."""
+        return bool(self.mask & WARP_MASK)
+
+    @property
+    def row_words(self) -> int:
+        return WARP_ROW_WORDS if self.warp else ROW_WORDS
+
+    def warp_limits(self) -> AugWarpLimits:
+        return AugWarpLimits(self.scale_max, self.aniso_max, math.tan(math.radians(self.rot_max_deg) / 2.0), self.frac, self.sat, self.mask & WARP_MASK)
+
+    def _channels(self):
+        """(geometry, colour): the entries' last integer argument for this object's table width."""
+        return (self.vector_channels, 0) if self.warp else (self.neg_g, self.neg_c)
 
     def draw(self, B: int, H: int, W: int) -> torch.Tensor:
-        """A fresh (B, 8) table at the state block's current p: one launch, and one step of this object's random stream."""
+        """A fresh (B, 8) — with a warp op enabled (B, 24) — table at the state block's current p: one launch, and one step of this object's random stream."""
         if self.state.device.type != "cuda":
             raise NativeError(f"ClipAugment: the state block is on {self.state.device} — the augmentation runs on the GPU only (there is no CPU fallback)")
-        table = torch.empty((int(B), 8), dtype=torch.int32, device=self.state.device)
+        table = torch.empty((int(B), self.row_words), dtype=torch.int32, device=self.state.device)
         lim = self.limits(H, W)
         seed, offset = self.rng._next()
+        if self.warp:
+            wl = self.warp_limits()
+            _call("dcv_aug_warp_draw", ptr(table), int(B), int(H), int(W), ptr(self.state), C.byref(lim), C.byref(wl), (seed + SEED_SALT) & 0xFFFFFFFFFFFFFFFF, offset,
+                  stream_ptr())
+            self.draws += 1
+            return table
         _call("dcv_aug_draw", ptr(table), int(B), int(H), int(W), ptr(self.state), C.byref(lim), (seed + SEED_SALT) & 0xFFFFFFFFFFFFFFFF, offset, stream_ptr())
         self.draws += 1
         return table
@@ -247,30 +328,31 @@ class ClipAugment:
             raise NativeError(f"augment: the pair's clips differ in B, T, H or W: {tuple(xg.shape)} and {tuple(xc.shape)}")
         B, H, W = xg.shape[0], xg.shape[3], xg.shape[4]
         if table is not None:
-            _require_table(table, B)
+            _require_table(table, B, self.row_words)
         else:
             table = self.draw(B, H, W)
+        ch_g, ch_c = self._channels()
         if torch.is_grad_enabled() and (xg.requires_grad or xc.requires_grad):
-            return _AugPair.apply(xg, xc, table, self.neg_g, self.neg_c)
+            return _AugPair.apply(xg, xc, table, ch_g, ch_c)
         # nothing asks for a gradient: no tape entry
-        return _launch("dcv_aug_apply", xg, table, False, self.neg_g), _launch("dcv_aug_apply", xc, table, True, self.neg_c)
+        return _launch(_entry(table, "apply"), xg, table, False, ch_g), _launch(_entry(table, "apply"), xc, table, True, ch_c)
 
     def fan_geometry(self, xg: torch.Tensor, t: int, table: torch.Tensor):
         """The fakes' geometry clip under a tape -> (xg for the colour generator, frame t / whole / whole of the augmented clip for the three discriminators); the
         gradient fan-in of all four readers is one launch (_AugFan)."""
         _require_clip(xg, "augment geometry clip")
-        _require_table(table, xg.shape[0])
+        _require_table(table, xg.shape[0], self.row_words)
         if not 0 <= int(t) < xg.shape[2]:
             raise NativeError(f"augment: frame {t} of a clip of {xg.shape[2]}")
-        return _AugFan.apply(xg, table, self.neg_g, int(t))
+        return _AugFan.apply(xg, table, self._channels()[0], int(t))
 
     def colour(self, xc: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
         """The colour clip of the pair whose geometry clip went through fan_geometry with the same table."""
         _require_clip(xc, "augment colour clip")
-        _require_table(table, xc.shape[0])
+        _require_table(table, xc.shape[0], self.row_words)
         if torch.is_grad_enabled() and xc.requires_grad:
-            return _AugOne.apply(xc, table, True, self.neg_c)
-        return _launch("dcv_aug_apply", xc, table, True, self.neg_c)
+            return _AugOne.apply(xc, table, True, self._channels()[1])
+        return _launch(_entry(table, "apply"), xc, table, True, self._channels()[1])
 
     def observe(self, y: torch.Tensor):
         """Add a discriminator's logits on the real batch to the accumulators (adaptive mode; a no-op in fixed mode)."""
@@ -314,6 +396,12 @@ class ClipAugment:
         return self.state_words()[3]
 
     def state_dict(self):
+        sd = self._state_dict_v1()
+        if self.warp:      # (today's keys only without a warp op)
+            sd.update(scale_max=self.scale_max, aniso_max=self.aniso_max, rot_max_deg=self.rot_max_deg, frac=self.frac, sat=self.sat)
+        return sd
+
+    def _state_dict_v1(self):
         return dict(state=self.state_words(), adaptive=self.adaptive, target=self.target, interval=self.interval, p_max=self.p_max, adjust_clips=self.adjust_clips,
                     batch=self.batch, mask=self.mask, max_dx=self.max_dx, max_dy=self.max_dy, cut_size=self.cut_size, contrast=self.contrast,
                     brightness=self.brightness, rng=dict(fixed_seed=self.rng._fixed_seed, seed_seen=self.rng._seed_seen, counter=self.rng._counter))
@@ -322,10 +410,17 @@ class ClipAugment:
         words = [int(v) for v in sd["state"]]
         if len(words) != STATE_WORDS:
             raise ValueError(f"ClipAugment: the state block has {STATE_WORDS} words, the checkpoint {len(words)}")
+        # the warp constants and the mask are held to the constructor's refusals before anything of this object changes
+        warp = {k: float(sd.get(k, getattr(self, k))) for k in ("scale_max", "aniso_max", "rot_max_deg", "frac", "sat")}
+        _check_warp_limits(**warp)
+        if int(sd["mask"]) & ~(15 | WARP_MASK):
+            raise ValueError(f"ClipAugment: the checkpoint's mask {sd['mask']!r} has bits of no known op")
         self.state.copy_(torch.tensor(words, dtype=torch.int32))
         self.adaptive, self.target, self.interval, self.p_max = bool(sd["adaptive"]), float(sd["target"]), int(sd["interval"]), float(sd["p_max"])
         self.adjust_clips, self.batch, self.mask = int(sd["adjust_clips"]), int(sd["batch"]), int(sd["mask"])
         self.max_dx, self.max_dy, self.cut_size = sd["max_dx"], sd["max_dy"], sd["cut_size"]
         self.contrast, self.brightness = float(sd["contrast"]), float(sd["brightness"])
+        for k, v in warp.items():      # a checkpoint without them loads: the constructor's values stay
+            setattr(self, k, v)
         r = sd["rng"]
         self.rng._fixed_seed, self.rng._seed_seen, self.rng._counter = r["fixed_seed"], r["seed_seen"], int(r["counter"])

@@ -52,6 +52,11 @@ class AugLimits(C.Structure):
     _fields_ = [("mx", C.c_int32), ("my", C.c_int32), ("size", C.c_int32), ("mask", C.c_int32), ("contrast", C.c_float), ("brightness", C.c_float)]
 
 
+class AugWarpLimits(C.Structure):
+    """dcv_aug_warp_limits: the ranges dcv_aug_warp_draw draws the extension words from (scale 16, rotate 32, aniso 64, subpixel 128, saturation 256)."""
+    _fields_ = [("scale_max", C.c_float), ("aniso_max", C.c_float), ("rot_tan_half", C.c_float), ("frac", C.c_float), ("sat", C.c_float), ("mask", C.c_int32)]
+
+
 _P = C.c_void_p
 _D = C.POINTER(Dims5)
 _G = C.POINTER(ConvGeom)
@@ -142,6 +147,11 @@ _SIGS = {
     "dcv_aug_fan_backward": (C.c_int, [_P, _D, _P, _D, _P, _D, _P, _D, C.c_int, _P, C.c_int, _P, _D, C.c_int, C.c_int, _P]),
     "dcv_aug_draw": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_uint64, C.c_uint64, _P]),
     "dcv_aug_observe": (C.c_int, [_P, C.c_int64, _P, _P]),
+    # ... its interpolated warps and saturation: the (B, 24) row (added symbols only)
+    "dcv_aug_warp_apply": (C.c_int, [_P, _D, _P, C.c_int, _P, _D, C.c_int, C.c_int, _P]),
+    "dcv_aug_warp_apply_backward": (C.c_int, [_P, _D, _P, C.c_int, _P, _D, C.c_int, C.c_int, _P]),
+    "dcv_aug_warp_fan_backward": (C.c_int, [_P, _D, _P, _D, _P, _D, _P, _D, C.c_int, _P, C.c_int, _P, _D, C.c_int, C.c_int, _P]),
+    "dcv_aug_warp_draw": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_uint64, C.c_uint64, _P]),
     "dcv_aug_adjust": (C.c_int, [_P, C.c_double, C.c_float, C.c_float, _P]),
     # LeCam regularisation of the discriminators (added symbols only: the ABI version stays 4)
     "dcv_lecam_sums": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P]),

@@ -444,7 +444,64 @@ typedef struct dcv_aug_limits {      /* a host struct, passed by value to the ke
  *   block 3: gain = 1 + (2 contrast) * (u(w0) - 0.5), bias = brightness * (u(w1) - 0.5), every operation rounded to fp32 on its own.
  * A gate that is off writes its op's identity words: p = 0 gives identity rows, p = 1 turns every enabled gate on. */
 int dcv_aug_draw(int32_t* table, int B, int H, int W, const int32_t* state, const dcv_aug_limits* limits, uint64_t seed, uint64_t offset, void* stream);
-/* state[SUM_SIGN] += sum sign(logits[i]) (sign(0) = 0, a NaN counts 0), state[COUNT] += n.  One workgroup, integer sums: exact and repeatable.  1 <= n <= 2^24. */
+/* ---- interpolated warps and saturation: the (N, 24) row (added symbols only: the ABI version stays 4; dcv_aug_limits is unchanged) ------ *
+ * Words 0-7 are the row above.  Word 8 `warp`: 0 = the exact integer path of words 0-2 (bits moved), non-zero = interpolating, where words 9-18 govern the geometry
+ * and words 0-2 are already composed into them.  Words 9-14: a b c d e f (fp32 bits), the inverse map in centred pixel coordinates.  Words 15-18: l00 l01 l10 l11,
+ * the forward linear part L = inverse of [[a, b], [d, e]], written by the draw and never inverted in a kernel.  Word 19: saturation s (1.0 = identity, and exactly
+ * 1.0 skips the step).  Words 20-23 reserved, zero.  Identity extension: {0, 1,0,0, 0,1,0, 1,0,0,1, 1.0, 0,0,0,0}.
+ * Every operation is ONE separately rounded fp32 operation; a unary minus below is 0 - x.  The numpy restatement is tests/augwarp.py.
+ * Forward, warp != 0, output pixel (h, w): 0 inside the cutout box; else cx = (W-1)*0.5, cy = (H-1)*0.5, u = w - cx, v = h - cy, su = (a*u + b*v) + c,
+ *   sv = (d*u + e*v) + f, sx = su + cx, sy = sv + cy, x0 = floor(sx), fx = sx - x0 (y alike); non-finite sx or sy gives 0; indices are clamped to [-2, W] before the
+ *   float-to-int conversion.  Taps (y0,x0) (y0,x0+1) (y0+1,x0) (y0+1,x0+1) with weights (1-fy)(1-fx), (1-fy)fx, fy(1-fx), fy fx; a tap outside the plane or of weight
+ *   exactly 0 is skipped; acc = +0, acc = acc + weight * value in tap order.  Colour stream: value = the colour step on the tap's source pixel,
+ *   m = ((v0+v1)+v2) * third (third = 0x3EAAAAAB), q_c = m + s*(v_c - m) (only when C == 3 and s != 1), y_c = q_c*gain + bias.  vector_channels = 1 (optical flow, C >= 2):
+ *   (r0', r1') = (l00*r0 + l01*r1, l10*r0 + l11*r1) after sampling.  warp == 0: dcv_aug_apply's bits, vector_channels = 1 meaning flip_negate_channel = 0; with
+ *   s != 1 the colour step above on the one source pixel.  colour and vector_channels are not both set, and vector_channels = 1 needs C >= 2 (DCV_EINVAL).
+ * Adjoint, warp != 0, a gather over source pixels p = (ys, xs): du = (xs - cx) - c, dv = (ys - cy) - f, centre ocx = (l00*du + l01*dv) + cx, ocy = (l10*du + l11*dv) + cy,
+ *   half-extents ex = min((|l00| + |l01|) + 1, 4), ey alike; candidates h in [max(ceil(ocy - ey), 0), min(floor(ocy + ey), H-1)] ascending, then w alike: at most 9 x 9.
+ *   A candidate outside the box whose recomputed taps (the forward's operations) contain p with a non-zero weight is a hit.  The hit list has room for 25, the lattice-point bound
+ *   A + P/2 + 1 of the rectangle L (-1, 1)^2 under dcv_aug_warp_draw's limits (sx, sy <= 2), so no drawn row loses a hit; a hand-made row is in contract when
+ *   4 |det L| + 2 (|L e1| + |L e2|) + 1 <= 25 (beyond that the first 25 in scan order count);
+ *   acc = +0, acc = acc + weight * t, t the cotangent there, on vector channels first mixed by L^T: t0 = l00*d0 + l10*d1, t1 = l01*d0 + l11*d1.  Colour stream, on
+ *   the gathered t_c: a_c = gain*t_c, ma = ((a0+a1)+a2)*third, dv_c = ma + s*(a_c - ma).  warp == 0: dcv_aug_apply_backward's bits.  An L outside the box cap is out
+ *   of contract: memory-safe, adjoint unspecified; dcv_aug_warp_draw never makes one.
+ * The fan-in entry forms ((base + A^T dy0) + A^T dy1) + A^T embed(dyf), each A^T term complete before it is added.  One launch each; no atomics.  Any table is memory-safe. */
+#define DCV_AUG_WARP_ROW_WORDS 24
+#define DCV_AUG_T_WARP 8
+#define DCV_AUG_T_INV 9        /* a b c d e f                                                                                  */
+#define DCV_AUG_T_FWD 15       /* l00 l01 l10 l11                                                                              */
+#define DCV_AUG_T_SAT 19
+int dcv_aug_warp_apply(const float* x, const dcv_dims5* xd, const int32_t* table, int table_rows, float* y, const dcv_dims5* yd, int colour, int vector_channels,
+                       void* stream);
+int dcv_aug_warp_apply_backward(const float* dy, const dcv_dims5* dyd, const int32_t* table, int table_rows, float* dx, const dcv_dims5* dxd, int colour,
+                                int vector_channels, void* stream);
+int dcv_aug_warp_fan_backward(const float* base, const dcv_dims5* based, const float* dy0, const dcv_dims5* dy0d, const float* dy1, const dcv_dims5* dy1d,
+                              const float* dyf, const dcv_dims5* dyfd, int frame, const int32_t* table, int table_rows, float* dx, const dcv_dims5* dxd, int colour,
+                              int vector_channels, void* stream);
+#define DCV_AUG_SCALE 16
+#define DCV_AUG_ROTATE 32
+#define DCV_AUG_ANISO 64
+#define DCV_AUG_SUBPIXEL 128
+#define DCV_AUG_SATURATION 256
+typedef struct dcv_aug_warp_limits {      /* a host struct, passed by value to the kernel */
+    float scale_max, aniso_max;      /* >= 1, scale_max * aniso_max <= 2: every drawn L stays inside the adjoint's box               */
+    float rot_tan_half;              /* tan(rot_max / 2), computed once on the host                                                 */
+    float frac;                      /* sub-pixel shift up to frac * W, frac * H                                                     */
+    float sat;                       /* s in 1 + sat * (-1, 1]                                                                       */
+    int32_t mask;                    /* DCV_AUG_SCALE | _ROTATE | _ANISO | _SUBPIXEL | _SATURATION                                   */
+} dcv_aug_warp_limits;
+/* Words 0-7 are what dcv_aug_draw writes for the same (seed, offset, p) (blocks 0-3 at idx = 4 b + j).  Extension blocks j = 4..6 of clip b at idx = 4 B + 4 b + (j - 4);
+ * vv(u) = (u + u) - 1; ratio(u, m): k = (m - 1) * |vv|, vv >= 0 ? 1 + k : 1 / (1 + k).  + - * / only, each rounded on its own.
+ *   block 4: w0 scale gate; w1 s_iso = ratio(u, scale_max); w2 rotate gate; w3 t = rot_tan_half * vv, den = 1 + t*t, cos = (1 - t*t) / den, sin = (t + t) / den
+ *            (the angle is 2 atan(t): slightly non-uniform in theta, denser towards 0)
+ *   block 5: w0 aniso gate; w1 r = ratio(u, aniso_max), sx = s_iso * r, sy = s_iso / r; w2 sub-pixel gate; w3 tx = (frac * W) * vv
+ *   block 6: w0 ty = (frac * H) * vv; w1 saturation gate; w2 s = 1 + sat * vv.        A gate that is off writes its identity.
+ * phi = flip ? -1 : 1, tau = (dx + tx, dy + ty); p_out = R diag(sx, sy) diag(phi, 1) p_src + tau:
+ *   l00 = (cos*sx)*phi, l01 = 0 - sin*sy, l10 = (sin*sx)*phi, l11 = cos*sy; a = phi*(cos/sx), b = phi*(sin/sx), d = 0 - sin/sy, e = cos/sy;
+ *   c = 0 - (a*taux + b*tauy), f = 0 - (d*taux + e*tauy).  warp = 1 iff a scale, rotate, aniso or sub-pixel gate is on; words 9-18 are written either way. */
+int dcv_aug_warp_draw(int32_t* table, int B, int H, int W, const int32_t* state, const dcv_aug_limits* limits, const dcv_aug_warp_limits* warp_limits, uint64_t seed,
+                      uint64_t offset, void* stream);
+/* state[SUM_SIGN] += sum sign(logits[i]) (sign(0) = 0, a NaN counts 0), state[COUNT] += n. One workgroup, integer sums: exact and repeatable.  1 <= n <= 2^24. */
 int dcv_aug_observe(const float* logits, int64_t n, int32_t* state, void* stream);
 /* ADA's rule (Karras et al. 2020) with r = E[sign(D(real))], one thread: if COUNT > 0: r = SUM_SIGN / COUNT in double, p = min(max(p + sgn(r - target) * step, 0), p_max)
  * in fp32 (sgn(0) = 0).  Then SUM_SIGN = COUNT = 0 and ADJUSTS += 1.  The host calls it every `interval` iterations; nothing is read back. */
