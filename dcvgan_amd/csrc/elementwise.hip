@@ -864,6 +864,8 @@ __device__ __forceinline__ void mt_strided(int64_t base, int64_t n, One one) {
 // the aligned branch does: right for kernels whose elements are independent (their results cannot depend on who computes them), and its accesses coalesce.
 // MT_QUAD_ORDER visits the aligned branch's elements per thread in the aligned branch's order, one at a time: for a kernel that adds a thread's elements up in
 // fp32, where the order is the result, so that the sum's bits do not depend on the alignment.  Do not swap one for the other: it changes bits.
+// MT_STRIDED: ema_multi_kernel, sn_scale_kernel, sn_project_kernel (and, through mt_strided alone, the Adam kernels).  MT_QUAD_ORDER: guard_partial_kernel (a
+// thread's fmaf chain of squares) and sn_inner_kernel.  tests/test_opt_exact_gpu.py holds the guard to it: the same gradients at an aligned and at a 4-byte-off base.
 enum MtOrder { MT_STRIDED, MT_QUAD_ORDER };
 template <MtOrder ORDER, class Quad, class One>
 __device__ __forceinline__ void mt_traverse(int64_t base, int64_t n, bool aligned, Quad quad, One one) {
@@ -970,7 +972,7 @@ __global__ __launch_bounds__(256) void guard_partial_kernel(const GuardPack k, i
     const float* __restrict__ g = k.g[at.t];
     float ss = 0.f;
     int bad = 0;
-    mt_traverse<MT_STRIDED>((int64_t)at.blk * MT_BLOCK, k.tab.n[at.t], mt_aligned16(g),
+    mt_traverse<MT_QUAD_ORDER>((int64_t)at.blk * MT_BLOCK, k.tab.n[at.t], mt_aligned16(g),      // a sum: the bits must not depend on the alignment
         [&](int64_t i) {
             const float4 x = *reinterpret_cast<const float4*>(g + i);
             guard_take(x.x, ss, bad); guard_take(x.y, ss, bad); guard_take(x.z, ss, bad); guard_take(x.w, ss, bad);
