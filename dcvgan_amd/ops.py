@@ -190,15 +190,38 @@ def _task_id() -> int:
     return torch._C._current_graph_task_id()
 
 
+def _engine_accumulates(p) -> bool:
+    """True iff the running pass will run `p`'s AccumulateGrad node, i.e. what this pass returns for `p` ends in p.grad.  Not so under torch.autograd.grad (its results
+    are captured and handed to the caller: .grad is left alone, and a gradient nobody asked for is dropped — and freed — as soon as the node that made it returns) nor
+    under backward(inputs=...) that leaves `p` out.  The in-place sums below are for the first kind of pass only; in the others they stand down and autograd gets
+    every contribution as a tensor of its own.  Asked once per (parameter, pass): where an in-place sum is about to be taken (grad_target) and for every weight whose
+    gradient would go to the companion stream (wgrad_companion: each weight of a default-stream backward) — a view node and one engine query per parameter and pass."""
+    tid = _task_id()
+    if tid < 0:      # no pass is running (a direct call): nothing to stand down from
+        return True
+    c = getattr(p, "_dcv_engine", None)
+    if c is not None and c[0] == tid:
+        return c[1]
+    with torch.enable_grad():
+        node = p.view_as(p).grad_fn.next_functions[0][0]
+    try:
+        ok = bool(torch._C._will_engine_execute_node(node))
+    except RuntimeError:      # "a leaf node was passed ... but we are currently running autograd.grad()": the parameter's gradient is being captured
+        ok = False
+    p._dcv_engine = (tid, ok)
+    return ok
+
+
 def grad_target(p):
     """Device pointer of the fp32 tensor this backward's NEXT gradient contribution of parameter `p` must be added to; None if this is the first one.
     (b) an existing .grad; (a) the tensor the first use in the running backward handed to autograd (noted by `note_first`; valid for that graph task only:
-    the engine holds the tensor until the parameter's AccumulateGrad node has run, which is after every use)."""
-    if not isinstance(p, torch.nn.Parameter):
+    the engine holds the tensor until the parameter's AccumulateGrad node has run, which is after every use).  Both only in a pass that ends in p.grad
+    (_engine_accumulates): torch.autograd.grad and backward(inputs=...) get every contribution returned."""
+    if not isinstance(p, torch.nn.Parameter) or not p.requires_grad:      # (a frozen Parameter: whatever is returned for it is dropped, and a .grad it still holds stays as it is)
         return None
     g = p.grad
     if g is not None:
-        if g.dtype == torch.float32 and g.is_cuda and g.is_contiguous() and g.shape == p.shape:
+        if g.dtype == torch.float32 and g.is_cuda and g.is_contiguous() and g.shape == p.shape and _engine_accumulates(p):
             b = getattr(p, "_dcv_bucket", None)      # data parallel: autograd will not visit this parameter's AccumulateGrad node (nothing is returned for it), so
             b = b() if b is not None else None       # the bucket's "a backward has produced gradients" mark is set here instead of by its post-accumulate hook
             if b is not None:
@@ -206,14 +229,14 @@ def grad_target(p):
             return g.data_ptr()
         return None
     a = getattr(p, "_dcv_acc", None)
-    if a is not None and a[0] == _task_id() and a[0] >= 0:
+    if a is not None and a[0] == _task_id() and a[0] >= 0 and _engine_accumulates(p):
         return a[1]
     return None
 
 
 def note_first(p, t) -> None:
     """`t` is the first contribution to p's gradient in the running backward (only its address is kept: an extra reference would make AccumulateGrad clone it)."""
-    if isinstance(p, torch.nn.Parameter) and t is not None and t.is_contiguous():
+    if isinstance(p, torch.nn.Parameter) and p.requires_grad and t is not None and t.is_contiguous():
         p._dcv_acc = (_task_id(), t.data_ptr())
 
 
@@ -265,6 +288,8 @@ def wgrad_companion(device, w, enabled: bool = True):
         return None
     cur = torch.cuda.current_stream(device)
     if cur.cuda_stream != torch.cuda.default_stream(device).cuda_stream:      # the discriminators' lanes already run beside one another
+        return None
+    if not _engine_accumulates(w):      # torch.autograd.grad / backward(inputs=...): the in-place sums stand down (grad_target), so autograd may add two contributions itself
         return None
     s = _side_streams.get(device.index)
     if s is None:
