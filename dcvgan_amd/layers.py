@@ -18,9 +18,6 @@ import torch.nn as nn
 
 from . import ops, ops_cl
 
-import os
-
-_FUSE_BN_STATS = os.environ.get("DCV_NO_BN_FUSION") is None
 # Test instrumentation: when a list is installed here, every fused (Leaky)ReLU appends the branch pattern `y > 0` of
 # its output, in execution order — the pattern the backward kernels differentiate with (tests/test_fullwidth_gpu.py
 # replays it in an fp64 evaluation of the same graph on the host).  None in production: nothing is recorded.
@@ -107,7 +104,7 @@ def run(seq: nn.Sequential, x: torch.Tensor, rng, out=None, grad_slot=None, act_
             # bf16 channels-last data path: the same grouping (conv [+ activation] in one launch), ops_cl's kernels
             fused = _act_of(nxt) if nxt is not None else None
             last = i + (2 if fused is not None else 1) >= n
-            box = [] if (fused is None and isinstance(nxt, _BNS) and nxt.training and _FUSE_BN_STATS) else None
+            box = [] if (fused is None and isinstance(nxt, _BNS) and nxt.training) else None
             _w_eff(layer, x)      # (raises on a marked convolution: spectral normalisation is fp32-path only)
             x = ops_cl.conv(x, layer.weight, geom_of(layer), *(fused or (ops.ACT_NONE, 0.0)), out=out if last else None, grad_slot=grad_slot if i == 0 else None, bn_stats=box,
                             act_slot=act_slot if (last and fused is not None) else None)
@@ -124,7 +121,7 @@ def run(seq: nn.Sequential, x: torch.Tensor, rng, out=None, grad_slot=None, act_
                 _tap(x, fused)
                 i += 2
             else:
-                box = [] if (isinstance(nxt, _BNS) and nxt.training and _FUSE_BN_STATS) else None
+                box = [] if (isinstance(nxt, _BNS) and nxt.training) else None
                 x = ops.conv(x, layer.weight, geom_of(layer), out=out if i + 1 >= n else None, bn_stats=box, grad_slot=grad_slot if i == 0 else None,
                              gate=gate if first_conv else None, w_eff=_w_eff(layer, x))
                 first_conv = False

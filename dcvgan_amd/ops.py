@@ -5,6 +5,7 @@ computation of the G+D step below goes through libdcvgan_hip.so (native.py).
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 from typing import Optional, Tuple
@@ -26,7 +27,19 @@ def _dense(t: torch.Tensor) -> torch.Tensor:
     return t
 
 
-_POISON = bool(int(os.environ.get("DCV_DEBUG_POISON", "0")))
+# --------------------------------------------------------------------------- #
+# Switches, all of this module's in one place.  The first four are read from the environment once, at import: documented opt-outs and debugging aids
+# (INTEGRATION.md lists every variable the package reads).  The rest are test seams: routes that are always on in the product, kept as module
+# attributes because the tests compare each route bit for bit with itself switched off (tests/test_graph_exact_gpu.py, test_grad_accumulation_gpu.py).
+# --------------------------------------------------------------------------- #
+_POISON = bool(int(os.environ.get("DCV_DEBUG_POISON", "0")))      # outputs are NaN-filled before the kernels write them (_empty)
+_USE_PACK_CACHE = os.environ.get("DCV_NO_PACK_CACHE") is None      # packed weights are kept between calls (_PackCache)
+_WGRAD_SIDE = os.environ.get("DCV_NO_WGRAD_SIDE") is None          # weight gradients on the companion stream, both paths (wgrad_companion)
+_HEAD_BN_DEFER = os.environ.get("DCV_NO_HEAD_BN_DEFER") is None    # the colour generator's last BatchNorm leaves its output unwritten (BnLink.defer)
+_SKIP_ACCUMULATE = True       # test seam: a skip tensor's two gradients meet in one slice (GradSlot)
+_GATED_DGRAD = True           # test seam: a data gradient applies its producers' activation derivative (_dgrad_gated_skip, _dgrad_gated_stem)
+_OWN_ACCUMULATION = True      # test seam: later contributions to a parameter's gradient are added by the library's kernels (grad_target); off: by autograd
+_HEAD_BN_FUSION = True        # test seam: the head's data gradient runs fused with the BatchNorm backward in front of it (BnLink)
 
 
 def _empty(shape, device) -> torch.Tensor:
@@ -152,11 +165,6 @@ class _PackCache:
                 e[3] = cur.cuda_stream
 
 
-_USE_PACK_CACHE = os.environ.get("DCV_NO_PACK_CACHE") is None
-_SKIP_ACCUMULATE = os.environ.get("DCV_NO_SKIP_ACCUMULATE") is None
-_GATED_DGRAD = os.environ.get("DCV_NO_GATED_DGRAD") is None
-
-
 def _pack_of(w):
     if not _USE_PACK_CACHE:
         return None
@@ -241,7 +249,10 @@ def note_first(p, t) -> None:
 
 
 def deliver_small(p, t):
-    """A small fp32 gradient `t` of parameter `p` (BatchNorm weight / bias, GRU weights): added in place by dcv_axpby when a target exists, else returned for autograd."""
+    """A small fp32 gradient `t` of parameter `p` (BatchNorm weight / bias, GRU weights): added in place by dcv_axpby when a target exists, else returned for autograd
+    (always, with the library's own sums switched off)."""
+    if not _OWN_ACCUMULATION:
+        return t
     tgt = grad_target(p)
     if tgt is None or not t.is_contiguous():
         note_first(p, t if t.is_contiguous() else None)
@@ -250,8 +261,6 @@ def deliver_small(p, t):
     check(lib().dcv_axpby(ptr(t), C.byref(td), 1.0, C.c_void_p(tgt), C.byref(td), 1.0, C.c_void_p(tgt), C.byref(td), stream_ptr()), "dcv_axpby (gradient accumulation)")
     return None
 
-
-_OWN_ACCUMULATION = os.environ.get("DCV_TORCH_GRAD_ADDS") is None      # DCV_TORCH_GRAD_ADDS=1: leave the sums to autograd (A/B, bit-identity test)
 
 # --------------------------------------------------------------------------- #
 # Weight gradients off the chain (round 5).  Nothing in a backward pass reads a weight gradient, so it need not sit between a layer's data gradient and the next layer's
@@ -267,9 +276,8 @@ _OWN_ACCUMULATION = os.environ.get("DCV_TORCH_GRAD_ADDS") is None      # DCV_TOR
 # hardware queues: 39.15 ms, slower than none), on the same companion (box-dependent: -0.15 ms on one, +0.7 on another), in the G phase only (neutral / +0.7); the
 # companion's launch before the layer's data gradient instead of after it (38.3).  (Round 3 tried a LOW-PRIORITY side stream released by a per-layer event on the fp32 path and
 # lost 0.3-1.2 ms; this form — normal priority, stream-wait on the chain, no per-layer join — wins there too.)
-# DCV_NO_WGRAD_SIDE=1: in-stream, as before, on both paths (DCV_CL_NO_WGRAD_SIDE=1: on the 16-bit path only) — A/B.
+# DCV_NO_WGRAD_SIDE=1: in-stream, as before, on both paths.
 # --------------------------------------------------------------------------- #
-_WGRAD_SIDE = os.environ.get("DCV_NO_WGRAD_SIDE") is None
 _side_streams = {}
 _join_pending = set()
 
@@ -317,7 +325,49 @@ def wgrad_join_at_end(device, cur, side) -> None:
     torch.autograd.Variable._execution_engine.queue_callback(join)
 
 
-_HEAD_BN_FUSION = os.environ.get("DCV_NO_HEAD_BN_FUSION") is None
+def deliver_wgrad(w, x, dy, device, launch, side_enabled: bool = True):
+    """The weight gradient of one convolution of parameter `w`, for both data paths: returns the tensor for autograd, or None when it was added into one that already
+    holds this parameter's gradient.  `launch(dst, accumulate)` is the caller's: it takes its workspace and issues its own entry point (plain, _acc, _bn, dcv_cl*) on
+    the stream that is current when it is called, writing (accumulate = 0) or adding to (1) the fp32 tensor of w's shape at `dst`.  `x`, `dy`: the operands it reads,
+    kept alive for the companion stream.  Data parallel: the first weight gradient of a backward is written straight into the parameter's slice of its bucket's flat
+    buffer (optim.GradBucket; autograd adopts the returned tensor as .grad), whatever _OWN_ACCUMULATION says."""
+    side = wgrad_companion(device, w, side_enabled)
+    if side is None:
+        return _wgrad_here(w, launch)
+    cur = torch.cuda.current_stream(device)      # the main chain's weight gradient on the companion stream (above)
+    side.wait_stream(cur)
+    for t in (x, dy):
+        t.record_stream(side)
+    with torch.cuda.stream(side):
+        dw = _wgrad_here(w, launch)
+    wgrad_join_at_end(device, cur, side)
+    return dw
+
+
+# identity token of the current backward pass: a weight's gradient slot is handed out once per backward (new_backward_epoch() is called by
+# the optimiser wrapper's step(), i.e. between two backwards of the same bucket)
+_epoch = [object()]
+
+
+def _wgrad_here(w, launch):
+    """deliver_wgrad on the current stream: the destination — the tensor that already holds this parameter's gradient, else its bucket slot, else a fresh tensor."""
+    tgt = grad_target(w) if _OWN_ACCUMULATION else None
+    if tgt is not None:      # a later contribution (second use in this backward, or .grad from an earlier backward): the slab reduce adds into the tensor that holds the first
+        launch(C.c_void_p(tgt), 1)
+        return None
+    slot = getattr(w, "_dcv_grad_slot", None)
+    if slot is not None and w.grad is None and getattr(w, "_dcv_slot_epoch", None) is not _epoch[0]:
+        w._dcv_slot_epoch = _epoch[0]
+        b = getattr(w, "_dcv_bucket", None)
+        if b is not None and b() is not None:
+            b().before_slot_write(w)      # a collective of the previous backward may still be reading this slice (GradBucket(overlap=True))
+        dw = slot.detach()
+    else:      # (also the second use of a slotted weight in one backward with the library's sums switched off: a tensor of its own, which autograd adds)
+        dw = _empty(w.shape, w.device)
+    launch(ptr(dw), 0)
+    if _OWN_ACCUMULATION:
+        note_first(w, dw)
+    return dw
 
 
 class BnLink:
@@ -325,7 +375,7 @@ class BnLink:
     UpBlock 5 -> cat with the stem's skip -> Outconv): `bn_act(..., link=)` notes what its backward needs, `conv(..., bn_link=)`'s backward then runs
     dcv_conv_backward_data_bn — the data gradient fused with that BatchNorm's backward — and leaves the BatchNorm's results here; the BatchNorm node of the SAME
     backward pass picks them up instead of reading its cotangent (whose memory the fused kernels never wrote).  Anything the fused entry point does not take
-    (another geometry, eval mode, a dropout mask, the 16-bit path) leaves the link empty and both nodes run as they always did.  DCV_NO_HEAD_BN_FUSION=1: off (A/B)."""
+    (another geometry, eval mode, a dropout mask, the 16-bit path) leaves the link empty and both nodes run as they always did."""
     __slots__ = ("x", "gamma", "beta", "stats", "act", "slope", "task", "dx", "dgb", "stream", "defer", "deferred", "out", "_keep")
 
     def __init__(self, defer: bool = False):
@@ -334,7 +384,7 @@ class BnLink:
         # `defer`: the BatchNorm group may leave its OUTPUT unwritten (statistics only) — the linked convolution's forward and weight gradient then read the BatchNorm
         # input and normalise + activate on load (dcv_conv_forward_bn / dcv_conv_backward_weight_bn); `deferred`: it did.  Only the caller knows that nothing else
         # reads that output (the generator: the up-path slice of the last concat buffer feeds the head alone)
-        self.defer, self.deferred = bool(defer) and _HEAD_BN_FUSION and os.environ.get("DCV_NO_HEAD_BN_DEFER") is None, False
+        self.defer, self.deferred = bool(defer) and _HEAD_BN_FUSION and _HEAD_BN_DEFER, False
 
     def view_args(self):
         """The (cbn, bn_x, dims, gamma, beta, mean, invstd, act, slope) tail of the *_bn entry points."""
@@ -343,11 +393,84 @@ class BnLink:
         return (self.x.shape[1], ptr(self.x), C.byref(bxd), ptr(self.gamma), ptr(self.beta), ptr(self.stats[0]), ptr(self.stats[1]), self.act, self.slope)
 
 
-class _Conv(Function):
-    # identity token of the current backward pass: a weight's gradient slot is handed out once per backward (new_backward_epoch() is called by
-    # the optimiser wrapper's step(), i.e. between two backwards of the same bucket)
-    _epoch = [object()]
+# --------------------------------------------------------------------------- #
+# The routes of a convolution's data gradient, shared by _Conv.backward and ops_cl._ConvCl.backward.  Each states its own precondition, launches through the
+# CALLING module's entry points and returns whether it ran (an entry point that answers DCV_EUNSUPPORTED launched nothing: the next route is tried).  A backward
+# tries them in the order they stand here; the first that runs is the data gradient.
+# --------------------------------------------------------------------------- #
+# One data-gradient call as the routes see it.  `fn(name)`: the calling module's entry point `<prefix><name>` (dcv_* here, dcv_cl_* / dcv_clf16_* in ops_cl);
+# `head`: the leading arguments every data-gradient entry of that path takes (geometry, dy, the weights or their packed tiles, dx); `tail`: the trailing ones in
+# front of the stream ([pack,] workspace).  `into`: the skip tensor's gradient slice that dx IS (the route accumulates), or None (dx is a fresh tensor).
+_Dgrad = collections.namedtuple("_Dgrad", "fn prefix g x dx dxd into head tail")
 
+
+def _fn(name: str):
+    """This module's entry point `dcv_<name>` (ops_cl._fn is its counterpart)."""
+    return getattr(lib(), "dcv_" + name)
+
+
+def _dgrad_bn_fused(d, link):
+    """The first channels of x are the output of a BatchNorm group that ran on this stream (BnLink), x is the whole input of a transposed convolution and no skip slice:
+    the data gradient fused with that BatchNorm's backward, whose results wait in the link for the BatchNorm's own node."""
+    x = d.x
+    if link is None or link.x is None or d.into is not None or not d.g.transposed or link.x.shape[0] != x.shape[0] or link.x.shape[2:] != x.shape[2:] \
+            or link.x.shape[1] >= x.shape[1] or torch.cuda.current_stream(x.device).cuda_stream != link.stream:
+        return False
+    bx = link.x
+    cbn = bx.shape[1]
+    bdx = _empty(bx.shape, bx.device)
+    dgb = _empty((2, cbn), bx.device)
+    bxd, bdxd = dims5(bx), dims5(bdx)
+    ws2p, ws2n = _ws("headbn", d.fn("conv_backward_data_bn_workspace_bytes")(C.byref(d.dxd), cbn), x.device)
+    fused = C.c_int(0)
+    rc = d.fn("conv_backward_data_bn")(*d.head, *d.tail, cbn, ptr(bx), C.byref(bxd), ptr(link.gamma), ptr(link.beta), ptr(link.stats[0]), ptr(link.stats[1]),
+                                       link.act, link.slope, ptr(bdx), C.byref(bdxd), ptr(dgb[0]), ptr(dgb[1]), ws2p, ws2n, C.byref(fused), stream_ptr())
+    if rc == N.DCV_EUNSUPPORTED:
+        return False
+    check(rc, d.prefix + "conv_backward_data_bn")
+    if fused.value:
+        link.dx, link.dgb, link.task = bdx, dgb, _task_id()
+    return True
+
+
+def _dgrad_gated(d, accumulate, src, act):
+    """dcv_conv_backward_data_gated: the data gradient times the derivative of the activation `act` = (code, slope) that produced `src`, read off `src`."""
+    sd = dims5(src)
+    rc = d.fn("conv_backward_data_gated")(*d.head, accumulate, ptr(src), C.byref(sd), act[0], act[1], *d.tail, stream_ptr())
+    if rc == N.DCV_EUNSUPPORTED:
+        return False
+    check(rc, d.prefix + "conv_backward_data_gated")
+    return True
+
+
+def _dgrad_gated_skip(d, slot):
+    """x is a skip tensor written by a conv + (Leaky)ReLU (`slot.act`), and its gradient slice `into` — laid out as x is — already holds the concat's share: accumulate
+    into the slice and apply the activation's derivative, read off x, in the same epilogue.  The producer then skips its own derivative pass."""
+    if d.into is None or slot.act is None or not _GATED_DGRAD or tuple(d.x.stride()) != tuple(d.into.stride()) or not _dgrad_gated(d, 1, d.x, slot.act):
+        return False
+    slot.act_applied = 1
+    return True
+
+
+def _dgrad_gated_stem(d, gate):
+    """x is (a noisy copy of) a discriminator's concat buffer `gate[0]` — laid out as dx is — whose two halves are conv + LeakyReLU stems (discriminator.py:122-124),
+    and no skip slice: the stems' activation derivative, read off the buffer, in this data gradient's epilogue.  Both stems then skip their own derivative passes."""
+    if gate is None or d.into is not None:
+        return False
+    gbuf, gslot = gate
+    if gslot.act is None or tuple(gbuf.shape) != tuple(d.dx.shape) or tuple(gbuf.stride()) != tuple(d.dx.stride()) or not _dgrad_gated(d, 0, gbuf, gslot.act):
+        return False
+    gslot.act_applied = 2
+    return True
+
+
+def _dgrad_plain(d):
+    """Always: dcv_conv_backward_data, accumulating when dx is a skip tensor's gradient slice."""
+    check(d.fn("conv_backward_data")(*d.head, int(d.into is not None), *d.tail, stream_ptr()), d.prefix + "conv_backward_data")
+    return True
+
+
+class _Conv(Function):
     @staticmethod
     def forward(ctx, x, w, g: ConvGeom, act: int, slope: float, out=None, bn_stats=None, grad_slot=None, act_slot=None, bn_link=None, gate=None, w_eff=None):
         N._require(x, "conv input"); N._require(w, "conv weight")
@@ -366,7 +489,7 @@ class _Conv(Function):
         ctx.bn_link = bn_link if _HEAD_BN_FUSION else None
         ctx.act_slot = act_slot if (act_slot is not None and act == ACT_LEAKY) else None
         if ctx.act_slot is not None:
-            ctx.act_slot.act, ctx.act_slot.act_applied = (act, slope), False
+            ctx.act_slot.produced_with(act, slope)
         if x.shape[1] != g.cin:
             raise N.NativeError(f"conv: input has {x.shape[1]} channels, module expects {g.cin}")
         if not w.is_contiguous():
@@ -427,10 +550,7 @@ class _Conv(Function):
         g = ctx.g
         L = lib()
         dy = _dense(dy)
-        fused_away = ctx.act_slot is not None and bool(ctx.act_slot.act_applied)    # the consumer's data gradient already applied act'
-        if ctx.act_slot is not None:
-            ctx.act_slot.act_applied = max(0, int(ctx.act_slot.act_applied) - 1)      # (a count: a discriminator's two stems share one buffer and one consumer)
-        if ctx.act != ACT_NONE and not fused_away:
+        if ctx.act != ACT_NONE and not (ctx.act_slot is not None and ctx.act_slot.skip_act()):      # (skipped: the consumer's data gradient already applied act')
             dz = _empty(y.shape, y.device)
             dyd, yd, dzd = dims5(dy), dims5(y), dims5(dz)   # y may be a strided concat-buffer slice; dz is dense
             check(L.dcv_act_backward(ptr(dy), C.byref(dyd), ptr(y), C.byref(yd), ptr(dz), C.byref(dzd), ctx.act, ctx.slope, stream_ptr()), "dcv_act_backward")
@@ -449,117 +569,30 @@ class _Conv(Function):
             wsp, wsn = _ws("conv", need, x.device)
             pk = ctx.pack.get(wv, 1, g, dx, dy, dxd, dyd) if ctx.pack is not None else None
             pkp = C.byref(pk) if pk is not None else None
-            rc = N.DCV_EUNSUPPORTED
-            link = ctx.bn_link
-            if link is not None and link.x is not None and into is None and g.transposed and link.x.shape[0] == x.shape[0] and link.x.shape[2:] == x.shape[2:] \
-                    and link.x.shape[1] < x.shape[1] and torch.cuda.current_stream(x.device).cuda_stream == link.stream:      # (the BatchNorm ran on this stream too)
-                # the first channels of x are a BatchNorm group's output: the data gradient fused with that BatchNorm's backward (BnLink)
-                bx = link.x
-                cbn = bx.shape[1]
-                bdx = _empty(bx.shape, bx.device)
-                dgb = _empty((2, cbn), bx.device)
-                bxd, bdxd = dims5(bx), dims5(bdx)
-                need2 = L.dcv_conv_backward_data_bn_workspace_bytes(C.byref(dxd), cbn)
-                ws2p, ws2n = _ws("headbn", need2, x.device)
-                fused = C.c_int(0)
-                rc = L.dcv_conv_backward_data_bn(C.byref(g), ptr(dy), C.byref(dyd), ptr(wv), ptr(dx), C.byref(dxd), pkp, wsp, wsn, cbn, ptr(bx), C.byref(bxd),
-                                                 ptr(link.gamma), ptr(link.beta), ptr(link.stats[0]), ptr(link.stats[1]), link.act, link.slope,
-                                                 ptr(bdx), C.byref(bdxd), ptr(dgb[0]), ptr(dgb[1]), ws2p, ws2n, C.byref(fused), stream_ptr())
-                if rc == N.DCV_EUNSUPPORTED:
-                    pass                      # (nothing ran: the plain call below)
-                else:
-                    check(rc, "dcv_conv_backward_data_bn")
-                    if fused.value:
-                        link.dx, link.dgb, link.task = bdx, dgb, _task_id()
-            if rc == N.DCV_EUNSUPPORTED and into is not None and slot.act is not None and _GATED_DGRAD and tuple(x.stride()) == tuple(into.stride()):
-                # ... and the derivative of the activation that produced x, read off x, in the same epilogue
-                xd_ = dims5(x)
-                rc = L.dcv_conv_backward_data_gated(C.byref(g), ptr(dy), C.byref(dyd), ptr(wv), ptr(dx), C.byref(dxd), 1, ptr(x), C.byref(xd_),
-                                                    slot.act[0], slot.act[1], pkp, wsp, wsn, stream_ptr())
-                if rc == 0:
-                    slot.act_applied = True
-                elif rc != N.DCV_EUNSUPPORTED:
-                    check(rc, "dcv_conv_backward_data_gated")
-            if rc == N.DCV_EUNSUPPORTED and ctx.gate is not None and into is None:
-                # x is (a noisy copy of) a discriminator's concat buffer whose two halves are conv + LeakyReLU stems (discriminator.py:122-124): the stems'
-                # activation derivative, read off the buffer, in this data gradient's epilogue — the stems then skip their own derivative passes
-                gbuf, gslot = ctx.gate
-                if gslot.act is not None and tuple(gbuf.shape) == tuple(dx.shape) and tuple(gbuf.stride()) == tuple(dx.stride()):
-                    gd_ = dims5(gbuf)
-                    rc = L.dcv_conv_backward_data_gated(C.byref(g), ptr(dy), C.byref(dyd), ptr(wv), ptr(dx), C.byref(dxd), 0, ptr(gbuf), C.byref(gd_),
-                                                        gslot.act[0], gslot.act[1], pkp, wsp, wsn, stream_ptr())
-                    if rc == 0:
-                        gslot.act_applied = 2
-                    elif rc != N.DCV_EUNSUPPORTED:
-                        check(rc, "dcv_conv_backward_data_gated")
-            if rc == N.DCV_EUNSUPPORTED:
-                check(L.dcv_conv_backward_data(C.byref(g), ptr(dy), C.byref(dyd), ptr(wv), ptr(dx), C.byref(dxd), int(into is not None),
-                                               pkp, wsp, wsn, stream_ptr()), "dcv_conv_backward_data")
+            d = _Dgrad(_fn, "dcv_", g, x, dx, dxd, into, (C.byref(g), ptr(dy), C.byref(dyd), ptr(wv), ptr(dx), C.byref(dxd)), (pkp, wsp, wsn))
+            # (the routes in order: the first that runs is the data gradient)
+            _dgrad_bn_fused(d, ctx.bn_link) or _dgrad_gated_skip(d, slot) or _dgrad_gated_stem(d, ctx.gate) or _dgrad_plain(d)
             _PackCache.commit(pk)
             if into is not None:
                 dx = None
-        side = wgrad_companion(x.device, w) if ctx.needs_input_grad[1] else None
-        if side is not None:      # the main chain's weight gradient on the companion stream (above)
-            cur = torch.cuda.current_stream(x.device)
-            side.wait_stream(cur)
-            for t in (x, dy):
-                t.record_stream(side)
-            with torch.cuda.stream(side):
-                need = L.dcv_conv_workspace_bytes(C.byref(g), C.byref(xd), C.byref(dyd), 2)
-                wsp, wsn = _ws("conv", need, x.device)
-                tgt = grad_target(w)
+        if ctx.needs_input_grad[1]:
+            def launch(dst, accumulate):
+                wsp, wsn = _ws("conv", L.dcv_conv_workspace_bytes(C.byref(g), C.byref(xd), C.byref(dyd), 2), x.device)
                 if ctx.bn_deferred:      # the operand's first channels exist only as the BatchNorm input: normalise on load
-                    if tgt is None:
-                        dw = _empty(w.shape, w.device)
-                    check(L.dcv_conv_backward_weight_bn(C.byref(g), ptr(x), C.byref(xd), ptr(dy), C.byref(dyd), C.c_void_p(tgt) if tgt is not None else ptr(dw),
-                                                        int(tgt is not None), wsp, wsn, *ctx.bn_link.view_args(), stream_ptr()), "dcv_conv_backward_weight_bn")
-                    if tgt is None:
-                        note_first(w, dw)
-                elif tgt is not None:
-                    check(L.dcv_conv_backward_weight_acc(C.byref(g), ptr(x), C.byref(xd), ptr(dy), C.byref(dyd), C.c_void_p(tgt), 1, wsp, wsn, stream_ptr()),
+                    check(L.dcv_conv_backward_weight_bn(C.byref(g), ptr(x), C.byref(xd), ptr(dy), C.byref(dyd), dst, accumulate, wsp, wsn,
+                                                        *ctx.bn_link.view_args(), stream_ptr()), "dcv_conv_backward_weight_bn")
+                elif accumulate:
+                    check(L.dcv_conv_backward_weight_acc(C.byref(g), ptr(x), C.byref(xd), ptr(dy), C.byref(dyd), dst, 1, wsp, wsn, stream_ptr()),
                           "dcv_conv_backward_weight_acc")
                 else:
-                    dw = _empty(w.shape, w.device)
-                    check(L.dcv_conv_backward_weight(C.byref(g), ptr(x), C.byref(xd), ptr(dy), C.byref(dyd), ptr(dw), wsp, wsn, stream_ptr()), "dcv_conv_backward_weight")
-                    note_first(w, dw)
-            wgrad_join_at_end(x.device, cur, side)
-        elif ctx.needs_input_grad[1]:
-            # data parallel: the parameter's slice of its bucket's flat gradient buffer (optim.GradBucket) — the first weight gradient of a
-            # backward is written straight into it (autograd adopts the returned tensor as .grad); a second use of the same weight in one
-            # backward (D on the real and the fake batch) gets a tensor of its own, which autograd adds
-            need = L.dcv_conv_workspace_bytes(C.byref(g), C.byref(xd), C.byref(dyd), 2)
-            wsp, wsn = _ws("conv", need, x.device)
-            tgt = grad_target(w) if _OWN_ACCUMULATION else None
-            if ctx.bn_deferred:
-                if tgt is None:
-                    dw = _empty(w.shape, w.device)
-                check(L.dcv_conv_backward_weight_bn(C.byref(g), ptr(x), C.byref(xd), ptr(dy), C.byref(dyd), C.c_void_p(tgt) if tgt is not None else ptr(dw),
-                                                    int(tgt is not None), wsp, wsn, *ctx.bn_link.view_args(), stream_ptr()), "dcv_conv_backward_weight_bn")
-                if tgt is None and _OWN_ACCUMULATION:
-                    note_first(w, dw)
-            elif tgt is not None:
-                # a later contribution (second use in this backward, or .grad from an earlier backward): the slab reduce adds into the tensor that holds the first
-                check(L.dcv_conv_backward_weight_acc(C.byref(g), ptr(x), C.byref(xd), ptr(dy), C.byref(dyd), C.c_void_p(tgt), 1, wsp, wsn, stream_ptr()),
-                      "dcv_conv_backward_weight_acc")
-            else:
-                slot = getattr(w, "_dcv_grad_slot", None)
-                if slot is not None and w.grad is None and getattr(w, "_dcv_slot_epoch", None) is not _Conv._epoch[0]:
-                    w._dcv_slot_epoch = _Conv._epoch[0]
-                    b = getattr(w, "_dcv_bucket", None)
-                    if b is not None and b() is not None:
-                        b().before_slot_write(w)      # a collective of the previous backward may still be reading this slice (GradBucket(overlap=True))
-                    dw = slot.detach()
-                else:
-                    dw = _empty(w.shape, w.device)
-                check(L.dcv_conv_backward_weight(C.byref(g), ptr(x), C.byref(xd), ptr(dy), C.byref(dyd), ptr(dw), wsp, wsn, stream_ptr()), "dcv_conv_backward_weight")
-                if _OWN_ACCUMULATION:
-                    note_first(w, dw)
+                    check(L.dcv_conv_backward_weight(C.byref(g), ptr(x), C.byref(xd), ptr(dy), C.byref(dyd), dst, wsp, wsn, stream_ptr()), "dcv_conv_backward_weight")
+            dw = deliver_wgrad(w, x, dy, x.device, launch)
         return dx, dw, None, None, None, None, None, None, None, None, None, None
 
 
 def new_backward_epoch():
     """Called when the gradients of the last backward have been consumed (optimiser step): weight-gradient slots may be handed out again."""
-    _Conv._epoch[0] = object()
+    _epoch[0] = object()
 
 
 def conv(x, w, g: ConvGeom, act: int = ACT_NONE, slope: float = 0.0, out=None, bn_stats=None, grad_slot=None, act_slot=None, bn_link=None, gate=None, w_eff=None):
@@ -627,9 +660,7 @@ class _BnAct(Function):
             # the consumer convolution's backward has already done this node's work (dcv_conv_backward_data_bn); dy's memory was never written
             dx, dgb = link.dx, link.dgb
             link.dx = link.dgb = None
-            if _OWN_ACCUMULATION:
-                return (dx, deliver_small(gamma, dgb[0]), deliver_small(beta, dgb[1])) + (None,) * 12
-            return (dx, dgb[0], dgb[1]) + (None,) * 12
+            return (dx, deliver_small(gamma, dgb[0]), deliver_small(beta, dgb[1])) + (None,) * 12
         L = lib()
         dy = _dense(dy)
         Cn = x.shape[1]
@@ -640,9 +671,7 @@ class _BnAct(Function):
         check(L.dcv_bn_act_backward(ptr(dy), C.byref(dyd), ptr(x), C.byref(xd), ptr(dx), C.byref(dxd), ptr(gamma), ptr(beta),
                                     ptr(stats[0]), ptr(stats[1]), ptr(mask), int(training), act, slope, ptr(dgb[0]), ptr(dgb[1]), wsp, wsn, stream_ptr()),
               "dcv_bn_act_backward")
-        if _OWN_ACCUMULATION:
-            return (dx, deliver_small(gamma, dgb[0]), deliver_small(beta, dgb[1])) + (None,) * 12
-        return (dx, dgb[0], dgb[1]) + (None,) * 12
+        return (dx, deliver_small(gamma, dgb[0]), deliver_small(beta, dgb[1])) + (None,) * 12
 
 
 def bn_act(x, gamma, beta, running_mean, running_var, training: bool, act: int = ACT_NONE, slope: float = 0.0,
@@ -701,9 +730,7 @@ class _SyncBnAct(Function):
         group.exchange(rows)
         check(L.dcv_bn_sync_backward_apply(ptr(dy), C.byref(dyd), ptr(x), C.byref(xd), ptr(dx), C.byref(dxd), ptr(gamma), ptr(beta), ptr(stats[0]), ptr(stats[1]), ptr(mask),
                                            act, slope, ptr(rows), group.world, group.rank, ptr(dgb[0]), ptr(dgb[1]), wsp, wsn, stream_ptr()), "dcv_bn_sync_backward_apply")
-        if _OWN_ACCUMULATION:
-            return (dx, deliver_small(gamma, dgb[0]), deliver_small(beta, dgb[1])) + (None,) * 13
-        return (dx, dgb[0], dgb[1]) + (None,) * 13
+        return (dx, deliver_small(gamma, dgb[0]), deliver_small(beta, dgb[1])) + (None,) * 13
 
 
 def sync_bn_act(x, gamma, beta, running_mean, running_var, training: bool, act: int = ACT_NONE, slope: float = 0.0,
@@ -873,11 +900,23 @@ class GradSlot:
 
     def __init__(self):
         self.g = None
-        # set by the conv + (Leaky)ReLU that PRODUCED the skip tensor (ops.conv(..., act_slot=)): its activation, whose
-        # derivative the consumer's data gradient can apply from the tensor itself (dcv_conv_backward_data_gated) — the
-        # producer then skips its own derivative pass (act_applied)
+        # set by the conv + (Leaky)ReLU that PRODUCED the skip tensor (conv(..., act_slot=), either path): its activation, whose
+        # derivative the consumer's data gradient can apply from the tensor itself (dcv_conv_backward_data_gated)
         self.act = None
+        # how many producers' backwards may still skip their own derivative pass: set by the consumer's data gradient when it has applied the derivative
+        # (1: _dgrad_gated_skip; 2: _dgrad_gated_stem, a discriminator's two stems share one buffer and one consumer), taken off by each producer's
+        # backward (skip_act).  An empty count is written False, which counts as 0: tests/test_graph_exact_gpu.py asserts that identity after a forward
         self.act_applied = False
+
+    def produced_with(self, act, slope) -> None:
+        """A producer's forward: its activation; nothing has applied the derivative yet."""
+        self.act, self.act_applied = (act, slope), False
+
+    def skip_act(self) -> bool:
+        """A producer's backward: take one off the count; True if there was one to take."""
+        n = self.act_applied
+        self.act_applied = max(0, n - 1)
+        return n > 0
 
     def take(self, x):
         g, self.g = self.g, None
@@ -1108,8 +1147,6 @@ class _GruSeq(Function):
         check(L.dcv_gru_backward(ptr(dout), ptr(e), ptr(h0), ptr(out), ptr(gates), ptr(w_ih), ptr(w_hh), ptr(dw_ih), ptr(dw_hh), ptr(db_ih), ptr(db_hh),
                                  T, B, dm, wsp, wsn, stream_ptr()), "dcv_gru_backward")
         # second and later contributions (the dead D-phase backward adds to the last G phase's gradients) by dcv_axpby, not by autograd's torch add
-        if not _OWN_ACCUMULATION:
-            return None, None, dw_ih, dw_hh, db_ih, db_hh
         return (None, None) + tuple(deliver_small(p, t) for p, t in zip((w_ih, w_hh, b_ih, b_hh), (dw_ih, dw_hh, db_ih, db_hh)))
 
 

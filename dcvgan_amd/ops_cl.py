@@ -15,12 +15,13 @@ import torch
 from torch.autograd import Function
 
 from . import native as N
+from . import ops as _o
 from .native import ACT_LEAKY, ACT_NONE, ConvGeom, check, dims5, lib, ptr, stream_ptr
-import os
-
 from .ops import _Opaque, _Out, _out_shape, _ws
 
-_FUSE_BN_STATS = os.environ.get("DCV_NO_BN_FUSION") is None
+# Test seams (no environment reads here): routes that are always on in the product, kept as attributes because the tests compare each with itself switched off.
+_WGRAD_SIDE = True      # weight gradients on the companion stream (ops.wgrad_companion; DCV_NO_WGRAD_SIDE=1 turns it off on both paths)
+_TWINS = True           # an fp32 boundary tensor carries its CL16 source (twin_of)
 
 BF16 = torch.bfloat16
 _ENABLED = [False]
@@ -132,8 +133,7 @@ class _FromF32(Function):
 # A module's fp32 output is the conversion of a CL16 tensor, and the next module converts it straight back (generator frames -> colour generator -> discriminators): the
 # fp32 tensor carries its source as `_dcv_cl_twin`, `from_f32` hands that out instead of converting, and the gradient flows from the consumer into the producer's
 # tape without the fp32 detour either (bf16 -> fp32 -> bf16 is the identity, so the forward values are the same bits).  Views made at the boundary (frames -> video)
-# carry the twin through `carry_twin`.  The fp32 tensor itself stays what the caller sees and what slicing / fp32 ops read.  DCV_CL_NO_TWINS=1: always convert (A/B).
-_TWINS = os.environ.get("DCV_CL_NO_TWINS") is None
+# carry the twin through `carry_twin`.  The fp32 tensor itself stays what the caller sees and what slicing / fp32 ops read.  (_TWINS off: always convert.)
 
 
 def twin_of(x: torch.Tensor):
@@ -287,7 +287,7 @@ class _ConvCl(Function):
         # this conv + (Leaky)ReLU writes a skip tensor (second slice of a concat buffer): the consumer's data gradient may apply the derivative (ops.GradSlot)
         ctx.act_slot = act_slot if (act_slot is not None and act == ACT_LEAKY) else None
         if ctx.act_slot is not None:
-            ctx.act_slot.act, ctx.act_slot.act_applied = (act, slope), False
+            ctx.act_slot.produced_with(act, slope)
         if x.shape[1] != g.cin:
             raise N.NativeError(f"conv: input has {x.shape[1]} channels, module expects {g.cin}")
         shape = _out_shape(g, x)
@@ -299,7 +299,7 @@ class _ConvCl(Function):
         xd, yd = dims5(x), dims5(y)
         pk = _packed(w, 0, g, xd, yd, tuple(x.shape))
         wsp, wsn = _ws("clconv", _fn("conv_workspace_bytes")(C.byref(g), C.byref(xd), C.byref(yd), 0), x.device)
-        sbytes = _fn("conv_stats_bytes")(C.byref(g), C.byref(xd), C.byref(yd)) if (bn_stats is not None and act == ACT_NONE and _FUSE_BN_STATS) else 0
+        sbytes = _fn("conv_stats_bytes")(C.byref(g), C.byref(xd), C.byref(yd)) if (bn_stats is not None and act == ACT_NONE) else 0
         if sbytes:
             # conv -> BatchNorm pair: the epilogue leaves per-tile {sum, sum^2} of the stored bf16 values, the BatchNorm op skips its statistics pass over y
             stat = torch.empty(sbytes // 4, dtype=torch.float32, device=x.device)
@@ -321,10 +321,7 @@ class _ConvCl(Function):
         g = ctx.g
         L = lib()
         dy = as_cl(dy)
-        fused_away = ctx.act_slot is not None and ctx.act_slot.act_applied      # the consumer's data gradient already applied act' (gated epilogue)
-        if ctx.act_slot is not None:
-            ctx.act_slot.act_applied = False
-        if ctx.act != ACT_NONE and not fused_away:
+        if ctx.act != ACT_NONE and not (ctx.act_slot is not None and ctx.act_slot.skip_act()):      # (skipped: the consumer's data gradient already applied act')
             dy = _ew(3 if ctx.act == ACT_LEAKY else 4, dy, y, ctx.slope)
         xd, dyd = dims5(x), dims5(dy)
         dx = dw = None
@@ -339,72 +336,25 @@ class _ConvCl(Function):
             dxd = dims5(dx)
             pk = _packed(w, 1, g, dxd, dyd, tuple(x.shape))
             wsp, wsn = _ws("clconv", _fn("conv_workspace_bytes")(C.byref(g), C.byref(dxd), C.byref(dyd), 1), x.device)
-            rc = N.DCV_EUNSUPPORTED
-            from . import ops as _o2
-            if into is not None and slot.act is not None and _o2._GATED_DGRAD and tuple(x.stride()) == tuple(into.stride()):
-                # ... and the derivative of the activation that produced x, read off x, in the same epilogue (Inconv -> DownBlock 0)
-                xgd = dims5(x)
-                rc = _fn("conv_backward_data_gated")(C.byref(g), ptr(dy), C.byref(dyd), ptr(pk), ptr(dx), C.byref(dxd), 1, ptr(x), C.byref(xgd),
-                                                       slot.act[0], slot.act[1], wsp, wsn, stream_ptr())
-                if rc == 0:
-                    slot.act_applied = True
-                elif rc != N.DCV_EUNSUPPORTED:
-                    check(rc, "dcv_cl_conv_backward_data_gated")
-            if rc == N.DCV_EUNSUPPORTED:
-                check(_fn("conv_backward_data")(C.byref(g), ptr(dy), C.byref(dyd), ptr(pk), ptr(dx), C.byref(dxd), int(into is not None), wsp, wsn, stream_ptr()),
-                      "dcv_cl_conv_backward_data")
+            # the routes are the fp32 path's (ops._dgrad_*): the skip's gradient with the derivative of the activation that produced x in the same epilogue
+            # (Inconv -> DownBlock 0), else the plain data gradient
+            d = _o._Dgrad(_fn, "dcv_cl_", g, x, dx, dxd, into, (C.byref(g), ptr(dy), C.byref(dyd), ptr(pk), ptr(dx), C.byref(dxd)), (wsp, wsn))
+            _o._dgrad_gated_skip(d, slot) or _o._dgrad_plain(d)
             if into is not None:
                 dx = None
         if ctx.needs_input_grad[1]:
-            dw = _wgrad_on_side(g, x, xd, dy, dyd, w)
+            def launch(dst, accumulate):
+                need = _fn("wgrad_workspace_bytes")(C.byref(g), C.byref(xd), C.byref(dyd))
+                if need == 0:
+                    raise N.NativeError("dcv_cl_wgrad_workspace_bytes: " + L.dcv_last_error().decode())
+                wsp, wsn = _ws("clconv", need, x.device)
+                if accumulate:
+                    check(_fn("conv_backward_weight_acc")(C.byref(g), ptr(x), C.byref(xd), ptr(dy), C.byref(dyd), dst, 1, wsp, wsn, stream_ptr()),
+                          "dcv_cl_conv_backward_weight_acc")
+                else:
+                    check(_fn("conv_backward_weight")(C.byref(g), ptr(x), C.byref(xd), ptr(dy), C.byref(dyd), dst, wsp, wsn, stream_ptr()), "dcv_cl_conv_backward_weight")
+            dw = _o.deliver_wgrad(w, x, dy, x.device, launch, _WGRAD_SIDE)      # (on the chain stream's companion where that is allowed, as on the fp32 path)
         return dx, dw, None, None, None, None, None, None, None
-
-
-def _wgrad_on_side(g, x, xd, dy, dyd, w):
-    """The layer's weight gradient: on the chain stream's companion where that is allowed (below), else in place."""
-    need = _fn("wgrad_workspace_bytes")(C.byref(g), C.byref(xd), C.byref(dyd))
-    if need == 0:
-        raise N.NativeError("dcv_cl_wgrad_workspace_bytes: " + lib().dcv_last_error().decode())
-    from . import ops as _o
-    side = _o.wgrad_companion(x.device, w, _WGRAD_SIDE)
-    if side is None:
-        return _wgrad_cl(g, x, xd, dy, dyd, w, need)
-    cur = torch.cuda.current_stream(x.device)
-    side.wait_stream(cur)
-    for t in (x, dy):
-        t.record_stream(side)
-    with torch.cuda.stream(side):
-        dw = _wgrad_cl(g, x, xd, dy, dyd, w, need)
-    _o.wgrad_join_at_end(x.device, cur, side)
-    return dw
-
-
-# Weight gradients off the chain: ops.wgrad_companion (the main stream's backward hands them to one companion stream; same kernels, bit-identical results).
-_WGRAD_SIDE = os.environ.get("DCV_CL_NO_WGRAD_SIDE") is None      # (DCV_NO_WGRAD_SIDE=1 turns it off on both paths)
-
-
-def _wgrad_cl(g, x, xd, dy, dyd, w, need):
-    """The weight gradient of one CL16 convolution on the CURRENT stream: returns the tensor for autograd, or None when it was added into an existing target."""
-    from . import ops as _o
-    wsp, wsn = _ws("clconv", need, x.device)
-    tgt = _o.grad_target(w) if _o._OWN_ACCUMULATION else None
-    if tgt is not None:      # a later contribution to this parameter's gradient: added by the slab reduce (ops.grad_target), nothing for autograd to sum
-        check(_fn("conv_backward_weight_acc")(C.byref(g), ptr(x), C.byref(xd), ptr(dy), C.byref(dyd), C.c_void_p(tgt), 1, wsp, wsn, stream_ptr()),
-              "dcv_cl_conv_backward_weight_acc")
-        return None
-    slot = getattr(w, "_dcv_grad_slot", None)       # data parallel: the parameter's slice of its bucket's flat buffer (optim.GradBucket), as on the fp32 path
-    if slot is not None and w.grad is None and getattr(w, "_dcv_slot_epoch", None) is not _o._Conv._epoch[0] and _o._OWN_ACCUMULATION:
-        w._dcv_slot_epoch = _o._Conv._epoch[0]
-        b = getattr(w, "_dcv_bucket", None)
-        if b is not None and b() is not None:
-            b().before_slot_write(w)
-        dw = slot.detach()
-    else:
-        dw = torch.empty(w.shape, dtype=torch.float32, device=w.device)
-    check(_fn("conv_backward_weight")(C.byref(g), ptr(x), C.byref(xd), ptr(dy), C.byref(dyd), ptr(dw), wsp, wsn, stream_ptr()), "dcv_cl_conv_backward_weight")
-    if _o._OWN_ACCUMULATION:
-        _o.note_first(w, dw)
-    return dw
 
 
 def conv(x, w, g: ConvGeom, act: int = ACT_NONE, slope: float = 0.0, out=None, grad_slot=None, bn_stats=None, act_slot=None):
@@ -456,10 +406,7 @@ class _BnActCl(Function):
         wsp, wsn = _ws("clbn", _fn("bn_workspace_bytes")(Cn), x.device)
         check(_fn("bn_act_backward")(ptr(dy), C.byref(dyd), ptr(x), C.byref(xd), ptr(dx), C.byref(dxd), ptr(gamma), ptr(beta), ptr(stats[0]), ptr(stats[1]),
                                        ptr(mask), int(training), act, slope, ptr(dgb[0]), ptr(dgb[1]), wsp, wsn, stream_ptr()), "dcv_cl_bn_act_backward")
-        from . import ops as _o
-        if _o._OWN_ACCUMULATION:
-            return dx, _o.deliver_small(gamma, dgb[0]), _o.deliver_small(beta, dgb[1]), None, None, None, None, None, None, None, None, None, None, None
-        return dx, dgb[0], dgb[1], None, None, None, None, None, None, None, None, None, None, None
+        return (dx, _o.deliver_small(gamma, dgb[0]), _o.deliver_small(beta, dgb[1])) + (None,) * 11
 
 
 def bn_act(x, gamma, beta, running_mean, running_var, training: bool, act: int = ACT_NONE, slope: float = 0.0, mask=None, momentum: float = 0.1,
@@ -474,15 +421,12 @@ def bn_act(x, gamma, beta, running_mean, running_var, training: bool, act: int =
 # --------------------------------------------------------------------------- #
 class ConcatBuffer:
     def __init__(self, n, ca, cb, spatial, device):
-        from .ops import _JoinSlices
-        self._join = _JoinSlices
         if ca % 8:
             raise N.NativeError("ConcatBuffer: the first member's channel count must be a multiple of 8 (16-byte aligned second slice)")
         self.buf = cl_empty((n, ca + cb) + tuple(spatial), device, zero=bool((ca + cb) % 8))
         self.first, self.second = self.buf[:, :ca], self.buf[:, ca:]
         self.second._dcv_trailing = True          # nothing live behind it inside a pixel (only the buffer's own padding): may have any channel count (_check_out_view)
-        from .ops import GradSlot, _SKIP_ACCUMULATE
-        self.slot = GradSlot() if _SKIP_ACCUMULATE else None
+        self.slot = _o.GradSlot() if _o._SKIP_ACCUMULATE else None
 
     def join(self, a, b):
-        return self._join.apply(a, b, _Out(self.buf), self.slot)
+        return _o._JoinSlices.apply(a, b, _Out(self.buf), self.slot)

@@ -887,5 +887,46 @@ def test_cl_graph_against_twin(dev, rec, monkeypatch, half, name, pattern):
             assert not [k for k in tot if k.endswith("weight_acc")], tot
 
 
+class _SlottedCL(G.DeviceCL):
+    """DeviceCL whose parameters carry a hand-set, NaN-filled `_dcv_grad_slot` (what optim.GradBucket hands its members under data parallelism)"""
+
+    def __init__(self, device):
+        super().__init__(device)
+        self.slots = []
+
+    def leaf(self, v, kind):
+        t = super().leaf(v, kind)
+        if kind == "param":
+            t._dcv_grad_slot = torch.full(tuple(t.shape), float("nan"), device=self.device)
+            self.slots.append((t, t._dcv_grad_slot))
+        return t
+
+
+@pytest.mark.parametrize("half", ["bf16", "fp16"])
+def test_cl_weight_gradient_slot_rule(dev, rec, monkeypatch, half):
+    """One rule for a weight's bucket slot on both paths (ops.deliver_wgrad): the first weight gradient of a backward is written into the slot whatever
+    _OWN_ACCUMULATION says.  The CL16 parameter-sum graph, its weight used twice in one backward (real and fake batch): with the library's sums the second use is added
+    into the slot by the accumulating entry and .grad IS the slot; without them the second use gets a tensor of its own from the plain entry and autograd adds.  The
+    twin's words either way, and the same words (two exact terms: one sum)."""
+    from dcvgan_amd import ops, ops_cl
+    monkeypatch.setattr(ops_cl, "_HALF", [{"bf16": torch.bfloat16, "fp16": torch.float16}[half]])
+    graph, pattern = CL_GRAPHS["psum_cl"], "two_forwards_summed"
+    res = {}
+    for own in (True, False):
+        with monkeypatch.context() as m:
+            m.setattr(ops, "_OWN_ACCUMULATION", own)
+            B = _SlottedCL(dev)
+            got, marks = G.run_pattern(B, graph, pattern, rec)
+        compare(f"cl {half} slotted own={own}", got, twin_cl("psum_cl", pattern))
+        (w, slot), = B.slots
+        k = _cl_counts(dict(marks)["bwd_both"], half)
+        assert (k["w"], k["w_acc"]) == ((1, 1) if own else (2, 0)) and k["data"] == 2 and not k["refused"], (own, marks)
+        assert bool(torch.isfinite(slot).all()), "the slot was not written"
+        if own:      # (where autograd's own sum ends up is autograd's business)
+            assert w.grad.data_ptr() == slot.data_ptr() and G.same_words(slot.cpu(), got["dw"])
+        res[own] = got
+    same(f"cl {half} slotted _OWN_ACCUMULATION", res[True], res[False])
+
+
 def test_zz_words_compared():
     print(f"graph-exact words compared: {WORDS[0]}")
