@@ -169,6 +169,8 @@ class ColorVideoGenerator(nn.Module):
         rng = self._source()
         if self.geometric_info == "segmentation":  # one-hot -> {-1, +1} maps (generator.py:378-385); SURVEY §8(f).4
             x = ops.segm_onehot(x)
+            if layers.ARGMAX_TAP is not None:
+                layers.ARGMAX_TAP.append(x.argmax(1, keepdim=True).cpu())
         if ops_cl.active():
             return self._forward_cl(x, z, rng)
         # Every torch.cat of the reference (generator.py:393-400) joins an up-path tensor with a skip:

@@ -22,6 +22,10 @@ from . import ops, ops_cl
 # its output, in execution order — the pattern the backward kernels differentiate with (tests/test_fullwidth_gpu.py
 # replays it in an fp64 evaluation of the same graph on the host).  None in production: nothing is recorded.
 KINK_TAP = None
+# Test instrumentation of the segmentation branch: when a list is installed here, the colour generator appends, per pass, the part index per pixel of the
+# {-1,+1} maps it actually read ((N, 1, H, W) int64 on the host) — the choice an fp64 evaluation of the same iteration on the host is told to take (tests/test_end_to_end_gpu.py).
+# None in production: nothing is recorded, no launch and no copy is added.
+ARGMAX_TAP = None
 # Diagnostic of the 16-bit paths (bench.py's stress leg, tests/test_fp16_gpu.py): when a list is installed here, every convolution output that feeds a BatchNorm
 # appends its largest magnitude (a 0-d device tensor) — the un-normalised sums that decide whether fp16's 65504 is enough.  None in production.
 PREBN_TAP = None

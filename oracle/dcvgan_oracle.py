@@ -143,6 +143,48 @@ class KinkTape:
         return m
 
 
+class ArgmaxTape:
+    """Test instrumentation for the segmentation branch's arg-max (generator.py:378-385), beside `KinkTape`.  The colour generator's
+    input is a step function of the geometry generator's softmax: a pixel whose two largest probabilities are within rounding of each
+    other takes the other part in another arithmetic, and everything downstream moves.  With a tape installed
+    (`with ArgmaxTape(maps) as tape:`) the i-th `cgen_forward(..., segmentation=True)` takes its part index per pixel from the i-th
+    recorded map ((N, 1, H, W) int64) instead of its own `argmax`, which is still computed: `tape.mismatch` collects, per call,
+    (pixels whose own choice differs, pixels, the largest gap among them) — the gap being own maximum minus the value at the
+    recorded part, in the evaluation's own precision; it is the top-2 gap when the recorded part is the runner-up and larger
+    otherwise."""
+
+    active = None
+
+    def __init__(self, maps=None, edit=None):
+        """`maps=None`: RECORD this evaluation's own choices into `self.recorded` instead of replaying; `edit(x, own) -> index` then
+        stands in for a faulty arg-max (the evaluation reads, and records, what it returns)."""
+        self.maps, self.pos, self.mismatch, self.edit = maps, 0, [], edit
+        self.recorded = [] if maps is None else None
+
+    def __enter__(self):
+        ArgmaxTape.active = self
+        return self
+
+    def __exit__(self, *a):
+        ArgmaxTape.active = None
+
+    def next(self, x, own):
+        if self.recorded is not None:
+            if self.edit is not None:
+                own = self.edit(x.detach(), own)
+            self.recorded.append(own.clone())
+            self.pos += 1
+            return own
+        m = self.maps[self.pos]
+        self.pos += 1
+        assert tuple(m.shape) == tuple(own.shape) and m.dtype == torch.long, (self.pos - 1, tuple(m.shape), m.dtype, tuple(own.shape))
+        assert int(m.min()) >= 0 and int(m.max()) < x.shape[1], (self.pos - 1, int(m.min()), int(m.max()))
+        xd = x.detach()
+        gap = (xd.gather(1, own) - xd.gather(1, m))[own != m]
+        self.mismatch.append((int(gap.numel()), own.numel(), float(gap.max()) if gap.numel() else 0.0))
+        return m
+
+
 class _PatternLeaky(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mask, slope):
@@ -241,6 +283,8 @@ def cgen_forward(st: State, x: torch.Tensor, z: torch.Tensor, rng, training: boo
     """ColorVideoGenerator.forward (generator.py:361-402)."""
     if segmentation:  # generator.py:378-385
         idx = torch.argmax(x, 1, keepdim=True)
+        if ArgmaxTape.active is not None:
+            idx = ArgmaxTape.active.next(x, idx)
         x = torch.full_like(x, -1.0).scatter_(1, idx, 1.0)
     # Inconv: conv3x3 + LeakyReLU(default slope 0.01)  (generator.py:173-176)
     hs = [_lrelu(F.conv2d(x, st["inconv.main.0.weight"], None, 1, 1), 0.01)]

@@ -10,6 +10,10 @@ both so that the update itself can be held tight:
   * it evaluates the pinned oracle's iteration in **fp64**, on the draws the checked run consumed (``ReplayRng64``);
   * every (Leaky)ReLU differentiates with the branch pattern the checked run took (``KinkTape``; the pattern itself is bounded
     separately: it may differ from fp64's own signs only within ``KINK_EPS`` rms of zero, for a handful of elements);
+  * for a segmentation config the colour generator reads the arg-max of the geometry generator's softmax, a step function: a pixel whose two largest
+    probabilities are within rounding of each other takes the other part in fp32 and everything downstream moves (one such pixel of 131 072 makes the
+    reference's own fp32 arithmetic miss the bars).  The fp64 side takes the part maps the checked run's colour generator actually read (``ArgmaxTape``); how
+    they differ from fp64's own choice is bounded separately: only where fp64's gap is <= ``ARGMAX_GAP``, at no more than ``ARGMAX_MAX`` pixels per pass;
   * before every iteration it is **teacher-forced**: parameters, BatchNorm buffers and Adam moments / step counts are overwritten
     with the checked run's current values, so iteration k compares one iteration, not the accumulated lottery of k of them;
   * the fp32 rounding of the stored parameter (<= ulp(theta) / 2 per optimiser call — 3e-4 of a move of lr for a BatchNorm gamma ~ 1;
@@ -57,8 +61,10 @@ def snapshot(models, opts) -> Dict[str, dict]:
 
 
 class ForcedStepOracle:
-    def __init__(self, cfg, draw_log, betas=(0.5, 0.999)):
-        self.cfg, self.betas = cfg, betas
+    def __init__(self, cfg, draw_log, betas=(0.5, 0.999), argmax_tape=True):
+        """`argmax_tape=False` leaves the fp64 side its own arg-max in front of the colour generator (tools/stepcheck_reference.py shows what
+        that lottery costs); the tests never do."""
+        self.cfg, self.betas, self.argmax_tape = cfg, betas, argmax_tape
         self.rng = ReplayRng64(draw_log)
         self.so = None
 
@@ -86,15 +92,21 @@ class ForcedStepOracle:
                                         "exp_avg_sq": s["exp_avg_sq"].double().clone()}
                     p.grad = None
 
-    def step(self, xc_real, xg_real, t_rand: int, kinks) -> dict:
-        """One iteration from the forced state with the recorded branch patterns.  -> losses + kink statistics."""
-        with O.KinkTape(kinks) as tape:
+    def step(self, xc_real, xg_real, t_rand: int, kinks, parts=()) -> dict:
+        """One iteration from the forced state with the recorded branch patterns and, for a segmentation config, the recorded part
+        maps the checked run's colour generator read (`parts`, one per pass).  -> losses + kink and arg-max statistics."""
+        if not self.argmax_tape:
+            parts = ()
+        with O.KinkTape(kinks) as tape, O.ArgmaxTape(list(parts)) as atape:
+            if not self.argmax_tape:
+                O.ArgmaxTape.active = None
             losses = self.so.step(xc_real.double(), xg_real.double(), t_rand)
         assert tape.pos == len(kinks), (tape.pos, len(kinks))
+        assert atape.pos == len(parts), (atape.pos, len(parts))
         flips = sum(m[0] for m in tape.mismatch); total = sum(m[1] for m in tape.mismatch)
         far = max([m[2] for m in tape.mismatch] or [0.0])
         worst_call = max(range(len(tape.mismatch)), key=lambda i: tape.mismatch[i][2]) if tape.mismatch else -1
-        return {"losses": losses, "kink_flips": flips, "kink_total": total, "kink_far": far,
+        return {"losses": losses, "kink_flips": flips, "kink_total": total, "kink_far": far, "argmax": list(atape.mismatch),
                 "kink_worst_call": (worst_call,) + tuple(tape.mismatch[worst_call]) if worst_call >= 0 else None}
 
     def compare(self, before, after, lrs) -> List[dict]:
@@ -161,22 +173,27 @@ def worst(rows, field):
 
 
 def checked_iteration(runner, models, opts, forced: ForcedStepOracle, layers_mod, xc_dev, xg_dev, xc_cpu, xg_cpu, t_rand: int, lrs) -> dict:
-    """Run ONE iteration of `runner` (the checked implementation; `layers_mod.KINK_TAP` is its branch-pattern tap) and the same
-    iteration of the teacher-forced fp64 oracle; return everything the callers assert on."""
+    """Run ONE iteration of `runner` (the checked implementation; `layers_mod.KINK_TAP` is its branch-pattern tap and
+    `layers_mod.ARGMAX_TAP` the tap of the part maps its colour generator read, which stays empty without a segmentation head) and
+    the same iteration of the teacher-forced fp64 oracle; return everything the callers assert on.  `argmax`: per colour-generator
+    pass (mismatches, pixels, worst fp64 gap), see O.ArgmaxTape."""
     before = snapshot(models, opts)
     forced.force(before, runner.iteration)
     layers_mod.KINK_TAP = kinks = []
+    layers_mod.ARGMAX_TAP = parts = []
     try:
         got = runner.step(xc_dev, xg_dev, t_rand)
     finally:
         layers_mod.KINK_TAP = None
+        layers_mod.ARGMAX_TAP = None
     got = {k: float(v) for k, v in got.items()}
     after = snapshot(models, opts)
-    ref = forced.step(xc_cpu, xg_cpu, t_rand, kinks)
+    ref = forced.step(xc_cpu, xg_cpu, t_rand, kinks, parts)
     rows = forced.compare(before, after, lrs)
     loss_rel = max(abs(got[k] - ref["losses"][k]) / max(abs(ref["losses"][k]), 1e-30) for k in ref["losses"])
     return {"losses": got, "ref_losses": ref["losses"], "loss_rel": loss_rel, "rows": rows, "buffers_rel": forced.buffers_rel(after),
-            "kink_flips": ref["kink_flips"], "kink_total": ref["kink_total"], "kink_far": ref["kink_far"], "kink_worst_call": ref["kink_worst_call"]}
+            "kink_flips": ref["kink_flips"], "kink_total": ref["kink_total"], "kink_far": ref["kink_far"], "kink_worst_call": ref["kink_worst_call"],
+            "argmax": ref["argmax"]}
 
 
 # The bars every caller uses.  Measured: the fixed-seed tests' reports (update <= 1.6e-5, pattern <= 1.2e-4 rms) and sweeps over 20 seeds x 3 full-width
@@ -187,6 +204,14 @@ def checked_iteration(runner, models, opts, forced: ForcedStepOracle, layers_mod
 UPDATE_TOL = 1e-3          # relative L2 of a tensor's update over its insensitive elements
 LOSS_TOL = 1e-4            # every loss of the iteration, relative
 BUFFER_TOL = 2e-4          # BatchNorm running statistics after the iteration, relative L2 per buffer
+# The segmentation head's arg-max (O.ArgmaxTape): two conditions, not tolerances.  The probabilities are ~1 / 25 and fp32 carries ~1e-8 there, so a pixel
+# that another fp32 arithmetic assigns to another part has an fp64 gap ~1e-8; ARGMAX_GAP is the bar tests/test_models_gpu.py::test_generators_eval already
+# uses, two orders above that.  Near zero the gaps have a density of ~550 per unit gap per pass of 2 x 16 x 64 x 64 pixels (measured on the width/8
+# config), i.e. ~1 expected mismatch; the reference's own fp32 arithmetic shows <= 1 per pass (profiles/stepcheck_segm.txt).  A mis-indexed channel or
+# pixel flips thousands, at gaps of the order of the probabilities themselves.
+ARGMAX_GAP = 1e-6          # fp64 gap of every pixel whose part differs from fp64's own choice
+ARGMAX_MAX = 16            # such pixels per colour-generator pass of ARGMAX_PIXELS
+ARGMAX_PIXELS = 2 * 16 * 64 * 64
 MOMENT_TOL = 1e-3          # Adam's exp_avg / exp_avg_sq after the iteration, relative L2 over the insensitive elements (round 4; measured: profiles/r04_step_parity/)
 
 
@@ -195,6 +220,8 @@ def assert_iteration(res, lrs, tag=""):
     assert res["loss_rel"] <= LOSS_TOL, (tag, res["losses"], res["ref_losses"])
     assert res["buffers_rel"] <= BUFFER_TOL, (tag, res["buffers_rel"])
     assert res["kink_flips"] <= max(8, KINK_FRAC * res["kink_total"]) and res["kink_far"] <= KINK_EPS, (tag, res["kink_flips"], res["kink_total"], res["kink_far"], res.get("kink_worst_call"))
+    for n, pixels, gap in res.get("argmax", ()):
+        assert gap <= ARGMAX_GAP and n <= ARGMAX_MAX * max(1, pixels // ARGMAX_PIXELS), (tag, res["argmax"])
     n_sens = n_off = 0
     w = 0.0
     for r in res["rows"]:
@@ -216,6 +243,7 @@ def report_lines(res, it):
            "# loss_rel %.3e  buffers_rel %.3e  kinks: %d of %d on the other branch than fp64, furthest %.2e rms from zero" %
            (res["loss_rel"], res["buffers_rel"], res["kink_flips"], res["kink_total"], res["kink_far"]),
            "# furthest: activation call %s" % (res.get("kink_worst_call"),),
+           "# arg-max per colour-generator pass (mismatches, pixels, worst fp64 gap): %s" % (res.get("argmax", []),),
            "# %-44s %9s %5s %-11s %-9s %-6s %-9s %-10s %-10s" % ("tensor", "numel", "calls", "rel_l2(ins)", "sensitive", "off", "worst/lr", "moment_rel", "moment2_rel")]
     for r in res["rows"]:
         out.append("%-46s %9d %5d %.3e   %9d %6d %.3e %.3e %.3e" % (r["model"] + "/" + r["key"], r["numel"], r["calls"], r["rel_l2"], r["n_sensitive"],

@@ -166,6 +166,28 @@ class Host:
     def fan_out(self, x, t, n_full):
         return (x[:, :, t],) + tuple(x for _ in range(n_full))
 
+    def segm_onehot(self, x):
+        """ops.segm_onehot: {-1, +1} maps by channel arg-max, the FIRST maximum on a tie; no gradient passes"""
+        with torch.no_grad():
+            y = torch.full_like(x, -1.0).scatter_(1, x.argmax(1, keepdim=True), 1.0)
+            return y.abs() if self.magnitude else y
+
+    def fan_geometry(self, x, t, rows):
+        """augment.ClipAugment.fan_geometry under a fixed table of flips, shifts and cutouts (the geometry stream moves values, tests/test_augment_cpu.py::forward_ref),
+        in fan_out's order: (frame t of the augmented clip, x itself for the colour generator, the augmented clip twice)"""
+        H, W = x.shape[3], x.shape[4]
+        hh, ww = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
+        planes = []
+        for b, r in enumerate(rows):
+            cy0, cx0, cs = r.get("cy0", 0), r.get("cx0", 0), r.get("cs", 0)
+            cut = (hh >= cy0) & (hh < cy0 + cs) & (ww >= cx0) & (ww < cx0 + cs)
+            hs, ws = hh - r.get("dy", 0), ww - r.get("dx", 0)
+            ok = ~cut & (hs >= 0) & (hs < H) & (ws >= 0) & (ws < W)
+            wsrc = W - 1 - ws if r.get("flip", 0) else ws
+            planes.append(x[b][:, :, hs.clamp(0, H - 1), wsrc.clamp(0, W - 1)] * ok.to(x.dtype))
+        y = torch.stack(planes)
+        return y[:, :, t], x, y, y
+
     def hinge_sum(self, terms):
         tot = None
         for y, kind in terms:
@@ -253,6 +275,17 @@ class Device:
 
     def fan_out(self, x, t, n_full):
         return self.ops.fan_out(x, t, n_full)
+
+    def segm_onehot(self, x):
+        return self.ops.segm_onehot(x)
+
+    def fan_geometry(self, x, t, rows):
+        from types import SimpleNamespace
+        from dcvgan_amd import augment
+        from tests.test_augment_cpu import make_table
+        aug = augment.ClipAugment(SimpleNamespace(batchsize=x.shape[0], geometric_info="segmentation"), self.device, p=1.0, adaptive=False)
+        g_c, g_i, g_v, g_g = aug.fan_geometry(x, t, torch.from_numpy(make_table(rows)).to(self.device))
+        return g_i, g_c, g_v, g_g
 
     def hinge_sum(self, terms):
         return self.ops.gan_loss_sum(list(terms))
@@ -438,6 +471,46 @@ def dfront_graph(slope, three_d=False):
                  dict(x=(2, 8) + sp_in, buffer=(2, 16) + sp_mid, y=(2, 16) + sp_out))
 
 
+SEGM_AUG_ROWS = (dict(flip=1, dx=1, dy=-1, cy0=1, cx0=2, cs=3), dict(dx=-2, dy=1, cy0=5, cx0=-1, cs=4))      # one row per clip: every branch of the geometry stream
+
+
+def segmfront_graph(slope, augmented=False):
+    """The generators' front of the segmentation iteration (trainer.StepRunner._colour): a (B, T, C, H, W) clip of C = 25 maps viewed as (B, C, T, H, W), fanned out
+    to four readers — frame t through conv4s2p1(25 -> 8) + act (the image discriminator's geometry stem), the clip through conv3d (4,4,4) s(1,2,2)(25 -> 8) + act
+    (the video discriminator's), its temporal difference through another (the gradient discriminator's), and the colour generator: the frames through segm_onehot
+    (no gradient passes) into the U-Net stage of unet_graph, whose stem conv3s1p1(25 -> 8) + act has NO data gradient while its act_slot is armed.  The clip's ONE
+    gradient is formed from three cotangents and a None.  `augmented`: augment.fan_geometry under SEGM_AUG_ROWS in fan_out's place (_AugFan has the same branch)."""
+    Bn, T, Cg, S, t = 2, 5, 25, 8, 2
+    spec = OrderedDict(x=((Bn, T, Cg, S, S), "input", ints), w1=((8, Cg, 3, 3), "param", _w(0.04)), w2=((16, 8, 4, 4), "param", _w(0.1)),
+                       w3=((16, 8, 4, 4), "param", _w(0.1)), w4=((8, 16, 3, 3), "param", _w(0.1)), wi=((8, Cg, 4, 4), "param", _w(0.1)),
+                       wv=((8, Cg, 4, 4, 4), "param", _w(0.05)), wg=((8, Cg, 4, 4, 4), "param", _w(0.05)))
+
+    def fn(B, L):
+        clip = L["x"].permute(0, 2, 1, 3, 4)                                  # the generators' layout: a view
+        g_i, g_c, g_v, g_g = B.fan_geometry(clip, t, SEGM_AUG_ROWS) if augmented else B.fan_out(clip, t, 3)
+        maps = B.segm_onehot(g_c.permute(0, 2, 1, 3, 4).reshape(Bn * T, Cg, S, S))      # forward_videos' frames: a view again
+        buf = B.buffer(Bn * T, 8, 8, (S, S))
+        a = B.conv(maps, L["w1"], (1, 1), (1, 1), act=slope, out=(buf, "second"), act_slot=buf)
+        d = B.conv(a, L["w2"], (2, 2), (1, 1), act=slope, grad_slot=buf)
+        u = B.conv(d, L["w3"], (2, 2), (1, 1), transposed=True, out=(buf, "first"))
+        yc = B.out(B.conv(B.join(buf, u, a), L["w4"], (1, 1), (1, 1)))
+        yi = B.conv(g_i, L["wi"], (2, 2), (1, 1), act=slope)
+        yv = B.conv(g_v, L["wv"], (1, 2, 2), (0, 1, 1), act=slope)
+        yg = B.conv(B.temporal_diff(g_g), L["wg"], (1, 2, 2), (0, 1, 1), act=slope)
+        return [yc, yi, yv, yg], dict(skip=a, buf=buf, maps=maps)
+
+    fwd = {"dcv_segm_onehot": 1, "dcv_conv_forward": 7, "dcv_axpby": 1}
+    # seven weight gradients and SIX data gradients: none for the stem.  dcv_axpby: three of temporal_diff's backward, two of fan_out's (vdis + gdis, then the frame)
+    bwd = {"dcv_act_backward": 4, "dcv_conv_backward_data_gated": 1, "dcv_conv_backward_data": 5, "dcv_conv_backward_weight": 7, "dcv_axpby": 5}
+    if augmented:
+        fwd["dcv_aug_apply"] = 1
+        bwd.update({"dcv_axpby": 3, "dcv_aug_fan_backward": 1})
+    late = ("w4", {"dcv_conv_backward_data": 1, "dcv_conv_backward_weight": 1})
+    return Graph(f"segmfront{'_aug' if augmented else ''}_s{slope}", spec, fn, fwd, bwd, late,
+                 [(Bn * T, 8, S, S), (Bn, 8, S // 2, S // 2), (Bn, 8, T - 3, S // 2, S // 2), (Bn, 8, T - 4, S // 2, S // 2)],
+                 dict(x=(Bn, T, Cg, S, S), maps=(Bn * T, Cg, S, S), skip=(Bn * T, 8, S, S), buffer=(Bn * T, 16, S, S), y=(Bn * T, 8, S, S)))
+
+
 def psum_graph(slope):
     """One weight, conv4s2p1(8 -> 8) + act; the call patterns run it on two batches (real and fake)"""
     spec = OrderedDict(x=((2, 8, 8, 8), "input", ints), w=((8, 8, 4, 4), "param", _w(0.25)))
@@ -487,7 +560,7 @@ def prove_cl(graph, pattern, cot_hi=1):
 
 GRAPHS = OrderedDict((g.name, g) for g in (
     [unet_graph(s) for s in SLOPES] + [unet_graph(0.25, thin=True)] + [dfront_graph(s) for s in SLOPES] + [dfront_graph(0.25, three_d=True)]
-    + [psum_graph(s) for s in SLOPES]))
+    + [psum_graph(s) for s in SLOPES] + [segmfront_graph(0.25)]))
 PATTERN_GRAPHS = ("unet_s0.25", "dfront_s0.25", "psum_s0.25")
 
 
@@ -749,6 +822,7 @@ ROUTES = {      # route -> (entry point that proves it, graphs that expect it)
     "skip accumulate, gated entry refused: two-step fallback": ("dcv_conv_backward_data_gated!refused", ("unet_thin_s0.25",)),
     "stem gate (act_applied 2 -> 1 -> 0)": ("dcv_conv_backward_data_gated", ("dfront_s0.25", "dfront_s0.0", "dfront3d_s0.25")),
     "weight gradient, first contribution": ("dcv_conv_backward_weight", ("psum_s0.25", "psum_s0.0")),
+    "skip accumulate + gated data gradient behind a stem without a data gradient (segm_onehot under no_grad)": ("dcv_conv_backward_data_gated", ("segmfront_s0.25",)),
     "weight gradient, later contribution (grad_target)": ("dcv_conv_backward_weight_acc", ("psum_s0.25", "psum_s0.0")),
 }
 

@@ -205,7 +205,11 @@ def step_fixture(ref, cfg, name, loss_name, num_gen_update, start_in_eval, B=2, 
     gdata = torch.Generator().manual_seed(seed + 1)
     lo, hi = (-0.5, 0.5) if cfg["Cg"] == 2 else (-1.0, 1.0)
     xc_real = torch.rand(B, 3, 16, 64, 64, generator=gdata) * 2 - 1
-    xg_real = torch.rand(B, cfg["Cg"], 16, 64, 64, generator=gdata) * (hi - lo) + lo
+    if cfg["Cg"] == 25:   # what dataset.py:176-181 yields for segm.npy: the one-hot (0 / 1) of the part labels, not noise
+        labels = torch.randint(0, 25, (B, 16, 64, 64), generator=gdata)
+        xg_real = torch.nn.functional.one_hot(labels, 25).permute(0, 4, 1, 2, 3).float().contiguous()
+    else:
+        xg_real = torch.rand(B, cfg["Cg"], 16, 64, 64, generator=gdata) * (hi - lo) + lo
     out["meta/seed_data"] = np.array(seed + 1)
     t_rands = [3, 11, 0, 15, 7][:iters]
     out["meta/t_rands"] = np.array(t_rands)
@@ -535,4 +539,6 @@ if __name__ == "__main__":
     small_segm = dict(geo="segmentation", Cg=25, dzc=4, dzm=2, dzcol=2, ngf_g=4, ngf_c=4, ndf_i=4, ndf_v=4, ndf_g=4,
                       noise_i=(True, 0.2), noise_v=(True, 0.2), noise_g=(True, 0.2))
     module_fixture(ref, small_segm, "modules_segm_w4.npz")
+    # config/surreal-segm.yml's iteration at width 4: softmax head, arg-max in front of the colour generator, BCE with num_gen_update 2
+    step_fixture(ref, small_segm, "step_segm_adv_g2.npz", "adversarial-loss", 2, False)
     segmentation_fixture(ref)

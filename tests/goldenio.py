@@ -40,6 +40,19 @@ def cfg_of(fx, B=None, loss="adversarial-loss", num_gen_update=1, num_dis_update
     )
 
 
+def real_clips(B, channel, seed_data):
+    """The real batch of a step fixture, as tests/golden/make_golden.py::step_fixture drew it: the colour clip uniform in [-1, 1), then the
+    geometry clip — uniform noise in the geometry's range, or for the 25 part maps the one-hot of uniform labels (0 / 1, what
+    dataset.py:176-181 yields)."""
+    gd = torch.Generator().manual_seed(int(seed_data))
+    xc = torch.rand(B, 3, 16, 64, 64, generator=gd) * 2 - 1
+    if channel == 25:
+        labels = torch.randint(0, 25, (B, 16, 64, 64), generator=gd)
+        return xc, torch.nn.functional.one_hot(labels, 25).permute(0, 4, 1, 2, 3).float().contiguous()
+    lo, hi = (-0.5, 0.5) if channel == 2 else (-1.0, 1.0)
+    return xc, torch.rand(B, channel, 16, 64, 64, generator=gd) * (hi - lo) + lo
+
+
 def sub(t, step=37):
     return t.detach().contiguous().view(-1)[::step].cpu().numpy()
 

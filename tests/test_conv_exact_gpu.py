@@ -127,6 +127,39 @@ FP32_ROWS = [
     Row(c("conv2d_4s2p1_dc24_j272", False, 2, 17, 24, 4, 2, 1, (8, 8), 2), {"wgrad": "wgrad_gemm_kernel (32 x 256 tile"}),
     Row(c("conv2d_4s2p1_dc33_j80", False, 2, 5, 33, 4, 2, 1, (8, 8), 2), {"wgrad": "wgrad_gemm_kernel (64 x 128 tile"}),
     Row(c("conv2d_4s2p1_dc24_j80", False, 2, 5, 24, 4, 2, 1, (8, 8), 2), {"wgrad": "wgrad_gemm_kernel (32 x 128 tile"}),
+    # ---- the segmentation configuration's own channel counts (CONFIGS["surreal-segm"]: 25 part maps, ggen 96, cgen 64, idis 64, vdis 48, gdis 32) ----
+    # One row per geometry.  Each pass's note was probed once at the config's batch (60 clips = 960 frames, zero operands, no reference); the row has the smallest
+    # probed n / depth whose notes name the same form and tile inside exactconv.FP64_BUDGET_MACS, and `forms` pins what was observed (slab counts aside).
+    # ggen head, 960 x (32, 32): the tiles below; n = 24 / 32 still run the data gradient on another tile
+    Row(c("segm_ggen_head_convT2d_96_25", True, 2, 96, 25, 4, 2, 1, (32, 32), 48), {"fwd": "(32 x 256 tile, 4 classes in one launch)", "dgrad": "(128 x 128 tile, 1 class in one launch)",
+                                                                                 "gated": "(128 x 128 tile, 1 class in one launch)", "wgrad": "wgrad_gemm_kernel (128 x 128 tile"}),
+    # cgen stem (Inconv, a reduction over 225), 960 x (64, 64): the register-staged form; n <= 16 runs the data gradient on another tile
+    Row(c("segm_cgen_stem_conv2d_3s1p1_25_64", False, 2, 25, 64, 3, 1, 1, (64, 64), 24), {"fwd": "gather_gemm_kernel (64 x 256 tile)", "dgrad": "gather_gemm_kernel (32 x 256 tile)",
+                                                                                       "gated": "gather_gemm_kernel (32 x 256 tile)", "wgrad": "wgrad_gemm_kernel (64 x 256 tile"}),
+    # idis geometry stem, 60 x (64, 64): every n from 1 up leaves the batch's notes
+    Row(c("segm_idis_stem_conv2d_4s2p1_25_32", False, 2, 25, 32, 4, 2, 1, (64, 64), 3), {"fwd": "(32 x 256 tile, 1 class in one launch, split-K)", "dgrad": "(32 x 256 tile, 4 classes in one launch)",
+                                                                                      "gated": "(32 x 256 tile, 4 classes in one launch)", "wgrad": "wgrad_gemm_kernel (32 x 256 tile"}),
+    # vdis / gdis geometry stems, 60 x (16 | 15, 64, 64).  The batch's forward runs WITHOUT split-K, which takes >= 98 304 output positions: 1.1e10 / 1.5e10 multiply-adds,
+    # outside the budget.  No size inside it has that note; these rows have the batch's data-gradient and weight-gradient notes and the forward with split-K
+    Row(c("segm_vdis_stem_conv3d_25_24", False, 3, 25, 24, 4, S3, P3, (4, 64, 64), 32), {"fwd": "(32 x 256 tile, 1 class in one launch, split-K)",
+                                                                                      "dgrad": "gather_gemm_dma_kernel<1, 2, 1, 4, true, true, 0> (32 x 256 tile, 4 classes in one launch)",
+                                                                                      "gated": "(32 x 256 tile, 4 classes in one launch)", "wgrad": "wgrad_gemm_kernel (32 x 256 tile"}),
+    Row(c("segm_gdis_stem_conv3d_25_32", False, 3, 25, 32, 4, S3, P3, (4, 64, 64), 32), {"fwd": "(32 x 256 tile, 1 class in one launch, split-K)",
+                                                                                      "dgrad": "gather_gemm_dma_kernel<1, 2, 1, 4, true, true, 0> (32 x 256 tile, 4 classes in one launch)",
+                                                                                      "gated": "(32 x 256 tile, 4 classes in one launch)", "wgrad": "wgrad_gemm_kernel (32 x 256 tile"}),
+    # vdis colour stem, 60 x (16, 64, 64): every probed size leaves the batch's notes (24 channels: not the 32-channel stem3d_wgrad_kernel; the gated entry is refused)
+    Row(c("segm_vdis_stem_conv3d_3_24", False, 3, 3, 24, 4, S3, P3, (5, 64, 64), 3), {"fwd": "(32 x 256 tile, 1 class in one launch)", "dgrad": "thin_quad_kernel<3, 4>",
+                                                                                   "wgrad": "wgrad_gemm_kernel (32 x 256 tile"}),
+    # vdis trunk, 60 x (13, 32, 32) and 60 x (10, 16, 16).  At the batch: forward 128 x 128 with ragged split-K, data gradient 64 x 256 without split-K (48 -> 96);
+    # data gradient 128 x 64 with ragged split-K (96 -> 192).  No probed size inside the budget keeps those (n = 32 at the full depth, 7.2e10 multiply-adds, still
+    # differs): the smallest rows, which keep the forward's and the weight gradient's tiles and run everything with plain split-K
+    Row(c("segm_vdis_trunk_conv3d_48_96", False, 3, 48, 96, 4, S3, P3, (6, 32, 32), 1), {"fwd": "(128 x 128 tile, 1 class in one launch, split-K)", "dgrad": "(64 x 256 tile, 4 classes in one launch, split-K)",
+                                                                                      "gated": "(64 x 256 tile, 4 classes in one launch, split-K)", "wgrad": "wgrad_gemm_kernel (128 x 128 tile"}),
+    Row(c("segm_vdis_trunk_conv3d_96_192", False, 3, 96, 192, 4, S3, P3, (6, 16, 16), 1), {"fwd": "(64 x 256 tile, 1 class in one launch, split-K)", "dgrad": "(128 x 128 tile, 4 classes in one launch, split-K)",
+                                                                                        "gated": "(128 x 128 tile, 4 classes in one launch, split-K)", "wgrad": "wgrad_dma_kernel<1, 0, true> (64 x 128 tile"}),
+    # vdis head, 60 x (7, 8, 8): every probed size leaves the batch's forms (the plane-group and share counts follow n)
+    Row(c("segm_vdis_head_conv3d_192_1", False, 3, 192, 1, 4, S3, P3, (5, 8, 8), 3), {"fwd": "head_fwd_kernel<4>", "dgrad": "(64 x 256 tile, 4 classes in one launch)",
+                                                                                   "gated": "(64 x 256 tile, 4 classes in one launch)", "wgrad": "head_wgrad_kernel<4>"}),
 ]
 del c
 

@@ -5,7 +5,8 @@ and uint8 depth frames in disk order, tests/golden/dataset_norm.npz `*_in`) -> D
 the device -> StepRunner with the losses read on the host where trainer.py:326-328,363 reads them — three iterations, against the oracle stepping on the
 normalised tensors (the one-line numpy form of dataset.py:127-131, asserted here against the REFERENCE's dataset output `*_out` for the same clips), with the
 oracle's draws injected: losses to 1e-3 and every stepcheck bar
-(losses 1e-4 against fp64 on this run's own activation pattern, BatchNorm buffers 2e-4, parameter updates and Adam moments 1e-3)."""
+(losses 1e-4 against fp64 on this run's own activation pattern, BatchNorm buffers 2e-4, parameter updates and Adam moments 1e-3).  The same
+chain for the segmentation configuration, from uint8 part labels: test_bytes_to_update_segmentation_four_iterations."""
 import itertools
 
 import numpy as np
@@ -92,3 +93,62 @@ def test_bytes_to_update_three_iterations():
     assert rng.pos == len(so.rng.log)                                            # the three iterations consumed exactly the oracle's draws
     xc_d, xg_d = drv.decoded[-1]
     assert torch.equal(xc_d.cpu(), xc_ref) and torch.equal(xg_d.cpu(), xg_ref)  # ... from exactly the reference's normalised tensors
+
+
+def test_bytes_to_update_segmentation_four_iterations():
+    """The shipped segmentation configuration (`CONFIGS["surreal-segm"]` at width / 8, B = 2; 25 part maps, softmax head, arg-max to {-1,+1} maps in front
+    of the colour generator, BCE with num_gen_update 2), bytes to update: uint8 part labels and uint8 colour frames decoded on the device, build_optimizers, a
+    default StepRunner (lanes on) reading its losses on the host, the oracle's draws injected, four checked iterations — the discriminators step in the 2nd
+    and the 4th.  Only this iteration runs ops.segm_onehot under no_grad in front of the stem (whose act_slot is armed although it has no data gradient),
+    ops.fan_out with a reader that hands back no gradient, the softmax backward on the strided video view and the 25-channel stems.  Every stepcheck bar, plus
+    the two arg-max conditions (oracle/stepcheck.py: the maps the colour generator read differ from fp64's own choice only where fp64's gap is <= 1e-6, at
+    <= 16 pixels per pass)."""
+    from dcvgan_amd import dataprep, layers, native, trainer
+    from dcvgan_amd.rng import InjectedRng
+    from tests import fullwidth as FW, segmstep as S
+    native.lib()
+    dev = torch.device("cuda:0")
+    cfg = S.config()
+    labels, color_u8 = S.clip_bytes()
+    xc_ref, xg_ref = S.decoded(labels, color_u8)
+    assert np.array_equal(xg_ref.numpy(), np.eye(25, dtype=np.float32)[labels].transpose(0, 4, 1, 2, 3))
+
+    models, states = S.initial_states(cfg)
+    torch.manual_seed(S.SEED_RUN)
+    so = O.StepOracle(cfg, states)                 # the reference's arithmetic (fp32 torch CPU): supplies the draws
+    want = [so.step(xc_ref, xg_ref, t) for t in S.T_RANDS]
+    FW.to_device(models, dev)
+    rng = InjectedRng(so.rng.log)
+    for m in models.values():
+        m._rng = rng
+    opts = trainer.build_optimizers(cfg, models)
+    runner = trainer.StepRunner(cfg, models, opts, trainer.build_loss(cfg), sync_losses=True)
+    forced = SC.ForcedStepOracle(cfg, so.rng.log)
+    lab_d, col_d = torch.from_numpy(labels).to(dev), torch.from_numpy(color_u8).to(dev)
+
+    class FromBytes:
+        decoded = []
+
+        @property
+        def iteration(self):
+            return runner.iteration
+
+        def step(self, _xc, _xg, t):
+            xc, xg = dataprep.decode_color(col_d), dataprep.decode_segmentation(lab_d)
+            self.decoded.append((xc, xg))
+            return runner.step(xc, xg, t)
+
+    drv = FromBytes()
+    for it, t in enumerate(S.T_RANDS):
+        res = SC.checked_iteration(drv, models, opts, forced, layers, None, None, xc_ref, xg_ref, t, cfg.lr)
+        print("\n".join(SC.report_lines(res, it + 1)[:5]))
+        if it == 0:     # identical weights on both sides (later the fp32 oracle's own run has drifted: the forced fp64 oracle is the reference there)
+            for k, v in want[0].items():
+                assert abs(res["losses"][k] - v) < 1e-3 * max(1.0, abs(v)), (k, res["losses"][k], v)
+        SC.assert_iteration(res, cfg.lr, f"segmentation bytes-to-update it {it + 1}")
+        assert len(res["argmax"]) == 2 and all(p == S.B * 16 * 64 * 64 for _, p, _ in res["argmax"])
+        d_steps = (it + 1) % cfg.num_gen_update == 0
+        assert all(r["calls"] == (2 if r["model"] == "ggen" else 1 if r["model"] == "cgen" or d_steps else 0) for r in res["rows"])
+    assert rng.pos == len(so.rng.log) == forced.rng.pos
+    xc_d, xg_d = drv.decoded[-1]
+    assert torch.equal(xc_d.cpu(), xc_ref) and torch.equal(xg_d.cpu(), xg_ref)      # bit for bit np.eye(25)[labels], transposed

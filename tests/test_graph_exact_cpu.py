@@ -32,6 +32,19 @@ def test_twin_is_exact_in_16_bits(make, pattern):
             G.prove_cl(G.GRAPHS["unet_s0.25"], "once")
 
 
+def test_augmented_segmentation_front_twin():
+    """The fan_geometry variant of the segmentation front (kept out of GRAPHS: it has one call pattern): exact, and the twin's geometry-stream augmentation is the
+    restatement of dcv_aug_apply (tests/test_augment_cpu.py::forward_ref) under the same rows, with x itself handed to the colour generator"""
+    import numpy as np
+    from tests.test_augment_cpu import forward_ref, make_table
+    res, worst = G.prove(G.segmfront_graph(0.25, augmented=True), "once")
+    assert 0.0 < worst < 1.0 and bool((res["dx"] != 0).any())
+    x = G.ints(torch.Generator().manual_seed(3), (2, 3, 4, 8, 8))
+    f, c, v, g = G.Host().fan_geometry(x, 1, G.SEGM_AUG_ROWS)
+    want = torch.from_numpy(forward_ref(x.numpy().astype(np.float32), make_table(G.SEGM_AUG_ROWS), False)).double()
+    assert c is x and v is g and torch.equal(v, want) and torch.equal(f, want[:, :, 1]) and not torch.equal(want, x)
+
+
 def test_prove_rejects_inexact_operands():
     """A case that claims exactness it does not have fails on the host: thirds are on no binary grid, and 2^22-sized activations overflow 24 bits"""
     g = G.psum_graph(0.25)

@@ -149,6 +149,37 @@ def test_unet_slot_state(dev, rec):
     assert slot.g is None and int(slot.act_applied) == 0
 
 
+@pytest.mark.parametrize("augmented", [False, True], ids=["fan_out", "fan_geometry"])
+def test_segmentation_front(dev, rec, monkeypatch, augmented):
+    """The generators' front as the segmentation iteration has it (G.segmfront_graph): the clip's four readers, of which the colour generator — segm_onehot under
+    no_grad into a stem whose act_slot is armed — hands back None.  The clip's gradient and all seven weight gradients are the twin's words; the stem has a weight
+    gradient and NO data-gradient entry (six for seven convolutions), its derivative pass is the consumer's gated epilogue, and the slot is left empty.  With
+    augment.fan_geometry (p = 1, a fixed table of flips, shifts and cutouts) in fan_out's place: _AugFan's missing-gradient branch, one dcv_aug_fan_backward."""
+    from dcvgan_amd import augment
+    monkeypatch.setattr(augment, "lib", rec)
+    graph = G.segmfront_graph(0.25, augmented)
+    B = G.Device(dev)
+    L = graph.leaves(B)
+    rec.reset()
+    outs, taps = graph.fn(B, L)
+    fwd = rec.launches()
+    assert not taps["maps"].requires_grad and taps["buf"].slot.act is not None and taps["buf"].slot.act_applied is False
+    seen = []
+    taps["skip"].register_hook(lambda g: seen.append((taps["buf"].slot.g is None, int(taps["buf"].slot.act_applied))))
+    rec.reset()
+    torch.autograd.backward(outs, graph.cotangents(B))
+    bwd = rec.launches()
+    print(f"graph-exact {graph.name}: fwd {dict(sorted(fwd.items()))} bwd {dict(sorted(bwd.items()))}")
+    got = OrderedDict(y=B.value(outs[0]))
+    G._grads(B, L, got, "")
+    want = G.prove(graph, "once")[0]
+    compare(graph.name, got, want)
+    assert got["dx"] is not None and bool((got["dx"] != 0).any())
+    assert fwd == graph.fwd and bwd == graph.bwd, (fwd, bwd)
+    assert sum(v for k, v in bwd.items() if "backward_data" in k) == 6 and sum(v for k, v in bwd.items() if "backward_weight" in k) == 7 and not [k for k in bwd if "!" in k]
+    assert seen == [(True, 1)] and taps["buf"].slot.g is None and int(taps["buf"].slot.act_applied) == 0
+
+
 # ------------------------------------------------------------------------------------------------------------------------------------------------------
 # every route ON against OFF, bit for bit
 # ------------------------------------------------------------------------------------------------------------------------------------------------------
@@ -170,7 +201,7 @@ def test_route_on_equals_off(dev, rec, monkeypatch, name, switch):
         compare(f"{name} {pattern} {switch} off", off, twin(name, pattern))
         tot_on, tot_off = sum((c for _, c in marks_on), Counter()), sum((c for _, c in marks_off), Counter())
         gated = tot_on["dcv_conv_backward_data_gated"]
-        if switch == "_GATED_DGRAD" or (switch == "_SKIP_ACCUMULATE" and name.startswith("unet")):
+        if switch == "_GATED_DGRAD" or (switch == "_SKIP_ACCUMULATE" and name.startswith(("unet", "segmfront"))):
             # the two-step route: no gated call at all (not even a refused one), the derivative passes come back
             assert not [k for k in tot_off if "gated" in k], tot_off
             stems = 2 if name.startswith("dfront") else 1

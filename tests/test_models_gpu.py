@@ -177,18 +177,17 @@ def test_discriminators(dev, fixture):
 
 
 @pytest.mark.parametrize("elide", [False, True], ids=["as_written", "dead_backward_elided"])
-@pytest.mark.parametrize("fixture", ["step_depth_adv_g1.npz", "step_depth_adv_g1_evalstart.npz", "step_flow_hinge_g2.npz"])
+@pytest.mark.parametrize("fixture", ["step_depth_adv_g1.npz", "step_depth_adv_g1_evalstart.npz", "step_flow_hinge_g2.npz", "step_segm_adv_g2.npz"])
 def test_training_step(dev, fixture, elide):
-    """3 iterations of trainer.py:279-363: losses + post-step parameter checksums vs the reference."""
+    """3 iterations of trainer.py:279-363: losses + post-step parameter checksums vs the reference.  `step_segm_adv_g2` is the segmentation
+    configuration's iteration (softmax head, arg-max in front of the colour generator, BCE, the D phase stepping in iteration 2 only): there
+    assert_iteration also holds the part maps the colour generator read to fp64's own choice (oracle.ArgmaxTape)."""
     from dcvgan_amd import trainer
     fx = G.load(fixture)
     cfg = G.cfg_of(fx, loss=str(fx["meta/loss"]), num_gen_update=int(fx["meta/num_gen_update"]),
                    num_dis_update=int(fx["meta/num_dis_update"]), start_in_eval=bool(fx["meta/start_in_eval"]))
     B = cfg.batchsize
-    gd = torch.Generator().manual_seed(int(fx["meta/seed_data"]))
-    lo, hi = (-0.5, 0.5) if cfg.channel == 2 else (-1.0, 1.0)
-    xc_real = torch.rand(B, 3, 16, 64, 64, generator=gd) * 2 - 1
-    xg_real = torch.rand(B, cfg.channel, 16, 64, 64, generator=gd) * (hi - lo) + lo
+    xc_real, xg_real = G.real_clips(B, cfg.channel, fx["meta/seed_data"])
     # the reference's run (the pinned fp32 oracle reproduces the fixture exactly, tests/test_oracle_golden.py): supplies the draws
     torch.manual_seed(int(fx["meta/seed_run"]))
     so = O.StepOracle(cfg, G.states(fx))
@@ -210,7 +209,8 @@ def test_training_step(dev, fixture, elide):
         del calls[:]
         res = SC.checked_iteration(runner, models, opts, forced, layers, xc_d, xg_d, xc_real, xg_real, int(fx["meta/t_rands"][it - 1]), lrs)
         got = [res["losses"][k] for k in ("loss_idis", "loss_vdis", "loss_gdis", "loss_gen")]
-        if it == 1:     # identical weights on both sides: a pure forward comparison with the reference's numbers
+        print("\n".join(SC.report_lines(res, it)[:5]))
+        if it == 1:    # identical weights on both sides: a pure forward comparison with the reference's numbers
             assert np.allclose(got, fx["losses"][0], rtol=TOL, atol=1e-5), (got, fx["losses"][0])
         # the optimiser wiring, exactly: schedule (incl. update gating and the double ggen step) and torch.optim.Adam's
         # arithmetic on the gradients each call was handed

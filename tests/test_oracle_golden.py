@@ -116,17 +116,14 @@ def test_losses(lname, kind):
         assert np.allclose(got, ref, atol=1e-7)
 
 
-@pytest.mark.parametrize("fixture", ["step_depth_adv_g1.npz", "step_depth_adv_g1_evalstart.npz", "step_flow_hinge_g2.npz"])
+@pytest.mark.parametrize("fixture", ["step_depth_adv_g1.npz", "step_depth_adv_g1_evalstart.npz", "step_flow_hinge_g2.npz", "step_segm_adv_g2.npz"])
 def test_step(fixture):
     fx = G.load(fixture)
     cfg = G.cfg_of(fx, loss=str(fx["meta/loss"]), num_gen_update=int(fx["meta/num_gen_update"]),
                    num_dis_update=int(fx["meta/num_dis_update"]), start_in_eval=bool(fx["meta/start_in_eval"]))
     st = G.states(fx)
     B = cfg.batchsize
-    gd = torch.Generator().manual_seed(int(fx["meta/seed_data"]))
-    lo, hi = (-0.5, 0.5) if cfg.channel == 2 else (-1.0, 1.0)
-    xc_real = torch.rand(B, 3, 16, 64, 64, generator=gd) * 2 - 1
-    xg_real = torch.rand(B, cfg.channel, 16, 64, 64, generator=gd) * (hi - lo) + lo
+    xc_real, xg_real = G.real_clips(B, cfg.channel, fx["meta/seed_data"])
     torch.manual_seed(int(fx["meta/seed_run"]))
     so = O.StepOracle(cfg, st)
     for it in range(1, int(fx["meta/iters"]) + 1):
