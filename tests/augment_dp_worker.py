@@ -3,7 +3,6 @@ Leg "observe": a ClipAugment with interval 1; each rank observes its own hand-wr
 concatenated logits through the C ABI without any collective.  Leg "step": the real DCVGAN modules at width / 8, trainer.StepRunner with
 optim.DataParallelAdam and trainer.build_augment(adaptive, interval 2), different data and random streams on every rank, two iterations.
 Usage: python tests/augment_dp_worker.py RANK WORLD PORT OUT.json"""
-import hashlib
 import json
 import os
 import sys
@@ -14,6 +13,8 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
+from tests import rig  # noqa: E402
+
 NAN = float("nan")
 LOGITS = [[[1.0, 2.0, -1.0, 0.0, NAN, 6.0], [3.0, 4.0, 5.0, 6.0, 7.0]],      # boundary 1: rank 0's (r = 2 / 6 alone), rank 1's (r = 1 alone); together 7 / 11
           [[-1.0, -2.0, 0.5], [-3.0, NAN, -0.0, -4.0]]]           # boundary 2
@@ -21,15 +22,12 @@ RULE = dict(p=0.3, target=0.6, interval=1, p_max=0.8, adjust_clips=16, batch=4) 
 
 
 def main():
-    rank, world, port, out = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4]
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = port
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    from dcvgan_amd import augment, native, optim, trainer
-    from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
+    rank, world, port, out, _ = rig.rank_args()
+    rig.init_rank(port, rank, world)
+    from dcvgan_amd import augment, native, trainer
     dev = torch.device("cuda:0")
     torch.cuda.set_device(0)
-    cfg = CONFIGS["isogd-depth"].scaled(batchsize=2, width_div=8)
+    cfg = rig.small_cfg()
     res = {"rank": rank}
 
     # ---- leg "observe" ----
@@ -49,23 +47,14 @@ def main():
     res["observe_collectives"] = aug.collectives
 
     # ---- leg "step" ----
-    torch.manual_seed(cfg.seed + 17 * rank)
-    models = trainer.build_models(cfg, dev)
-    for m in models.values():
-        optim.broadcast_module(m)
+    models, _ = rig.seeded_models(cfg, dev, cfg.seed + 17 * rank, 1000 + cfg.seed + rank, broadcast=True)
     opts = trainer.build_optimizers(cfg, models, data_parallel=True)
     aug2 = trainer.build_augment(cfg, models, opts, p=0.5, adaptive=True, interval=2, adjust_clips=8, seed=1000 + rank)
     assert aug2.batch == cfg.batchsize * world
-    g = torch.Generator().manual_seed(cfg.seed + rank)
-    xc = (torch.rand(2, 3, 16, 64, 64, generator=g) * 2 - 1).to(dev)
-    xg = (torch.rand(2, 1, 16, 64, 64, generator=g) * 2 - 1).to(dev)
-    r = PhiloxRng(1000 + cfg.seed + rank)
-    for m in models.values():
-        m._rng = r
+    xc, xg = rig.clip_pair(cfg, dev, cfg.seed + rank, geo_channels=1)
     runner = trainer.StepRunner(cfg, models, opts, trainer.build_loss(cfg), augment=aug2)
 
-    def sha(ts):
-        return hashlib.sha256(b"".join(t.detach().cpu().reshape(-1).view(torch.uint8).numpy().tobytes() for t in ts)).hexdigest()
+    sha = rig.sha_of
 
     def weights():
         return [p for n in trainer.MODEL_NAMES for p in models[n].parameters()]

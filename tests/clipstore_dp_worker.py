@@ -3,7 +3,6 @@ rank and world come from torch.distributed; for each of ITERATIONS batches (they
 single-process sampler of batch size B x world makes on the same store.  The sampler makes no collective call; the only ones here are this check's own
 all_gathers, which put the ranks' batches side by side.
 Usage: python tests/clipstore_dp_worker.py RANK WORLD PORT OUT.json"""
-import hashlib
 import json
 import os
 import sys
@@ -12,6 +11,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
+
+from tests import rig  # noqa: E402
 
 T, H, W, B = 16, 12, 10, 3
 COUNTS = [T, T + 1, 40, T + 3, 25, T, T + 1, 31, T + 2, 60, T + 1, 19, 22]      # 13 videos: two iterations of 2 x 3 clips per epoch, one video dropped
@@ -22,9 +23,8 @@ SEED = 77
 def main():
     import torch
     import torch.distributed as dist
-    rank, world, port, out = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4]
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = port
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    rank, world, port, out, _ = rig.rank_args()
+    rig.init_rank(port, rank, world)
     from dcvgan_amd import clipstore as CS
     from dcvgan_amd import native
     native.lib()
@@ -50,7 +50,7 @@ def main():
             dist.all_gather(parts, b[k].cpu())
             ok = ok and bool(torch.equal(torch.cat(parts), full[k].cpu()))
         res["gathered_equal"].append(ok)
-        res["sha"].append(hashlib.sha256(b["color"].cpu().numpy().tobytes() + b["depth"].cpu().numpy().tobytes()).hexdigest())
+        res["sha"].append(rig.sha_of([b["color"], b["depth"]]))
         res["state"].append([mine.epoch, mine.iteration])
     json.dump(res, open(out, "w"))
     dist.destroy_process_group()

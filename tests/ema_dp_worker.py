@@ -3,7 +3,6 @@ GradGuard per phase, synchronised BatchNorm, trainer.build_ema; gloo, cuda:0), d
 synchronised because the twins carry copies of the running statistics: with distinct data per rank those are the same on every rank only when the statistics
 cover every rank's batch (tests/test_sync_bn_dp_gpu.py has the control) — the parameters are identical either way.  Mode "inf": rank 1 writes one inf into a
 local generator gradient right before the second iteration's G-phase measurement.  Usage: python tests/ema_dp_worker.py RANK WORLD PORT OUT.json plain|inf"""
-import hashlib
 import json
 import os
 import sys
@@ -14,33 +13,24 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
+from tests import rig  # noqa: E402
+
 
 def main():
-    rank, world, port, out, mode = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4], sys.argv[5]
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = port
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    rank, world, port, out, (mode,) = rig.rank_args()
+    rig.init_rank(port, rank, world)
     from dcvgan_amd import optim, trainer
-    from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
     dev = torch.device("cuda:0")
     torch.cuda.set_device(0)
-    cfg = CONFIGS["isogd-depth"].scaled(batchsize=2, width_div=8)
-    torch.manual_seed(cfg.seed + 17 * rank)
-    models = trainer.build_models(cfg, dev, sync_bn=True)
-    for m in models.values():
-        optim.broadcast_module(m)
+    cfg = rig.small_cfg()
+    models, _ = rig.seeded_models(cfg, dev, cfg.seed + 17 * rank, 1000 + cfg.seed + rank, sync_bn=True, broadcast=True)
     opts = trainer.build_optimizers(cfg, models, data_parallel=True, guard=dict(max_norm=10.0))
     guard_g = opts["ggen"].guard
     ema = trainer.build_ema(cfg, models, opts, decay=0.9)
     assert ema.guard is guard_g and guard_g is not None and ema.guard is not opts["idis"].guard
     group = optim.sync_bn_group_of(models)
     assert group is not None and group.world == world and optim.sync_bn_group_of(ema.twins) is group      # the twins carry the mark ...
-    g = torch.Generator().manual_seed(cfg.seed + rank)
-    xc = (torch.rand(2, 3, 16, 64, 64, generator=g) * 2 - 1).to(dev)
-    xg = (torch.rand(2, 1, 16, 64, 64, generator=g) * 2 - 1).to(dev)
-    r = PhiloxRng(1000 + cfg.seed + rank)
-    for m in models.values():
-        m._rng = r
+    xc, xg = rig.clip_pair(cfg, dev, cfg.seed + rank, geo_channels=1)
     runner = trainer.StepRunner(cfg, models, opts, trainer.build_loss(cfg), ema=ema)
 
     orig = guard_g.measure
@@ -52,26 +42,26 @@ def main():
         orig()
     guard_g.measure = measure
 
-    def twin_bytes():
-        return b"".join(v.detach().cpu().reshape(-1).view(torch.uint8).numpy().tobytes() for n in ema.names for v in ema.module(n).state_dict().values())
+    def twins():
+        return [v for n in ema.names for v in ema.module(n).state_dict().values()]
 
-    def live_bytes():
-        return b"".join(p.detach().cpu().reshape(-1).view(torch.uint8).numpy().tobytes() for n in ema.names for p in models[n].parameters())
+    def live():
+        return [p for n in ema.names for p in models[n].parameters()]
 
-    res = {"rank": rank, "mode": mode, "twin_sha": [hashlib.sha256(twin_bytes()).hexdigest()], "live_sha": [], "counts": [], "skipped_gen": []}
+    res = {"rank": rank, "mode": mode, "twin_sha": [rig.sha_of(twins())], "live_sha": [], "counts": [], "skipped_gen": []}
     for it in range(2):
         o = runner.step(xc, xg, 3 + it)
         torch.cuda.synchronize()
-        res["twin_sha"].append(hashlib.sha256(twin_bytes()).hexdigest())
-        res["live_sha"].append(hashlib.sha256(live_bytes()).hexdigest())
+        res["twin_sha"].append(rig.sha_of(twins()))
+        res["live_sha"].append(rig.sha_of(live()))
         res["counts"].append(ema.num_updates())
         res["skipped_gen"].append(float(o["skipped_gen"]))
     from dcvgan_amd import sampling
     c0 = group.collectives
     sampling.generate_samples(ema.module("ggen"), ema.module("cgen"), num=2, batchsize=2)
     res["twin_forward_collectives"] = group.collectives - c0      # ... and, in eval mode, never exchange
-    res["twins_differ_from_live"] = twin_bytes()[:1 << 16] != b"".join(
-        v.detach().cpu().reshape(-1).view(torch.uint8).numpy().tobytes() for n in ema.names for v in models[n].state_dict().values())[:1 << 16]
+    first_64k = lambda ts: torch.cat([rig.byte_view(t) for t in ts])[:1 << 16]
+    res["twins_differ_from_live"] = not torch.equal(first_64k(twins()), first_64k(v for n in ema.names for v in models[n].state_dict().values()))
     json.dump(res, open(out, "w"))
     dist.destroy_process_group()
 

@@ -10,6 +10,8 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 
+from tests import rig  # noqa: E402
+
 N_ROWS, DIM, CLASSES = 37, 80, 7      # rows over both ranks (an odd count: the halves differ), feature and class counts
 
 
@@ -26,9 +28,8 @@ def rows_of(rank, world):
 def main():
     import torch
     import torch.distributed as dist
-    rank, world, port, out = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4]
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = port
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    rank, world, port, out, _ = rig.rank_args()
+    rig.init_rank(port, rank, world)
     from dcvgan_amd import evaluation as E
     dev = torch.device("cuda:0")
     torch.cuda.set_device(0)

@@ -11,30 +11,21 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
+from tests import rig  # noqa: E402
+
 
 def main():
-    rank, world, port, out = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4]
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = port
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    from dcvgan_amd import optim, trainer
-    from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
+    rank, world, port, out, _ = rig.rank_args()
+    rig.init_rank(port, rank, world)
+    from dcvgan_amd import trainer
     dev = torch.device("cuda:0")
     torch.cuda.set_device(0)
-    cfg = CONFIGS["isogd-depth"].scaled(batchsize=2, width_div=8)
-    torch.manual_seed(cfg.seed + 17 * rank)
-    models = trainer.build_models(cfg, dev)
-    for m in models.values():
-        optim.broadcast_module(m)
+    cfg = rig.small_cfg()
+    models, _ = rig.seeded_models(cfg, dev, cfg.seed + 17 * rank, 1000 + cfg.seed + rank, broadcast=True)
     opts = trainer.build_optimizers(cfg, models, data_parallel=True, guard={})
     guard_d, guard_g = opts["idis"].guard, opts["ggen"].guard
     assert opts["cgen"].guard is guard_g and opts["gdis"].guard is guard_d and guard_d is not guard_g
-    g = torch.Generator().manual_seed(cfg.seed + rank)
-    xc = (torch.rand(2, 3, 16, 64, 64, generator=g) * 2 - 1).to(dev)
-    xg = (torch.rand(2, 1, 16, 64, 64, generator=g) * 2 - 1).to(dev)
-    r = PhiloxRng(1000 + cfg.seed + rank)
-    for m in models.values():
-        m._rng = r
+    xc, xg = rig.clip_pair(cfg, dev, cfg.seed + rank, geo_channels=1)
     runner = trainer.StepRunner(cfg, models, opts, trainer.build_loss(cfg))
 
     orig = guard_g.measure

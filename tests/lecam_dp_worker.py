@@ -3,7 +3,6 @@ Leg "anchors": a LeCam over three discriminators; each rank hands it its own log
 iterations.  Leg "step": the real DCVGAN modules at width / 8, trainer.StepRunner with optim.DataParallelAdam and trainer.build_lecam(start=0), different data and
 random streams on every rank, two iterations.
 Usage: python tests/lecam_dp_worker.py RANK WORLD PORT OUT.json"""
-import hashlib
 import json
 import os
 import sys
@@ -12,6 +11,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
+
+from tests import rig  # noqa: E402
 
 SIZES = [(2, 2), (128, 128), (300, 77)]      # (real, fake) logits per rank of the three discriminators
 RULE = dict(weight=0.3, decay=0.9, start=0, one_sided=True)
@@ -28,15 +29,12 @@ def logits(iteration, rank):
 def main():
     import torch
     import torch.distributed as dist
-    rank, world, port, out = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4]
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = port
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    from dcvgan_amd import lecam, loss, optim, trainer
-    from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
+    rank, world, port, out, _ = rig.rank_args()
+    rig.init_rank(port, rank, world)
+    from dcvgan_amd import lecam, loss, trainer
     dev = torch.device("cuda:0")
     torch.cuda.set_device(0)
-    cfg = CONFIGS["isogd-depth"].scaled(batchsize=2, width_div=8)
+    cfg = rig.small_cfg()
     res = {"rank": rank}
 
     # ---- leg "anchors" ----
@@ -52,22 +50,13 @@ def main():
     res["anchor_collectives"] = lc.collectives
 
     # ---- leg "step" ----
-    torch.manual_seed(cfg.seed + 17 * rank)
-    models = trainer.build_models(cfg, dev)
-    for m in models.values():
-        optim.broadcast_module(m)
+    models, _ = rig.seeded_models(cfg, dev, cfg.seed + 17 * rank, 1000 + cfg.seed + rank, broadcast=True)
     opts = trainer.build_optimizers(cfg, models, data_parallel=True)
     lc2 = trainer.build_lecam(cfg, models, opts, weight=0.3, start=0)
-    g = torch.Generator().manual_seed(cfg.seed + rank)
-    xc = (torch.rand(2, 3, 16, 64, 64, generator=g) * 2 - 1).to(dev)
-    xg = (torch.rand(2, 1, 16, 64, 64, generator=g) * 2 - 1).to(dev)
-    r = PhiloxRng(1000 + cfg.seed + rank)
-    for m in models.values():
-        m._rng = r
+    xc, xg = rig.clip_pair(cfg, dev, cfg.seed + rank, geo_channels=1)
     runner = trainer.StepRunner(cfg, models, opts, trainer.build_loss(cfg), lecam=lc2)
 
-    def sha(ts):
-        return hashlib.sha256(b"".join(t.detach().cpu().reshape(-1).view(torch.uint8).numpy().tobytes() for t in ts)).hexdigest()
+    sha = rig.sha_of
 
     def weights():
         return [p for n in trainer.MODEL_NAMES for p in models[n].parameters()]

@@ -2,7 +2,6 @@
 GradGuard per phase, trainer.build_spectral_norm; gloo, cuda:0), different data and random streams on every rank, two iterations.  Mode "overlap": the buckets'
 collectives start during the backward.  Mode "inf": rank 1 writes one inf into a local discriminator gradient right before the second iteration's projection.
 Usage: python tests/spectral_dp_worker.py RANK WORLD PORT OUT.json plain|overlap|inf"""
-import hashlib
 import json
 import os
 import sys
@@ -13,31 +12,22 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
+from tests import rig  # noqa: E402
+
 
 def main():
-    rank, world, port, out, mode = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4], sys.argv[5]
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = port
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    from dcvgan_amd import optim, trainer
-    from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
+    rank, world, port, out, (mode,) = rig.rank_args()
+    rig.init_rank(port, rank, world)
+    from dcvgan_amd import trainer
     dev = torch.device("cuda:0")
     torch.cuda.set_device(0)
-    cfg = CONFIGS["isogd-depth"].scaled(batchsize=2, width_div=8)
-    torch.manual_seed(cfg.seed + 17 * rank)
-    models = trainer.build_models(cfg, dev)
-    for m in models.values():
-        optim.broadcast_module(m)
+    cfg = rig.small_cfg()
+    models, _ = rig.seeded_models(cfg, dev, cfg.seed + 17 * rank, 1000 + cfg.seed + rank, broadcast=True)
     opts = trainer.build_optimizers(cfg, models, data_parallel=True, overlap=(mode == "overlap"), guard=dict(max_norm=10.0))
     sn = trainer.build_spectral_norm(cfg, models, opts)      # the same seed on every rank
     guard_d = opts["idis"].guard
     assert sn.guard is guard_d and guard_d is not None and len(sn._dp) == 3 and len(sn.convs) == 14
-    g = torch.Generator().manual_seed(cfg.seed + rank)
-    xc = (torch.rand(2, 3, 16, 64, 64, generator=g) * 2 - 1).to(dev)
-    xg = (torch.rand(2, 1, 16, 64, 64, generator=g) * 2 - 1).to(dev)
-    r = PhiloxRng(1000 + cfg.seed + rank)
-    for m in models.values():
-        m._rng = r
+    xc, xg = rig.clip_pair(cfg, dev, cfg.seed + rank, geo_channels=1)
     runner = trainer.StepRunner(cfg, models, opts, trainer.build_loss(cfg), spectral=sn)
 
     orig = sn.project
@@ -49,8 +39,7 @@ def main():
         orig()
     sn.project = project
 
-    def sha(ts):
-        return hashlib.sha256(b"".join(t.detach().cpu().reshape(-1).view(torch.uint8).numpy().tobytes() for t in ts)).hexdigest()
+    sha = rig.sha_of
 
     def weights():
         return [p for n in ("idis", "vdis", "gdis") for p in models[n].parameters()]

@@ -1,5 +1,5 @@
 """Child process of tests/test_sync_bn_dp_gpu.py: one data-parallel rank with synchronised BatchNorm on cuda:0, gloo collectives (two ranks may share one card; RCCL
-refuses that).  Usage: python tests/sync_bn_worker.py RANK WORLD PORT MODE OUT.json
+refuses that).  Usage: python tests/sync_bn_worker.py RANK WORLD PORT OUT.json MODE
 MODE: "models-2+2" | "models-3+1": idis and vdis (width / 8, no input noise) on 4 real clips split over the ranks, against a one-process run on the 4 clips;
       "step" | "step-overlap" | "step-control": trainer.StepRunner over build_models(sync_bn=True) (control: False), distinct data and Philox streams per rank."""
 import copy
@@ -13,6 +13,8 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
+
+from tests import rig  # noqa: E402
 
 
 def rel(a, b):
@@ -30,9 +32,8 @@ def same_on_all_ranks(world, tensors) -> bool:
 
 def models_mode(rank, world, split, dev, res):
     from dcvgan_amd import optim, trainer
-    from dcvgan_amd.configs import CONFIGS
     from dcvgan_amd.rng import PhiloxRng
-    cfg = CONFIGS["isogd-depth"].scaled(batchsize=2, width_div=8, use_noise=dict(idis=False, vdis=False, gdis=False))
+    cfg = rig.small_cfg(use_noise=dict(idis=False, vdis=False, gdis=False))
     torch.manual_seed(cfg.seed)
     models = trainer.build_models(cfg, dev)
     models = {k: models[k] for k in ("idis", "vdis")}
@@ -43,9 +44,7 @@ def models_mode(rank, world, split, dev, res):
     solo = copy.deepcopy(models)                               # the one-process twin: unmarked, runs all 4 clips
     group = optim.sync_batchnorm(models)
     assert group.world == world and group.rank == rank and optim.sync_bn_group_of(solo) is None
-    g = torch.Generator().manual_seed(77)
-    xc = (torch.rand(4, 3, 16, 64, 64, generator=g) * 2 - 1).to(dev)
-    xg = (torch.rand(4, 1, 16, 64, 64, generator=g) * 2 - 1).to(dev)
+    xc, xg = rig.clip_pair(cfg, dev, 77, batch=4, geo_channels=1)
     lo = sum(split[:rank]); hi = lo + split[rank]
     bucket = optim.GradBucket()
     for m in models.values():
@@ -94,23 +93,14 @@ def models_mode(rank, world, split, dev, res):
 
 def step_mode(rank, world, mode, dev, res):
     from dcvgan_amd import optim, trainer
-    from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
     sync, overlap = mode != "step-control", mode == "step-overlap"
-    cfg = CONFIGS["isogd-depth"].scaled(batchsize=2, width_div=8)
-    torch.manual_seed(cfg.seed + 17 * rank)                    # deliberately different replicas ...
-    models = trainer.build_models(cfg, dev, sync_bn=sync)
-    for m in models.values():
-        optim.broadcast_module(m)                              # ... made identical here
+    cfg = rig.small_cfg()
+    # deliberately different replicas, made identical by the broadcast; distinct noise / dropout / latent streams per rank
+    models, _ = rig.seeded_models(cfg, dev, cfg.seed + 17 * rank, 1000 + rank, sync_bn=sync, broadcast=True)
     group = optim.sync_bn_group_of(models)
     assert (group is not None and group.world == world) if sync else group is None
     opts = trainer.build_optimizers(cfg, models, data_parallel=True, overlap=overlap)
-    g = torch.Generator().manual_seed(cfg.seed + rank)         # distinct data per rank
-    xc = (torch.rand(2, 3, 16, 64, 64, generator=g) * 2 - 1).to(dev)
-    xg = (torch.rand(2, 1, 16, 64, 64, generator=g) * 2 - 1).to(dev)
-    r = PhiloxRng(1000 + rank)                                 # distinct noise / dropout / latent streams per rank
-    for m in models.values():
-        m._rng = r
+    xc, xg = rig.clip_pair(cfg, dev, cfg.seed + rank, geo_channels=1)      # distinct data per rank
     runner = trainer.StepRunner(cfg, models, opts, trainer.build_loss(cfg))
     per_it, finite = [], True
     for it in range(2):
@@ -129,9 +119,8 @@ def step_mode(rank, world, mode, dev, res):
 
 
 def main():
-    rank, world, port, mode, out = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4], sys.argv[5]
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = port
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
+    rank, world, port, out, (mode,) = rig.rank_args()
+    rig.init_rank(port, rank, world, timeout=datetime.timedelta(seconds=120))
     dev = torch.device("cuda:0")
     torch.cuda.set_device(0)
     res = {"rank": rank, "mode": mode}

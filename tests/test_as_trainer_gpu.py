@@ -6,21 +6,15 @@ import gc
 import pytest
 import torch
 
+from tests import rig
+
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 
 
 def _cfg_models(B=2, div=8):
-    from dcvgan_amd import trainer
-    from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
-    cfg = CONFIGS["surreal-depth1"].scaled(batchsize=B, width_div=div)      # num_gen_update = 2: every second iteration's D phase is gated off
-    torch.manual_seed(3)
-    models = trainer.build_models(cfg, DEV)
-    r = PhiloxRng(5)
-    for m in models.values():
-        m._rng = r
-    return cfg, models
+    cfg = rig.small_cfg("surreal-depth1", B, div)      # num_gen_update = 2: every second iteration's D phase is gated off
+    return cfg, rig.seeded_models(cfg, DEV, 3, 5)[0]
 
 
 def test_host_mirror_equals_tensor_cpu_and_survives_the_trainers_uses():

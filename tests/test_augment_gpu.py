@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import rig
 from tests import test_augment_cpu as R
 
 pytestmark = pytest.mark.gpu
@@ -405,16 +406,10 @@ def test_state_dict_round_trip():
 # ---- the iteration --------------------------------------------------------------------------------------------------------------------------------------------
 def _iterate(iters, aug_kw, cfg_name="debug-isogd-depth", seed=21):
     from dcvgan_amd import native, trainer
-    from dcvgan_amd.rng import PhiloxRng
     native.lib()
     cfg = _cfg(cfg_name).scaled(batchsize=2)
-    torch.manual_seed(seed)
-    models = trainer.build_models(cfg, DEV)
-    r = PhiloxRng(9)
-    for m in models.values():
-        m._rng = r
-    g = torch.Generator().manual_seed(4)
-    xc = (torch.rand(2, 3, 16, 64, 64, generator=g) * 2 - 1).to(DEV); xg = (torch.rand(2, cfg.channel, 16, 64, 64, generator=g) * 2 - 1).to(DEV)
+    models, r = rig.seeded_models(cfg, DEV, seed, 9)
+    xc, xg = rig.clip_pair(cfg, DEV, 4)
     opts = trainer.build_optimizers(cfg, models)
     aug = trainer.build_augment(cfg, models, opts, **aug_kw) if aug_kw is not None else None
     runner = trainer.StepRunner(cfg, models, opts, trainer.build_loss(cfg), sync_losses=True, augment=aug)

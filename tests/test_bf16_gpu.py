@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import rig
+
 pytestmark = pytest.mark.gpu
 
 
@@ -72,16 +74,13 @@ def test_training_iteration_in_bf16_mode(bf16, name):
     one configs[4] names for the 16-bit MFMA path): finite losses, parameters move, forward within 3e-2 of the fp32 mode."""
     from dcvgan_amd import native, trainer
     from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
     dev = bf16
     cfg = CONFIGS[name].scaled(batchsize=4, num_gen_update=1)
     torch.manual_seed(5)
     models = trainer.build_models(cfg, dev)
 
     def fakes():
-        r = PhiloxRng(77)
-        for m in models.values():
-            m._rng = r
+        rig.share_rng(models, 77)
         with torch.no_grad():
             xg = models["ggen"].sample_videos(4)
             return xg, models["cgen"].forward_videos(xg)
@@ -93,8 +92,7 @@ def test_training_iteration_in_bf16_mode(bf16, name):
     assert 1e-4 < rel(xc_b, xc_f) < 3e-2 and rel(xg_b, xg_f) < 3e-2
     before = torch.cat([p.detach().reshape(-1) for p in models["cgen"].parameters()]).clone()
     runner = trainer.StepRunner(cfg, models, trainer.build_optimizers(cfg, models), trainer.build_loss(cfg), sync_losses=True)
-    g = torch.Generator().manual_seed(1)
-    xc = (torch.rand(4, 3, 16, 64, 64, generator=g) * 2 - 1).to(dev); xg = (torch.rand(4, cfg.channel, 16, 64, 64, generator=g) * 2 - 1).to(dev)
+    xc, xg = rig.clip_pair(cfg, dev, 1, batch=4)
     out = runner.step(xc, xg, 3)
     assert all(v == v and abs(v) < 100 for v in out.values()), out
     after = torch.cat([p.detach().reshape(-1) for p in models["cgen"].parameters()])

@@ -17,9 +17,9 @@ import pytest
 import torch
 
 from tests import exactbn as X
+from tests import rig
 
 pytestmark = pytest.mark.gpu
-FAULTED = []
 
 
 @pytest.fixture(scope="module")
@@ -31,18 +31,12 @@ def dev():
 
 @pytest.fixture(autouse=True)
 def _stop_after_fault():
-    """After a device fault nothing else of this module is started on the GPU"""
-    if FAULTED:
-        pytest.fail(f"not run: the device reported a fault earlier in this module ({FAULTED[0]})")
+    """After a device fault (seen here or anywhere else through tests/rig.py) nothing else of this module is started on the GPU"""
+    rig.stop_after_fault()
     yield
 
 
-def sync():
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as e:
-        FAULTED.append(str(e)[:200])
-        raise
+sync = rig.sync
 
 
 def note():

@@ -10,6 +10,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import rig
+
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 
@@ -206,10 +208,8 @@ def test_models_cl16_against_fp32_path(name):
     the fp32 HIP path's (bf16 storage of ~20 layers' activations), parameter gradients of a generator-loss backward within 1e-1 relative L2 per model."""
     import os
     from dcvgan_amd import native, ops_cl, trainer
-    from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
     native.lib()
-    cfg = CONFIGS[name].scaled(batchsize=2, width_div=4)
+    cfg = rig.small_cfg(name, width_div=4)
     torch.manual_seed(3)
     models = trainer.build_models(cfg, DEV)
     for m in models.values():
@@ -219,9 +219,8 @@ def test_models_cl16_against_fp32_path(name):
     loss = trainer.build_loss(cfg)
 
     def run():
-        r = PhiloxRng(99)
+        rig.share_rng(models, 99)
         for m in models.values():
-            m._rng = r
             m.zero_grad()
         xg = models["ggen"].sample_videos(2)
         xc = models["cgen"].forward_videos(xg)
@@ -283,18 +282,12 @@ def test_training_iteration_cl16(name):
     gpurun_out/cl16_iteration_<config>.txt (committed as profiles/r04_cl16_tolerance.txt)."""
     from dcvgan_amd import native, ops_cl, trainer
     from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
     native.lib()
     cfg = CONFIGS[name].scaled(batchsize=4, num_gen_update=1)
-    g = torch.Generator().manual_seed(1)
-    xc = (torch.rand(4, 3, 16, 64, 64, generator=g) * 2 - 1).to(DEV); xg = (torch.rand(4, cfg.channel, 16, 64, 64, generator=g) * 2 - 1).to(DEV)
+    xc, xg = rig.clip_pair(cfg, DEV, 1, batch=4)
     outs = {}
     for mode in (False, True):
-        torch.manual_seed(5)
-        models = trainer.build_models(cfg, DEV)
-        r = PhiloxRng(77)
-        for m in models.values():
-            m._rng = r
+        models, _ = rig.seeded_models(cfg, DEV, 5, 77)
         before = {n: torch.cat([p.detach().reshape(-1) for p in m.parameters()]).clone() for n, m in models.items()}
         ops_cl.enable(mode)
         try:

@@ -2,33 +2,16 @@
 and computes its own slice of the epoch — no sampler object shared, no communication; the rank's batch is its slice of the single-process batch of size 2 B, byte
 for byte, across an epoch boundary.  The only collective calls are the check's own (tests/clipstore_dp_worker.py).  The two ranks are fresh child processes, started
 once for this module; the parent waits for each with a limit, kills leftovers, never retries."""
-import json
-import os
-import socket
-import subprocess
-import sys
-
 import pytest
 
+from tests import rig
+
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 @pytest.fixture(scope="module")
 def ranks(tmp_path_factory):
-    tmp = tmp_path_factory.mktemp("clipstore_dp")
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    outs = [str(tmp / f"clipstore{r}.json") for r in range(2)]
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "clipstore_dp_worker.py"), str(r), "2", str(port), outs[r]], env=env) for r in range(2)]
-    try:
-        for p in procs:
-            assert p.wait(timeout=300) == 0
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    return [json.load(open(o)) for o in outs]
+    return rig.run_ranks("clipstore_dp_worker.py", tmp_path_factory.mktemp("clipstore_dp"), tag="clipstore", timeout=300)
 
 
 def test_each_rank_reads_its_slice_of_the_single_process_batch(ranks):

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import rig
+
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 MODES = {"colour+depth": ("depth", False), "flow": ("optical-flow", False), "segmentation": ("segmentation", False), "surreal-depth": ("depth", True)}
@@ -261,21 +263,15 @@ def test_two_iterations_fed_by_the_sampler():
     """Two StepRunner.step calls at debug widths, B = 2, fed by the sampler: the losses are finite and are those of a run fed the same batches built on the host
     with decode_*."""
     from dcvgan_amd import trainer
-    from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
     CS = _cs()
-    cfg = CONFIGS["isogd-depth"].scaled(batchsize=2, width_div=8)
+    cfg = rig.small_cfg()
     T = cfg.video_length
     counts = [T, T + 1, 40, T + 5, 33]
     videos = _videos(np.random.default_rng(6), counts, 64, 64, "depth", False)
     st = CS.ClipStore.from_arrays(videos, T, "depth", DEV)
 
     def run(feed):
-        torch.manual_seed(21)
-        models = trainer.build_models(cfg, DEV)
-        r = PhiloxRng(9)
-        for m in models.values():
-            m._rng = r
+        models, _ = rig.seeded_models(cfg, DEV, 21, 9)
         opts = trainer.build_optimizers(cfg, models)
         runner = trainer.StepRunner(cfg, models, opts, trainer.build_loss(cfg), sync_losses=True)
         return [runner.step(xc, xg, t) for (xc, xg), t in zip(feed, (3, 11))]

@@ -2,29 +2,19 @@
 The ranks are fresh child processes (never a re-exec of this one)."""
 import json
 import os
-import socket
 import subprocess
 import sys
 
 import pytest
+
+from tests import rig
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def _run(mode, tmp_path):
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    outs = [str(tmp_path / f"{mode}{r}.json") for r in range(2)]
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "dp_worker.py"), str(r), "2", str(port), mode, outs[r]], env=env) for r in range(2)]
-    try:
-        for p in procs:
-            assert p.wait(timeout=600) == 0
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    return [json.load(open(o)) for o in outs]
+    return rig.run_ranks("dp_worker.py", tmp_path, mode, tag=mode, timeout=600)
 
 
 def test_two_ranks_distinct_data(tmp_path):
@@ -88,7 +78,7 @@ def test_bench_under_the_drivers_launcher():
     """The command line the driver uses for N > 1 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py
     --gpus N ...`): RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* come from the launcher, bench.py must not spawn ranks of its own, and exactly one JSON line comes out
     (rank 0's).  Two ranks on this one card, hence gloo and --all-ranks-on-device0; the launcher itself never touches the GPU."""
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
+    port = rig.free_port()
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR", "LOCAL_WORLD_SIZE")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),

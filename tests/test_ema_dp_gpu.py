@@ -1,31 +1,15 @@
 """GPU, two ranks on one card (gloo): the generators' EMA under data parallelism.  Replicas are bit-identical after every step and every rank runs the same
 kernel on the same bits, so the twins and the counts are bit-identical across the ranks without a collective; one rank's inf reaches every rank's G measurement,
 so every rank skips the three G steps AND the EMA update.  The ranks are fresh child processes; the parent waits with a limit, kills leftovers, never retries."""
-import json
-import os
-import socket
-import subprocess
-import sys
-
 import pytest
 
+from tests import rig
+
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def _two_ranks(tmp_path, mode):
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    outs = [str(tmp_path / f"ema_{mode}{r}.json") for r in range(2)]
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "ema_dp_worker.py"), str(r), "2", str(port), outs[r], mode], env=env) for r in range(2)]
-    try:
-        for p in procs:
-            assert p.wait(timeout=600) == 0
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    return [json.load(open(o)) for o in outs]
+    return rig.run_ranks("ema_dp_worker.py", tmp_path, mode, tag=f"ema_{mode}", timeout=600)
 
 
 def test_twins_and_counts_are_identical_across_ranks(tmp_path):

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import rig
+
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 BAR = 2.0 ** -21
@@ -141,9 +143,8 @@ def test_copy_mode_is_bit_exact():
 
 def _models(name="isogd-depth", width_div=8, seed=3, **kw):
     from dcvgan_amd import native, trainer
-    from dcvgan_amd.configs import CONFIGS
     native.lib()
-    cfg = CONFIGS[name].scaled(batchsize=2, width_div=width_div, **kw)
+    cfg = rig.small_cfg(name, width_div=width_div, **kw)
     torch.manual_seed(seed)
     return cfg, trainer.build_models(cfg, DEV)
 
@@ -303,13 +304,9 @@ def test_packed_weights_follow_the_twin(cl):
 
 def _iterate(cfg_name, width_div, iters, with_ema, seed=21, **kw):
     from dcvgan_amd import trainer
-    from dcvgan_amd.rng import PhiloxRng
     cfg, models = _models(cfg_name, width_div, seed, **kw)
-    r = PhiloxRng(9)
-    for m in models.values():
-        m._rng = r
-    g = torch.Generator().manual_seed(4)
-    xc = (torch.rand(2, 3, 16, 64, 64, generator=g) * 2 - 1).to(DEV); xg = (torch.rand(2, cfg.channel, 16, 64, 64, generator=g) * 2 - 1).to(DEV)
+    rig.share_rng(models, 9)
+    xc, xg = rig.clip_pair(cfg, DEV, 4)
     opts = trainer.build_optimizers(cfg, models)
     ema = trainer.build_ema(cfg, models, opts) if with_ema else None
     start = {n: {k: v.detach().clone() for k, v in models[n].named_parameters()} for n in ("ggen", "cgen")}

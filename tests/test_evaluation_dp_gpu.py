@@ -2,36 +2,18 @@
 Inception sums and the row counts) every rank holds the state of one process that saw all the rows: exactly for the moments of integer-valued features, and to the
 Inception sums' bar for the rest.  The two ranks are fresh child processes, started once for this module; the parent waits for each with a limit, kills leftovers,
 never retries."""
-import json
-import os
-import socket
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
+from tests import rig
 from tests import test_evaluation_cpu as R
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 @pytest.fixture(scope="module")
 def ranks(tmp_path_factory):
-    tmp = tmp_path_factory.mktemp("evaluation_dp")
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    outs = [str(tmp / f"evaluation{r}.json") for r in range(2)]
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "evaluation_dp_worker.py"), str(r), "2", str(port), outs[r]], env=env) for r in range(2)]
-    try:
-        for p in procs:
-            assert p.wait(timeout=300) == 0
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    return [json.load(open(o)) for o in outs]
+    return rig.run_ranks("evaluation_dp_worker.py", tmp_path_factory.mktemp("evaluation_dp"), tag="evaluation", timeout=300)
 
 
 def test_every_rank_holds_the_single_process_state(ranks):

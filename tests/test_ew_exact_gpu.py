@@ -17,9 +17,9 @@ import torch
 
 from tests import exactbn as X
 from tests import exactew as E
+from tests import rig
 
 pytestmark = pytest.mark.gpu
-FAULTED = []
 NOTES = {"normal_fill_max_err": 0.0, "cl_noise_max_err": 0.0, "gru": {}}
 G = X.GUARD
 TANH_ULPS = 5          # tests/test_bn_exact_gpu.py: OpenCL C "relative error as ULPs", tanh <= 5 ulp
@@ -39,18 +39,12 @@ def dev():
 
 @pytest.fixture(autouse=True)
 def _stop_after_fault():
-    """After a device fault nothing else of this module is started on the GPU"""
-    if FAULTED:
-        pytest.fail(f"not run: the device reported a fault earlier in this module ({FAULTED[0]})")
+    """After a device fault (seen here or anywhere else through tests/rig.py) nothing else of this module is started on the GPU"""
+    rig.stop_after_fault()
     yield
 
 
-def sync():
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as e:
-        FAULTED.append(str(e)[:200])
-        raise
+sync = rig.sync
 
 
 def call(name, *args):

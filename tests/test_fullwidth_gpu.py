@@ -24,6 +24,7 @@ import torch
 
 from tests import fullwidth as FW
 from tests import goldenio as G
+from tests import rig
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
@@ -278,17 +279,11 @@ def test_iteration_is_bitwise_reproducible(dev, name, B, dp):
     replica mismatch debuggable."""
     from dcvgan_amd import trainer
     from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
     cfg = CONFIGS[name].scaled(batchsize=B)     # also with the data-parallel optimiser wrappers (world of one) and at a batch where the big-problem kernels run
-    g = torch.Generator().manual_seed(3)
-    xc = (torch.rand(B, 3, 16, 64, 64, generator=g) * 2 - 1).to(dev); xg = (torch.rand(B, cfg.channel, 16, 64, 64, generator=g) * 2 - 1).to(dev)
+    xc, xg = rig.clip_pair(cfg, dev, 3, batch=B)
 
     def run(side_streams=True):
-        torch.manual_seed(11)
-        models = trainer.build_models(cfg, dev)
-        r = PhiloxRng(5)
-        for m in models.values():
-            m._rng = r
+        models, _ = rig.seeded_models(cfg, dev, 11, 5)
         runner = trainer.StepRunner(cfg, models, trainer.build_optimizers(cfg, models, data_parallel=dp), trainer.build_loss(cfg), sync_losses=True, side_streams=side_streams)
         assert (runner._lanes is not None) == side_streams
         losses = [runner.step(xc, xg, 2 + i) for i in range(2)]

@@ -7,6 +7,8 @@ library's build flag cannot reach; this removes them from the parameter path (an
 import pytest
 import torch
 
+from tests import rig
+
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 
@@ -14,20 +16,14 @@ DEV = torch.device("cuda:0")
 def _run(cfg_name, B, own, cl=False, steps=2):
     from dcvgan_amd import ops, ops_cl, trainer
     from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
     dev = torch.device("cuda:0")
     cfg = CONFIGS[cfg_name].scaled(batchsize=B)
-    g = torch.Generator().manual_seed(3)
-    xc = (torch.rand(B, 3, 16, 64, 64, generator=g) * 2 - 1).to(dev); xg = (torch.rand(B, cfg.channel, 16, 64, 64, generator=g) * 2 - 1).to(dev)
+    xc, xg = rig.clip_pair(cfg, dev, 3, batch=B)
     old = ops._OWN_ACCUMULATION
     ops._OWN_ACCUMULATION = own
     ops_cl.enable(cl)
     try:
-        torch.manual_seed(11)
-        models = trainer.build_models(cfg, dev)
-        r = PhiloxRng(5)
-        for m in models.values():
-            m._rng = r
+        models, _ = rig.seeded_models(cfg, dev, 11, 5)
         runner = trainer.StepRunner(cfg, models, trainer.build_optimizers(cfg, models), trainer.build_loss(cfg), sync_losses=True)
         losses = [runner.step(xc, xg, 2 + i) for i in range(steps)]
         grads = {f"{k}.{n}": p.grad.detach().clone().cpu() for k, m in models.items() for n, p in m.named_parameters() if p.grad is not None}
@@ -40,22 +36,15 @@ def _run(cfg_name, B, own, cl=False, steps=2):
 
 def _run_schedule(name, B, companion, cl):
     from dcvgan_amd import native, ops, ops_cl, trainer
-    from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
     native.lib()
     old = (ops._WGRAD_SIDE, ops_cl._WGRAD_SIDE)
     ops._WGRAD_SIDE = companion
     ops_cl.enable(cl)
     try:
-        cfg = CONFIGS[name].scaled(batchsize=B, width_div=2)
-        torch.manual_seed(5)
-        models = trainer.build_models(cfg, DEV)
-        r = PhiloxRng(17)
-        for m in models.values():
-            m._rng = r
+        cfg = rig.small_cfg(name, B, 2)
+        models, _ = rig.seeded_models(cfg, DEV, 5, 17)
         runner = trainer.StepRunner(cfg, models, trainer.build_optimizers(cfg, models), trainer.build_loss(cfg), sync_losses=True)
-        g = torch.Generator().manual_seed(6)
-        xc = (torch.rand(B, 3, 16, 64, 64, generator=g) * 2 - 1).to(DEV); xg = (torch.rand(B, cfg.channel, 16, 64, 64, generator=g) * 2 - 1).to(DEV)
+        xc, xg = rig.clip_pair(cfg, DEV, 6, batch=B)
         outs = [runner.step(xc, xg, t) for t in (2, 9, 5)]
         return outs, torch.cat([p.detach().reshape(-1) for m in models.values() for p in m.parameters()]).clone()
     finally:
@@ -91,15 +80,9 @@ def test_no_torch_add_for_parameter_gradients():
 
     def adds(own):
         from dcvgan_amd import ops, trainer
-        from dcvgan_amd.configs import CONFIGS
-        from dcvgan_amd.rng import PhiloxRng
         dev = torch.device("cuda:0")
-        cfg = CONFIGS["isogd-depth"].scaled(batchsize=2, width_div=4)
-        torch.manual_seed(1)
-        models = trainer.build_models(cfg, dev)
-        r = PhiloxRng(5)
-        for m in models.values():
-            m._rng = r
+        cfg = rig.small_cfg(width_div=4)
+        models, _ = rig.seeded_models(cfg, dev, 1, 5)
         xc = torch.rand(2, 3, 16, 64, 64, device=dev) * 2 - 1; xg = torch.rand(2, 1, 16, 64, 64, device=dev) * 2 - 1
         old = ops._OWN_ACCUMULATION
         ops._OWN_ACCUMULATION = own
@@ -126,18 +109,12 @@ def test_no_torch_compute_kernel_in_the_iteration(config, cl):
     (ops.fan_out), the tiled latents (ops.tile_rows) and the backward roots are the library's; what torch still does is memory copies (the loss mirrors)."""
     from torch.profiler import ProfilerActivity, profile
     from dcvgan_amd import trainer
-    from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
     from dcvgan_amd import ops_cl
     dev = torch.device("cuda:0")
-    cfg = CONFIGS[config].scaled(batchsize=2, width_div=4)
-    torch.manual_seed(1)
+    cfg = rig.small_cfg(config, width_div=4)
     ops_cl.enable(cl)
     try:
-        models = trainer.build_models(cfg, dev)
-        r = PhiloxRng(5)
-        for m in models.values():
-            m._rng = r
+        models, _ = rig.seeded_models(cfg, dev, 1, 5)
         xc = torch.rand(2, 3, 16, 64, 64, device=dev) * 2 - 1; xg = torch.rand(2, cfg.channel, 16, 64, 64, device=dev) * 2 - 1
         runner = trainer.StepRunner(cfg, models, trainer.build_optimizers(cfg, models), trainer.build_loss(cfg), sync_losses=False)
         for t in (1, 2):      # both parities of the update gating (surreal-depth1: the D phase's backward every second iteration), Adam state exists

@@ -1,32 +1,17 @@
 """GPU, two ranks on one card (gloo): a GradGuard per phase under data parallelism.  guard.measure() reduces the bucket first and measures the averaged
 gradient, so one rank's inf reaches every rank's measurement and all of them skip the same step.  The ranks are fresh child processes."""
-import json
 import math
-import os
-import socket
 import struct
-import subprocess
-import sys
 
 import pytest
 
+from tests import rig
+
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def test_one_ranks_inf_skips_the_step_on_every_rank(tmp_path):
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    outs = [str(tmp_path / f"guard{r}.json") for r in range(2)]
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "grad_guard_dp_worker.py"), str(r), "2", str(port), outs[r]], env=env) for r in range(2)]
-    try:
-        for p in procs:
-            assert p.wait(timeout=600) == 0
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    a, b = [json.load(open(o)) for o in outs]
+    a, b = rig.run_ranks("grad_guard_dp_worker.py", tmp_path, tag="guard", timeout=600)
     for r in (a, b):
         assert r["skipped_total"] == [0.0, 1.0], r                      # D guard never, G guard once
         assert r["skipped"] == [[0.0, 0.0], [0.0, 1.0], [0.0, 0.0]], r

@@ -13,6 +13,7 @@ import math
 import pytest
 import torch
 
+from tests import rig
 from tests.test_adam_gpu import SIZES
 
 pytestmark = pytest.mark.gpu
@@ -276,24 +277,15 @@ def test_no_host_wait_and_launch_counts():
 # the training iteration
 # --------------------------------------------------------------------------------------------------------------------------------------------------------- #
 def _setup(width_div=8):
-    from dcvgan_amd import trainer
-    from dcvgan_amd.configs import CONFIGS
     dev = torch.device("cuda:0")
-    cfg = CONFIGS["isogd-depth"].scaled(batchsize=2, width_div=width_div)
-    torch.manual_seed(cfg.seed)
-    models = trainer.build_models(cfg, dev)
-    g = torch.Generator().manual_seed(cfg.seed)
-    xc = (torch.rand(2, 3, 16, 64, 64, generator=g) * 2 - 1).to(dev)
-    xg = (torch.rand(2, 1, 16, 64, 64, generator=g) * 2 - 1).to(dev)
-    return cfg, models, xc, xg
+    cfg = rig.small_cfg(width_div=width_div)
+    models, _ = rig.seeded_models(cfg, dev, cfg.seed, 1234)
+    return (cfg, models) + rig.clip_pair(cfg, dev, cfg.seed, geo_channels=1)
 
 
 def _runner(cfg, models, guard):
     from dcvgan_amd import trainer
-    from dcvgan_amd.rng import PhiloxRng
-    r = PhiloxRng(1234)
-    for m in models.values():
-        m._rng = r
+    rig.share_rng(models, 1234)      # a fresh stream for every runner over these models
     opts = trainer.build_optimizers(cfg, models, guard=guard)
     return trainer.StepRunner(cfg, models, opts, trainer.build_loss(cfg)), opts
 

@@ -3,36 +3,18 @@ over the feature's own process group, so every rank holds the anchors of one pro
 they are without the feature.  The logits of the first leg are multiples of 2^-8 below 8 in magnitude, so every sum is exact in any order
 (tests/test_lecam_cpu.py::test_exact_logits_sum_exactly).  The two ranks are fresh child processes, started once for this module; the parent waits for each with a
 limit, kills leftovers, never retries."""
-import json
-import os
-import socket
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
+from tests import rig
 from tests import test_lecam_cpu as R
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 @pytest.fixture(scope="module")
 def ranks(tmp_path_factory):
-    tmp = tmp_path_factory.mktemp("lecam_dp")
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    outs = [str(tmp / f"lecam{r}.json") for r in range(2)]
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "lecam_dp_worker.py"), str(r), "2", str(port), outs[r]], env=env) for r in range(2)]
-    try:
-        for p in procs:
-            assert p.wait(timeout=300) == 0
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    return [json.load(open(o)) for o in outs]
+    return rig.run_ranks("lecam_dp_worker.py", tmp_path_factory.mktemp("lecam_dp"), tag="lecam", timeout=300)
 
 
 def test_every_rank_holds_the_anchors_of_one_process_on_the_concatenated_logits(ranks):

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import rig
 from tests import test_lecam_cpu as R
 
 pytestmark = pytest.mark.gpu
@@ -155,15 +156,9 @@ def test_non_finite_mean_freezes_that_discriminator_only():
 # ---- 4. - 6. the iteration ------------------------------------------------------------------------------------------------------------------------------------
 def _runner(lecam_kw, seed=21, pass_arg=True, sync_losses=False):
     from dcvgan_amd import native, trainer
-    from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
     native.lib()
-    cfg = CONFIGS["isogd-depth"].scaled(batchsize=2, width_div=8)
-    torch.manual_seed(seed)
-    models = trainer.build_models(cfg, DEV)
-    r = PhiloxRng(9)
-    for m in models.values():
-        m._rng = r
+    cfg = rig.small_cfg()
+    models, _ = rig.seeded_models(cfg, DEV, seed, 9)
     opts = trainer.build_optimizers(cfg, models)
     lc = trainer.build_lecam(cfg, models, opts, **lecam_kw) if lecam_kw is not None else None
     kw = dict(lecam=lc) if pass_arg else {}
@@ -171,36 +166,11 @@ def _runner(lecam_kw, seed=21, pass_arg=True, sync_losses=False):
 
 
 def _data(cfg):
-    g = torch.Generator().manual_seed(4)
-    return (torch.rand(2, 3, 16, 64, 64, generator=g) * 2 - 1).to(DEV), (torch.rand(2, cfg.channel, 16, 64, 64, generator=g) * 2 - 1).to(DEV)
+    return rig.clip_pair(cfg, DEV, 4)
 
 
-def _counted_steps(runner, xc, xg, ts):
-    from dcvgan_amd import native
-    counts, outs = [], []
-    torch.cuda.set_sync_debug_mode("error")
-    try:
-        for t in ts:
-            n0 = native.launch_count()
-            outs.append(runner.step(xc, xg, t))
-            counts.append(native.launch_count() - n0)
-    finally:
-        torch.cuda.set_sync_debug_mode("default")
-    return counts, outs
-
-
-def _snapshot(models, opts):
-    """Every parameter, buffer and Adam moment, as bytes."""
-    from dcvgan_amd import trainer
-    torch.cuda.synchronize()
-    snap = {}
-    for n in trainer.MODEL_NAMES:
-        for k, v in models[n].state_dict().items():
-            snap[(n, k)] = v.detach().cpu().reshape(-1).view(torch.uint8).clone()
-        for i, p in enumerate(models[n].parameters()):
-            s = opts[n].state[p]
-            snap[(n, i, "m")], snap[(n, i, "v")] = s["exp_avg"].cpu().reshape(-1).view(torch.uint8).clone(), s["exp_avg_sq"].cpu().reshape(-1).view(torch.uint8).clone()
-    return snap
+_counted_steps = rig.counted_steps
+_snapshot = rig.state_bytes      # every parameter, buffer and Adam moment, as bytes
 
 
 def _loss_bits(out):

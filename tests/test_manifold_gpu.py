@@ -6,6 +6,7 @@ and, their closest margin asserted first, to exact counts and metrics.  Measured
 import numpy as np
 import pytest
 
+from tests import rig
 from tests import test_manifold_cpu as R
 
 pytestmark = pytest.mark.gpu
@@ -234,14 +235,8 @@ def test_evaluator_reports_the_four_metrics(dev):
     views of the clip; the four keys are manifold_metrics on the stored buffers."""
     import torch
     from dcvgan_amd import evaluation as E, native, trainer
-    from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
-    cfg = CONFIGS["isogd-depth"].scaled(batchsize=2, width_div=8)
-    torch.manual_seed(cfg.seed)
-    models = trainer.build_models(cfg, dev)
-    r = PhiloxRng(123)
-    for m in models.values():
-        m._rng = r
+    cfg = rig.small_cfg()
+    models, _ = rig.seeded_models(cfg, dev, cfg.seed, 123)
 
     def extractor(xc):
         flat = xc.permute(0, 2, 1, 3, 4).reshape(xc.shape[0], -1)

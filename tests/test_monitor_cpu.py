@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import rig
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("dcv_monitor_observe", "dcv_monitor_roll", "dcv_hist_u8", "dcv_video_grid_u8")
 CPU = torch.device("cpu")
@@ -231,14 +233,8 @@ def test_run_monitor_refuses_cpu_tensors_and_bad_arguments():
 
 def _host_run(seed, monitor, guard=None, lecam=False):
     from dcvgan_amd import trainer
-    from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
-    cfg = CONFIGS["isogd-depth"].scaled(batchsize=2, width_div=8)
-    torch.manual_seed(seed)
-    models = trainer.build_models(cfg, CPU)
-    r = PhiloxRng(seed + 100)
-    for m in models.values():
-        m._rng = r
+    cfg = rig.small_cfg()
+    models, _ = rig.seeded_models(cfg, CPU, seed, seed + 100)
     opts = trainer.build_optimizers(cfg, models, guard=guard)
     lc = trainer.build_lecam(cfg, models, opts, weight=0.3, start=0) if lecam else None
     mon = trainer.build_monitor(cfg, models, opts, interval=7, lecam=lc, ring=3) if monitor else None

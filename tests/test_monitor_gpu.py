@@ -1,5 +1,6 @@
 """GPU: dcv_monitor_observe / dcv_monitor_roll / dcv_hist_u8 / dcv_video_grid_u8 against their numpy mirrors (dcvgan_amd.monitor, checked on the CPU by
 tests/test_monitor_cpu.py) with exact equality, the monitored iteration, RunState with a monitor, and sample_log end to end."""
+import functools
 import math
 import re
 
@@ -7,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import rig
 from tests.test_monitor_cpu import compat_grid
 
 pytestmark = pytest.mark.gpu
@@ -223,15 +225,9 @@ def test_no_host_read_no_torch_kernel():
 # ---- 4. the iteration ---------------------------------------------------------------------------------------------------------------------------------------------
 def _runner(monitor, seed=21, guard=None, lecam_kw=None, interval=2, **cfg_kw):
     from dcvgan_amd import native, trainer
-    from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
     native.lib()
-    cfg = CONFIGS["isogd-depth"].scaled(batchsize=2, width_div=8, **cfg_kw)
-    torch.manual_seed(seed)
-    models = trainer.build_models(cfg, DEV)
-    r = PhiloxRng(9)
-    for m in models.values():
-        m._rng = r
+    cfg = rig.small_cfg(**cfg_kw)
+    models, _ = rig.seeded_models(cfg, DEV, seed, 9)
     opts = trainer.build_optimizers(cfg, models, guard=guard)
     lc = trainer.build_lecam(cfg, models, opts, **lecam_kw) if lecam_kw is not None else None
     mon = trainer.build_monitor(cfg, models, opts, interval=interval, lecam=lc) if monitor else None
@@ -241,30 +237,12 @@ def _runner(monitor, seed=21, guard=None, lecam_kw=None, interval=2, **cfg_kw):
 
 
 def _data(cfg):
-    g = torch.Generator().manual_seed(4)
-    return (torch.rand(2, 3, 16, 64, 64, generator=g) * 2 - 1).to(DEV), (torch.rand(2, cfg.channel, 16, 64, 64, generator=g) * 2 - 1).to(DEV)
+    return rig.clip_pair(cfg, DEV, 4)
 
 
-def _model_bytes(models):
-    from dcvgan_amd import trainer
-    torch.cuda.synchronize()
-    return {(n, k): v.detach().cpu().reshape(-1).view(torch.uint8).clone() for n in trainer.MODEL_NAMES for k, v in models[n].state_dict().items()}
-
-
-def _counted_steps(runner, xc, xg, ts):
-    """The library's launches per iteration; from the second iteration on (the first makes optimiser state, workspaces and pointer tables) no host sync is allowed."""
-    from dcvgan_amd import native
-    counts, outs = [], []
-    try:
-        for k, t in enumerate(ts):
-            if k == 1:
-                torch.cuda.set_sync_debug_mode("error")
-            n0 = native.launch_count()
-            outs.append(runner.step(xc, xg, t))
-            counts.append(native.launch_count() - n0)
-    finally:
-        torch.cuda.set_sync_debug_mode("default")
-    return counts, outs
+_model_bytes = rig.state_bytes
+# the library's launches per iteration; from the second iteration on (the first makes optimiser state, workspaces and pointer tables) no host sync is allowed
+_counted_steps = functools.partial(rig.counted_steps, strict_from=1)
 
 
 def _hook_logits(models):

@@ -7,6 +7,7 @@ and every other one, or an exact tie between centroids with integer coordinates.
 import numpy as np
 import pytest
 
+from tests import rig
 from tests import test_prd_cpu as R
 from tests.test_manifold_gpu import shifted, strided, to_dev
 
@@ -332,14 +333,8 @@ def test_evaluator_reports_the_two_scores(dev):
     """Generators of the smallest configuration the suite builds; 12 real clips, 70 samples in batches of 10.  The extractor returns free views of the clip."""
     import torch
     from dcvgan_amd import evaluation as E, native, trainer
-    from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
-    cfg = CONFIGS["isogd-depth"].scaled(batchsize=2, width_div=8)
-    torch.manual_seed(cfg.seed)
-    models = trainer.build_models(cfg, dev)
-    r = PhiloxRng(123)
-    for m in models.values():
-        m._rng = r
+    cfg = rig.small_cfg()
+    models, _ = rig.seeded_models(cfg, dev, cfg.seed, 123)
 
     def extractor(xc):
         flat = xc.permute(0, 2, 1, 3, 4).reshape(xc.shape[0], -1)

@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import rig
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("dcv_state_workspace_bytes", "dcv_state_pack_multi", "dcv_state_unpack_multi", "dcv_state_digest_multi")
 M64 = (1 << 64) - 1
@@ -268,14 +270,8 @@ def test_philox_and_guard_round_trips():
 def _host_run(seed, width_div=8, guard=None, options=True, stepped=True):
     """Models, optimisers and every optional component on the host, with Adam state as after `3` steps (made up: nothing trains on the CPU)."""
     from dcvgan_amd import trainer
-    from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
-    cfg = CONFIGS["isogd-depth"].scaled(batchsize=2, width_div=width_div)
-    torch.manual_seed(seed)
-    models = trainer.build_models(cfg, CPU)
-    r = PhiloxRng(seed + 100)
-    for m in models.values():
-        m._rng = r
+    cfg = rig.small_cfg(width_div=width_div)
+    models, r = rig.seeded_models(cfg, CPU, seed, seed + 100)
     opts = trainer.build_optimizers(cfg, models, guard=guard)
     sn = trainer.build_spectral_norm(cfg, models, opts) if options else None
     if stepped:

@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import rig
+
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 PAD = 8                          # dwords of sentinel on either side of every tensor a kernel reads or writes (32 bytes: the 16-byte grid is kept)
@@ -127,15 +129,10 @@ def _build(seed, options, name="isogd-depth"):
     ClipSampler over five 20-frame videos; without them fixed batches.  t_rand comes from a random stream of the caller's (`free`, no fixed seed: it follows
     torch's) and a count kept in `extra`."""
     from dcvgan_amd import clipstore, native, trainer
-    from dcvgan_amd.configs import CONFIGS
     from dcvgan_amd.rng import PhiloxRng
     native.lib()
-    cfg = CONFIGS[name].scaled(batchsize=2, width_div=8)
-    torch.manual_seed(seed)
-    models = trainer.build_models(cfg, DEV)
-    r = PhiloxRng(seed + 50)
-    for m in models.values():
-        m._rng = r
+    cfg = rig.small_cfg(name)
+    models, _ = rig.seeded_models(cfg, DEV, seed, seed + 50)
     opts = trainer.build_optimizers(cfg, models, guard=dict(max_norm=10.0, dynamic=True, loss_scale=4.0, growth_interval=2) if options else None)
     sn = ema = aug = lc = sampler = data = None
     if options:
@@ -146,8 +143,7 @@ def _build(seed, options, name="isogd-depth"):
         store = clipstore.ClipStore.from_arrays(_videos(np.random.default_rng(77), cfg), cfg.video_length, cfg.geometric_info, DEV)
         sampler = trainer.build_clip_sampler(cfg, store, seed=seed + 9, rank=0, world=1)
     else:
-        g = torch.Generator().manual_seed(4)
-        data = ((torch.rand(2, 3, 16, 64, 64, generator=g) * 2 - 1).to(DEV), (torch.rand(2, cfg.channel, 16, 64, 64, generator=g) * 2 - 1).to(DEV))
+        data = rig.clip_pair(cfg, DEV, 4)
     runner = trainer.StepRunner(cfg, models, opts, trainer.build_loss(cfg), ema=ema, spectral=sn, augment=aug, lecam=lc)
     free, extra = PhiloxRng(), {"t_count": 0, "seed": seed}
     rs = trainer.build_run_state(cfg, models, opts, runner=runner, ema=ema, spectral=sn, augment=aug, lecam=lc, sampler=sampler, rngs=(free,), extra=extra)
@@ -177,7 +173,7 @@ def _iterate(run, n, fingerprints=None):
 def _all_bytes(run):
     torch.cuda.synchronize()
     lay = run["rs"]._layout()
-    return {n: t.detach().cpu().reshape(-1).view(torch.uint8).clone() for n, t in zip(lay.names, lay.tensors)}
+    return {n: rig.byte_view(t).clone() for n, t in zip(lay.names, lay.tensors)}
 
 
 def _host_state(run):

@@ -8,6 +8,8 @@ tests/test_abi_cpu.py::test_library_has_no_packed_fp32_arithmetic looks at the s
 import pytest
 import torch
 
+from tests import rig
+
 pytestmark = pytest.mark.gpu
 
 
@@ -15,22 +17,16 @@ pytestmark = pytest.mark.gpu
 def test_iterations_are_bitwise_repeatable_on_side_streams(mode):
     from dcvgan_amd import native, trainer
     from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
     native.lib()
     native.set_precision(mode)
     try:
         dev = torch.device("cuda:0")
         B = 16
         cfg = CONFIGS["surreal-depth1"].scaled(batchsize=B)
-        g = torch.Generator().manual_seed(3)
-        xc = (torch.rand(B, 3, 16, 64, 64, generator=g) * 2 - 1).to(dev); xg = (torch.rand(B, cfg.channel, 16, 64, 64, generator=g) * 2 - 1).to(dev)
+        xc, xg = rig.clip_pair(cfg, dev, 3, batch=B)
 
         def run(side_streams):
-            torch.manual_seed(11)
-            models = trainer.build_models(cfg, dev)
-            r = PhiloxRng(5)
-            for m in models.values():
-                m._rng = r
+            models, _ = rig.seeded_models(cfg, dev, 11, 5)
             runner = trainer.StepRunner(cfg, models, trainer.build_optimizers(cfg, models), trainer.build_loss(cfg), sync_losses=True, side_streams=side_streams)
             losses = [runner.step(xc, xg, 2 + i) for i in range(2)]
             return losses, torch.cat([v.detach().float().reshape(-1) for m in models.values() for v in m.state_dict().values()]).cpu()
@@ -49,19 +45,14 @@ def test_a_module_at_another_precision_on_the_next_stream_changes_nothing():
     With packed-FP32 code in thin_quad_kernel this differed in ~85 % of the trials."""
     from dcvgan_amd import native, trainer, util
     from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
     native.lib()
     native.set_precision("fp32")
     dev = torch.device("cuda:0")
     B = 16
     cfg = CONFIGS["surreal-depth1"].scaled(batchsize=B)
-    g = torch.Generator().manual_seed(3)
-    xc = (torch.rand(B, 3, 16, 64, 64, generator=g) * 2 - 1).to(dev).requires_grad_(True); xg = (torch.rand(B, cfg.channel, 16, 64, 64, generator=g) * 2 - 1).to(dev).requires_grad_(True)
-    torch.manual_seed(11)
-    models = trainer.build_models(cfg, dev)
-    rng = PhiloxRng(5)
+    xc, xg = (x.requires_grad_(True) for x in rig.clip_pair(cfg, dev, 3, batch=B))
+    models, rng = rig.seeded_models(cfg, dev, 11, 5)
     for m in models.values():
-        m._rng = rng
         m.train()
     util.set_precision(models["vdis"], "bf16")
     names = ("vdis", "gdis")

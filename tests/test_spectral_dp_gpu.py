@@ -2,31 +2,15 @@
 kernels on the same bits, so the weights, u, v, sigma and W / sigma are bit-identical across the ranks without a collective of their own — with plain buckets and
 with collectives overlapped with the backward; one rank's inf reaches every rank's D measurement, so every rank skips the three D steps AND the power iteration.
 The ranks are fresh child processes; the parent waits with a limit, kills leftovers, never retries."""
-import json
-import os
-import socket
-import subprocess
-import sys
-
 import pytest
 
+from tests import rig
+
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def _two_ranks(tmp_path, mode):
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    outs = [str(tmp_path / f"sn_{mode}{r}.json") for r in range(2)]
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "spectral_dp_worker.py"), str(r), "2", str(port), outs[r], mode], env=env) for r in range(2)]
-    try:
-        for p in procs:
-            assert p.wait(timeout=600) == 0
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    return [json.load(open(o)) for o in outs]
+    return rig.run_ranks("spectral_dp_worker.py", tmp_path, mode, tag=f"sn_{mode}", timeout=600)
 
 
 @pytest.mark.parametrize("mode", ["plain", "overlap"])

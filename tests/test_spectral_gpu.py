@@ -16,6 +16,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import rig
+
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 EPS = 1e-12
@@ -475,15 +477,9 @@ def test_module_plumbing(kind):
 # ---- 7. the iteration -----------------------------------------------------------------------------------------------------------------------------------------
 def _runner(marked, seed=21, spectral_kw=True):
     from dcvgan_amd import native, trainer
-    from dcvgan_amd.configs import CONFIGS
-    from dcvgan_amd.rng import PhiloxRng
     native.lib()
-    cfg = CONFIGS["isogd-depth"].scaled(batchsize=2, width_div=8)
-    torch.manual_seed(seed)
-    models = trainer.build_models(cfg, DEV)
-    r = PhiloxRng(9)
-    for m in models.values():
-        m._rng = r
+    cfg = rig.small_cfg()
+    models, _ = rig.seeded_models(cfg, DEV, seed, 9)
     opts = trainer.build_optimizers(cfg, models, guard=dict(max_norm=10.0))
     sn = trainer.build_spectral_norm(cfg, models, opts, seed=4) if marked else None
     kw = dict(spectral=sn) if spectral_kw else {}
@@ -491,22 +487,10 @@ def _runner(marked, seed=21, spectral_kw=True):
 
 
 def _data(cfg):
-    g = torch.Generator().manual_seed(4)
-    return (torch.rand(2, 3, 16, 64, 64, generator=g) * 2 - 1).to(DEV), (torch.rand(2, cfg.channel, 16, 64, 64, generator=g) * 2 - 1).to(DEV)
+    return rig.clip_pair(cfg, DEV, 4)
 
 
-def _counted_steps(runner, xc, xg, ts):
-    from dcvgan_amd import native
-    counts, outs = [], []
-    torch.cuda.set_sync_debug_mode("error")
-    try:
-        for t in ts:
-            n0 = native.launch_count()
-            outs.append(runner.step(xc, xg, t))
-            counts.append(native.launch_count() - n0)
-    finally:
-        torch.cuda.set_sync_debug_mode("default")
-    return counts, outs
+_counted_steps = rig.counted_steps
 
 
 def test_iteration():

@@ -2,33 +2,16 @@
 The ranks are fresh child processes (tests/sync_bn_worker.py; never a re-exec of this one); the parent waits with a limit, kills leftovers and never retries.
 
 Bars (tests/test_ops_gpu.py::test_bn_act's): rel() < 1e-3 on outputs and gradients, < 1e-5 on the running statistics."""
-import json
-import os
-import socket
-import subprocess
-import sys
-
 import pytest
 
+from tests import rig
+
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 TOL, TOL_STATS = 1e-3, 1e-5
 
 
 def _run(mode, tmp_path):
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    outs = [str(tmp_path / f"{mode}{r}.json") for r in range(2)]
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "sync_bn_worker.py"), str(r), "2", str(port), mode, outs[r]], env=env) for r in range(2)]
-    try:
-        for p in procs:
-            assert p.wait(timeout=300) == 0
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-                p.wait()
-    return [json.load(open(o)) for o in outs]
+    return rig.run_ranks("sync_bn_worker.py", tmp_path, mode, tag=mode, timeout=300)
 
 
 @pytest.mark.parametrize("split", ["2+2", "3+1"])
