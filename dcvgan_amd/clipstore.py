@@ -346,6 +346,11 @@ class ClipStore:
     def launches_per_gather(self) -> int:
         return 3 if self.surreal else 2
 
+    def nearest(self, queries: torch.Tensor, k: int = 1, stream: str = "colour", exclude=None, max_workspace_bytes: int = 1 << 30):
+        """The k nearest training windows of every query clip, over every window of every video: clipnn.nearest_windows(self, ...)."""
+        from . import clipnn
+        return clipnn.nearest_windows(self, queries, k, stream, exclude, max_workspace_bytes)
+
 
 # --------------------------------------------------------------------------- #
 # the sampler

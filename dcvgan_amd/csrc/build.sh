@@ -18,7 +18,7 @@ NOPK="-Xclang -target-feature -Xclang -packed-fp32-ops"
 FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -I$ROOT/include -I$HERE -Wall -Wno-unused-function -mllvm -amdgpu-mfma-vgpr-form $NOPK"
 mkdir -p "$OBJ"
 pids=()
-for f in conv_mfma elementwise conv_cl16 cl_elementwise augment lecam clipstore evalstats evalknn evalprd runstate monitor; do
+for f in conv_mfma elementwise conv_cl16 cl_elementwise augment lecam clipstore evalstats evalknn evalprd runstate monitor clipnn; do
   if [ ! -f "$OBJ/$f.o" ] || [ "$HERE/$f.hip" -nt "$OBJ/$f.o" ] || [ "$HERE/dcv_common.h" -nt "$OBJ/$f.o" ] || [ "$ROOT/include/dcvgan_hip.h" -nt "$OBJ/$f.o" ]; then
     hipcc $FLAGS ${EXTRA_HIPCC_FLAGS:-} -c "$HERE/$f.hip" -o "$OBJ/$f.o" 2> >(grep -v "not a recognized feature for this target" >&2) &
     pids+=($!)
@@ -32,7 +32,7 @@ for f in conv_cl16 cl_elementwise; do
   fi
 done
 for p in "${pids[@]:-}"; do [ -n "$p" ] && { wait "$p" || exit 1; }; done
-hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT" "$OBJ/conv_mfma.o" "$OBJ/elementwise.o" "$OBJ/conv_cl16.o" "$OBJ/cl_elementwise.o" "$OBJ/conv_cl16_f16.o" "$OBJ/cl_elementwise_f16.o" "$OBJ/augment.o" "$OBJ/lecam.o" "$OBJ/clipstore.o" "$OBJ/evalstats.o" "$OBJ/evalknn.o" "$OBJ/evalprd.o" "$OBJ/runstate.o" "$OBJ/monitor.o"
+hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT" "$OBJ/conv_mfma.o" "$OBJ/elementwise.o" "$OBJ/conv_cl16.o" "$OBJ/cl_elementwise.o" "$OBJ/conv_cl16_f16.o" "$OBJ/cl_elementwise_f16.o" "$OBJ/augment.o" "$OBJ/lecam.o" "$OBJ/clipstore.o" "$OBJ/evalstats.o" "$OBJ/evalknn.o" "$OBJ/evalprd.o" "$OBJ/runstate.o" "$OBJ/monitor.o" "$OBJ/clipnn.o"
 # The flag above is only worth something if it took effect (its "not a recognized feature" host-pass message is filtered, and a hipcc that dropped or renamed
 # the feature would bring the packed instructions back silently): disassemble the device code of the library just linked and fail on any packed-FP32 arithmetic.
 OBJDUMP=/opt/rocm/lib/llvm/bin/llvm-objdump

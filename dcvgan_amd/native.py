@@ -160,6 +160,12 @@ _SIGS = {
     "dcv_clipstore_draw": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_uint64, C.c_uint64, C.c_int64, _P]),
     "dcv_clipstore_gather": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P]),
     "dcv_clipstore_surreal": (C.c_int, [_P, C.c_int, C.c_int64, _P]),
+    # nearest-training-clip search on the device-resident dataset (added symbols only: the ABI version stays 4)
+    "dcv_clipnn_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int64]),
+    "dcv_clipnn_pack_queries": (C.c_int, [_P, C.c_int, _D, _P, _P]),
+    "dcv_clipnn_search": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int64, C.c_int64,
+                                    _P, _P, _P, C.c_size_t, _P]),
+    "dcv_clipnn_gather_u8": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     # on-device evaluation statistics: Inception score, Fréchet and kernel distance (added symbols only: the ABI version stays 4)
     "dcv_eval_moments_update": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int64, _P, _P, _P]),
     "dcv_eval_inception_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),

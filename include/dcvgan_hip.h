@@ -564,6 +564,42 @@ int dcv_clipstore_gather(const void* frames, int mode, const int32_t* table, con
  * (< 1e10) min-max of the WINDOW goes to [-1, 0.8], background 1.0 — dcv_surreal_depth's arithmetic.  One launch, one workgroup per clip. */
 int dcv_clipstore_surreal(float* clips, int B, int64_t per_clip, void* stream);
 
+/* ---- nearest-training-clip search on the device-resident dataset (added symbols only: the ABI version stays 4) ------ *
+ * "Are the samples copies of training clips?"  The reference has no counterpart: it never compares a sample with the training set.  The store is a packed uint8
+ * stream as above, frames of K = H*W*C bytes in disk order (H, W, C); a query clip is T frames of K bytes in the same order.  For a window (v, s), 0 <= s <= n_v - T:
+ *   d(q, v, s) = sum_{t < T} sum_{j < K} ((int)q[t][j] - (int)frame[starts[v] + s + t][j])^2                                  (int64, exact)
+ * and a query's result is the k windows with the smallest (d, v, s) in lexicographic order, except those of video exclude[q] (if >= 0); windows never cross a video
+ * boundary; places beyond the admissible windows hold rows (-1, -1) and distance INT64_MAX.
+ * Arithmetic: bytes are shifted to int8 (x ^ 0x80 = x - 128) and a frame pair's distance is |a'|^2 + |b'|^2 - 2 a'.b' (independent of the shift), the dot on
+ * v_mfma_i32_32x32x32_i8 with an int32 accumulator — exact while K <= 65536 (128 * 128 * 65536 = 2^30) — and both norms int32 sums over the same loaded bytes;
+ * bytes padded beyond K are zero AFTER the shift.  Clip distances are int64 sums of T uint32 frame distances.  No atomics; the chunking changes no output bit. */
+/* Bytes of workspace dcv_clipnn_search needs for n queries when a call covers chunk_frames window starts: the running best (n k int64), the workgroups' candidates
+ * (2 n k ceil(chunk_frames / 1024) int64) and the uint32 frame distances (n T rows of chunk_frames + T - 1 columns, rounded up to 64).  0 with dcv_last_error set
+ * unless 1 <= n <= 65535, 1 <= T <= 4096, n T < 2^24, 1 <= k <= 8, 1 <= chunk_frames < 2^30.  Host arithmetic only. */
+size_t dcv_clipnn_workspace_bytes(int n, int T, int k, int64_t chunk_frames);
+/* Queries (n, C, T, H, W) with the element strides of xd, uint8 (is_f32 = 0: copied) or fp32 (is_f32 = 1: uint8((clip(x,-1,1)+1)/2*255) in dcv_videos_to_uint8's
+ * fp32 operation order, bytes identical) -> out: n T frames of H*W*C bytes in disk order (H, W, C), contiguous.  One launch, one thread per byte.
+ * DCV_EINVAL before the launch: a NULL pointer, is_f32 outside {0, 1}, an extent < 1, C > 4, fp32 data off a 4-byte boundary; DCV_EUNSUPPORTED: H*W*C > 65536. */
+int dcv_clipnn_pack_queries(const void* x, int is_f32, const dcv_dims5* xd, uint8_t* out, void* stream);
+/* One chunk of a search: window starts chunk_start .. chunk_start + chunk_frames - 1 of the packed buffer of F = starts[N] frames (a window start is a frame
+ * index f with f + T <= F; those whose T frames span two videos are masked out).  A search is the calls chunk_start = 0, chunk_frames, 2 chunk_frames, ... while
+ * chunk_start <= F - T, in that order, with the same arguments and workspace: the call with chunk_start = 0 starts the running best, the others merge into it, and
+ * after the last one rows (n, k, 2) int32 = (video, t0) and dist (n, k) int64 hold the result — the same bits for every chunk_frames.
+ * The query clips are `queries` (n T packed frames, dcv_clipnn_pack_queries) or, with queries NULL, the windows that the (n, 2) int32 table `qtable` names in the
+ * store itself; a table row that names no T frames of one video is read as nothing and gets no window at all.  exclude: NULL, or query q excludes video
+ * exclude[q * exclude_stride] (negative: none); qtable with stride 2 excludes each query's own video.
+ * Three launches: the int8 GEMM (workgroups of 256 query frames x 64 store frames, grid over the chunk's frames and the query tiles; 16-byte fragment loads when
+ * H*W*C % 16 == 0 and both buffers are on 16-byte boundaries, else unaligned and, in the last K step, single-byte loads), the diagonal sums with the per-workgroup
+ * k best, the merge.  DCV_EINVAL before any launch: a NULL or misaligned pointer, both or neither of queries / qtable, an extent or count outside the limits of
+ * dcv_clipnn_workspace_bytes, C outside 1..4, N or F outside [1, 2^31), F < T, chunk_start not a multiple of chunk_frames inside [0, F - T]; DCV_EUNSUPPORTED:
+ * H*W*C > 65536; DCV_EWORKSPACE: fewer than dcv_clipnn_workspace_bytes bytes. */
+int dcv_clipnn_search(const uint8_t* frames, const int64_t* starts, int64_t N, int64_t F, int T, int H, int W, int C, const uint8_t* queries, const int32_t* qtable, int n,
+                      const int32_t* exclude, int exclude_stride, int k, int64_t chunk_start, int64_t chunk_frames, int32_t* rows, int64_t* dist, void* ws,
+                      size_t ws_bytes, void* stream);
+/* out (B, C, T, H, W) uint8 contiguous = the stored bytes of the table's windows of a uint8 stream (F, H, W, C): a copy, no arithmetic.  A row that names no T frames
+ * of one video is written as zeros and nothing is read for it.  One launch.  DCV_EINVAL before it unless 1 <= B <= 65535, T, H, W >= 1, 1 <= C <= 4, 1 <= N < 2^31. */
+int dcv_clipnn_gather_u8(const uint8_t* frames, const int32_t* table, const int64_t* starts, int64_t N, int B, int T, int H, int W, int C, uint8_t* out, void* stream);
+
 /* ---- on-device evaluation statistics: Inception score, Frechet and kernel distance (added symbols only: the ABI version stays 4) ------ *
  * The reference's Trainer.evaluate (trainer.py:171-224) moves the generators to the CPU, writes every generated clip as an mp4 and lets an external package read
  * them back for IS / FID / PRD.  These entries are the dense arithmetic AFTER the feature network (which stays the caller's): they accumulate, in fp64 and in device
